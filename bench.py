@@ -13,6 +13,9 @@ Secondary legs with their own roofline objects: C2 (1024 x 400) and C3 (4096 DNA
 
     python bench.py [--gpus N --steps K --warmup W] [--nseq 4096 --len 400 --dna]
 
+--dump-outputs DIR: after the timed steps, what the last one returned (records, coded paths, gap arrays) as
+DIR/<name>.npy, to compare two builds output for output (see dump_outputs()).
+
 N > 1 (launched by torch.distributed.run, one rank per GPU): see multi_gpu_main() -- ONE guide
 tree (C4's shape) sharded over the ranks by subtree (kalign_amd.dist.sharded_tree) -> strong scaling.
 """
@@ -151,10 +154,40 @@ def timed_tree(ctx, job, subm, scal, steps, warmup, barrier=None):
     if barrier:
         barrier()
     elapsed = time.perf_counter() - t0
-    recs, _, gaps = ctx.tree_download(want_gaps=True)  # (after the clock: the gap arrays are what the CPU leg compares)
+    recs, paths, gaps = ctx.tree_download(want_gaps=True)  # (after the clock: the gap arrays are what the CPU leg compares)
     kern_ms, n_launch = ctx.tree_kernel_ms()          # HIP events on the launch stream, last step
-    return {"elapsed": elapsed, "recs": recs, "gaps": gaps, "kern_ms": kern_ms, "n_launch": n_launch,
+    return {"elapsed": elapsed, "recs": recs, "paths": paths, "gaps": gaps, "kern_ms": kern_ms, "n_launch": n_launch,
             "cells": float(sum(r.len_a * r.len_b for r in recs))}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, recs, paths, gaps=None, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: what the timed path handed its caller after the last step, one float64 .npy per array --
+    records.npy (a row per task, a column per field of ka_task_rec in header order, each 64-bit hash as its high and
+    low 32 bits), paths.npy (every task's coded path, paths[path_off : path_off + plen + 2], in task order) and
+    gaps.npy (every sequence's gap array, in sequence order).  Past `limit` bytes in all, every array keeps the same
+    share of its rows, drawn with a fixed seed; <name>_rows.npy then lists the rows kept."""
+    from kalign_amd import api
+    cols = []
+    for name, ctype in api.TaskRec._fields_:
+        v = np.array([getattr(r, name) for r in recs], np.uint64 if ctype is api.C.c_uint64 else np.float64)
+        cols += [v >> np.uint64(32), v & np.uint64(0xFFFFFFFF)] if v.dtype == np.uint64 else [v]
+    arrays = {"records": np.stack([c.astype(np.float64) for c in cols], axis=1),
+              "paths": np.concatenate([paths[r.path_off:r.path_off + r.plen + 2] for r in recs] or [np.zeros(0)]).astype(np.float64)}
+    if gaps is not None:
+        arrays["gaps"] = np.concatenate(list(gaps) or [np.zeros(0)]).astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    # a kept row costs its bytes plus its index: one fraction for all arrays keeps the sum (headers aside) within `limit`
+    frac = 1.0 if total <= limit else limit / float(sum(a.nbytes + 8 * len(a) for a in arrays.values()))
+    os.makedirs(out_dir, exist_ok=True)
+    for i, (name, a) in enumerate(sorted(arrays.items())):
+        if frac < 1.0:
+            rows = np.sort(np.random.RandomState(seed + i).choice(len(a), int(len(a) * frac), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def roofline_of(res, key, workload=None):
@@ -869,7 +902,10 @@ def main():
     ap.add_argument("--no-c4", action="store_true")
     ap.add_argument("--scale-workload", action="store_true", help="N > 1: shard --nseq x --len instead of C4 (tests)")
     ap.add_argument("--scale-fast", action="store_true", help="N > 1: --fast mode instead of the default mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.quick:
         args.no_legs = args.no_cpu = True
 
@@ -896,6 +932,8 @@ def main():
         torch.cuda.synchronize()
 
     res = timed_tree(ctx, job, subm, scal, args.steps, args.warmup, barrier)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res["recs"], res["paths"], res["gaps"])
     elapsed, cells = res["elapsed"], res["cells"]
     key = "headline" if (args.nseq, args.len, args.dna) == (4096, 400, False) else "other"
     out = {
@@ -1060,6 +1098,8 @@ def multi_gpu_main(args, rank, world, local_rank):
     elapsed = kd.reduce_scalar(time.perf_counter() - t0, "max", device=coll_dev)
     if cd is not None:
         recs, paths = cd.download()                                # (every rank holds every record and path after each step)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, recs, paths)
     cells = float(sum(r.len_a * r.len_b for r in recs))
     pair_cells = 0.0
     if anchors:

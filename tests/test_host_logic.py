@@ -117,3 +117,35 @@ def test_c_subtree_plan_matches_the_python_plan():
             rr_c, top_c = api.dist_plan_subtrees(lens, tasks, world)
             assert list(rr_c) == [int(x) for x in rr_py], (n, world)
             assert top_c == [int(t) for t in top_py], (n, world)
+
+
+def test_bench_dump_outputs_holds_what_the_tree_returned(oracle, tmp_path):
+    """bench.py --dump-outputs: records, coded paths and gap arrays as float64 .npy, exactly; past the size limit a fixed
+    sample of every array's rows, with the rows kept beside it, within the limit."""
+    import os
+    import bench
+    from kalign_amd import api
+    from util import Golden
+    g = Golden("tree_prot32x200")
+    recs, paths, gaps, _ = oracle.msa_tree(g.codes, g.tasks, g.subm, g.scal, g.seq_distances)
+    bench.dump_outputs(str(tmp_path / "all"), recs, paths, gaps)
+    z = {n: np.load(str(tmp_path / "all" / (n + ".npy"))) for n in ("records", "paths", "gaps")}
+    assert sorted(os.listdir(str(tmp_path / "all"))) == ["gaps.npy", "paths.npy", "records.npy"]
+    assert all(a.dtype == np.float64 for a in z.values())
+    names = [n for n, _ in api.TaskRec._fields_]
+    assert z["records"].shape == (len(recs), len(names) + 3)                # three 64-bit hashes, two columns each
+    for r, row in zip(recs, z["records"]):
+        assert row[names.index("plen")] == r.plen and row[names.index("path_off")] == r.path_off
+        assert row[names.index("score")] == r.score and row[names.index("len_b")] == r.len_b
+    assert np.array_equal(z["paths"], np.concatenate([paths[r.path_off:r.path_off + r.plen + 2] for r in recs]))
+    assert np.array_equal(z["gaps"], np.concatenate(gaps))
+    limit = sum(a.nbytes for a in z.values()) // 4
+    for k in range(2):                                                      # the same sample every time
+        bench.dump_outputs(str(tmp_path / ("cut%d" % k)), recs, paths, gaps, limit=limit)
+    files = sorted(os.listdir(str(tmp_path / "cut0")))
+    assert files == sorted(os.listdir(str(tmp_path / "cut1")))
+    assert sum(np.load(str(tmp_path / "cut0" / f)).nbytes for f in files) <= limit
+    for n in ("records", "paths", "gaps"):
+        a, rows = (np.load(str(tmp_path / "cut0" / (n + s))) for s in (".npy", "_rows.npy"))
+        assert np.array_equal(a, np.load(str(tmp_path / "cut1" / (n + ".npy"))))
+        assert len(rows) > 0 and np.array_equal(a, z[n][rows.astype(np.int64)])
