@@ -15,9 +15,6 @@
 // aln_seqseq.c:241-420, aln_controller.c:194-436): the sub-problems of a level are independent given their windows.
 #pragma once
 
-#ifndef KA_SUB_EARLY
-#define KA_SUB_EARLY 0                                           // ka_sub_pass: the next step's column record is read right behind this step's wait (1) or behind the dot products (0); round 6, measured: no difference (passes of a 430 x 420 task 464 / 466 us) -- the reads are covered either way
-#endif
 #define KA_SUB_MAXROWS 64                                       // a subtree in ONE wave region: decided when the sub-problem is emitted (ka_child_is_subtree)
 #define KA_SUB_WIDEROWS 128                                     // ... in TWO regions (round 5): decided per recursion level at run time (ka_run_items)
 #if KA_TP
@@ -147,11 +144,22 @@ __device__ __forceinline__ KaState ka_sub_state(const int code, const KaState ro
 // The passes pass0 .. pass0 + (64 >> sshift) - 1 of the current level (pass p = sub-problem p / 2, direction p & 1),
 // 1 << sshift lanes apiece, ONE DP row per lane (the level's passes have at most 1 << sshift rows), in lock-step.
 // The cell is ka_packed's; the profile-profile dot product packs two residues per v_pk_mul_f32 and adds the two
-// products one after the other (as ka_strip<.., Q = 1>).  The column record of the NEXT step is fetched behind the
-// dot-product chain (loads the compiler tracks; KA_UNTRACKED_READS in ka_pass.h has the history).
+// products one after the other (as ka_strip<.., Q = 1>).
 // NB > 0 (round 4): the anchor-consistency bonus of the lane's row (aln_profileprofile.c:108-110 and its seq-seq / seq-profile
 // twins: added behind the substitution terms), the row's entries held in registers as in ka_strip / ka_packed -- until then a job
 // with a consistency table ran its deep recursion levels level by level across the workgroup.
+//
+// Steps go in PAIRS (t, t + 1), software-pipelined.  Lane ls's diagonal state of step t + 1 is its up-neighbour's state of step
+// t, i.e. lane ls - 1's cell of step t - 1: the substitution chain of step t + 1 (kmax3, then one dependent add per residue
+// product, in the reference's order) needs nothing of step t.  One step at a time, every chain ran exposed at dependent-VALU
+// latency (~785 cycles for a ~107-instruction step).  Here a pair runs in three parts:
+//   1. the column terms of both steps, the injected states, step t's neighbours, the products and the first max of both chains
+//      (all independent of this pair's chains);
+//   2. the column records of the NEXT pair (issued here, waited for at the top of the next pair: a whole pair covers them);
+//   3. the two chains interleaved add by add, then the two cell tails (t + 1's up-neighbours are t's cells, one DPP shift).
+// The row-buffer stores of both steps come last, behind the pair's arithmetic (their exec-masked branches do not split it).
+// A wave runs an even number of steps: the last, extra one of an odd count touches no cell any writer stores (its v is beyond
+// every pass's last column), and its record reads are clamped like the others.
 template <int KIND, int NRES, int NB = 0>
 __device__ __forceinline__ void ka_sub_pass(const KaSubCtx& X, const ka_li* qc, const int npass, const int pass0, const int sshift, const int lane, const float* tss,
                                             const int2* ent = nullptr)
@@ -160,6 +168,7 @@ __device__ __forceinline__ void ka_sub_pass(const KaSubCtx& X, const ka_li* qc, 
         constexpr int G0 = RW - 4;                                     // the gap chunk of a record
         constexpr int NV = (NRES + 3) / 4;
         constexpr int NPAIR = NRES / 2;
+        constexpr int NPR = (KIND == KA_PP && NPAIR > 0) ? NPAIR : 1;
         const int p = pass0 + (lane >> sshift);
         const int ls = lane & ((1 << sshift) - 1);
         const bool live = p < npass;
@@ -175,10 +184,14 @@ __device__ __forceinline__ void ka_sub_pass(const KaSubCtx& X, const ka_li* qc, 
         const bool near_t = (dir == KA_FWD) ? (X.b0 + sb == 0) : (X.b0 + eb == X.Lb);
         const bool far_t = (dir == KA_FWD) ? (X.b0 + eb == X.Lb) : (X.b0 + sb == 0);
         const KaState inj = (dir == KA_FWD) ? ka_sub_state((e.c >> 16) & 3, X.rfin) : ka_sub_state((e.c >> 18) & 3, X.rbin);
-        ka_lf* const rowbuf = ((dir == KA_FWD) ? X.F : X.B) + 3 * roff;
-
-#define SREC(v_) ((dir == KA_FWD) ? (sb + (v_)) : (eb + 1 - (v_)))     /* column record, relative to b0 */
-#define SIDX(v_) ((dir == KA_FWD) ? (v_) : (ncols - (v_)))
+        // lane constants of the step: column v's record is rec0 + vs * v (relative to b0), its bonus column jb0 + vs * v, its
+        // row-buffer cell wrow + 3 * vs * v
+        const int vs = (dir == KA_FWD) ? 1 : -1;
+        const int rec0 = (dir == KA_FWD) ? sb : eb + 1;
+        const int jb0 = X.b0 + ((dir == KA_FWD) ? sb : eb);
+        ka_lf* const wrow = ((dir == KA_FWD) ? X.F : X.B) + 3 * (roff + ((dir == KA_FWD) ? 0 : ncols));
+        const bool zr = (nrows == 0);                                 // a pass without rows stores its injected row
+        const int tc0 = near_t ? 0 : -(1 << 20), tcN = far_t ? ncols : -(1 << 20);   // the terminal columns of the pass (none: a column no step has)
 
         const bool writer = live && (ls == max(nrows - 1, 0));        // owner of the pass's last row (or of the init row)
         const int uA = min(ls, max(nrows - 1, 0));
@@ -189,7 +202,7 @@ __device__ __forceinline__ void ka_sub_pass(const KaSubCtx& X, const ka_li* qc, 
         KaBonus<NB> bon;
         if (NB) bon.load(ent, min(max(X.a0 + iA, 0), X.La - 1), dir);
         float oA, eA, tA, orpA;
-        float2v p1p[KIND == KA_PP ? (NPAIR > 0 ? NPAIR : 1) : 1];     // the counts of residues (2i, 2i+1)
+        float2v p1p[NPR];                                             // the counts of residues (2i, 2i+1)
         float p1last = 0.0f;
         int res1A = 0;
         const ka_lf* srowA = nullptr;
@@ -218,11 +231,10 @@ __device__ __forceinline__ void ka_sub_pass(const KaSubCtx& X, const ka_li* qc, 
         float inia = inj.a, iniga = inj.ga, inigb = inj.gb;
         float copen_prev = 0.0f;
         float4v q[2][KIND == KA_PP ? NV + 1 : 1];
-        int resq[2] = {0, 0};
 
-        // profile columns: the record of column counter vcol (clamped), untracked reads + a manual wait (see ka_strip)
+        // profile columns: the record of column counter vcol (clamped), read a pair ahead (see ka_strip for the two forms)
         const unsigned cols_u = (unsigned)(unsigned long long)X.colsL;
-        auto rec_addr = [&](int vcol) -> unsigned { const int vv = min(max(vcol, 0), ncols); return cols_u + (unsigned)(SREC(vv) * (RW * 4)); };
+        auto rec_addr = [&](int vcol) -> unsigned { const int vv = min(max(vcol, 0), ncols); return cols_u + (unsigned)((rec0 + vs * vv) * (RW * 4)); };
         auto pp_read = [&](float4v* dstq, unsigned a, auto& dep) {
                 if (!KA_UNTRACKED_READS) {
                         // (tracked loads: see KA_UNTRACKED_READS in ka_pass.h)
@@ -261,99 +273,109 @@ __device__ __forceinline__ void ka_sub_pass(const KaSubCtx& X, const ka_li* qc, 
         auto res_fetch = [&](int vcol) -> int {
                 // residue of column record rec sits at rec - 1 of the sequence (clamped like ka_packed does)
                 const int vv = min(max(vcol, 0), ncols);
-                return X.colres[min(max(SREC(max(vv, 1)) - 1, 0), X.C - 1) + 1];
+                return X.colres[min(max(rec0 + vs * max(vv, 1) - 1, 0), X.C - 1) + 1];
         };
-        if (KIND == KA_PP) { float nodep = 0.0f; pp_read(q[0], rec_addr(-ls), nodep); }
-        else resq[0] = res_fetch(-ls);
+        auto score = [&](int r) -> float { return (KIND == KA_SS) ? tss[res1A + r] : srowA[r]; };
+        // the injected row at step t: only lane 0 of a pass consumes it (as its up-neighbour, or as the row a pass without rows
+        // stores), and there v == t -- so the column tests are on the wave-uniform step
+        auto inject = [&](const int t, const float copen, const float cext, const float ctext) {
+                const float gx = near_t ? ctext : cext, gy = near_t ? ctext : copen;
+                const float g = kmax(iniga + gx, inia + gy);
+                const bool v0 = (t == 0), vmid = (t < ncols);
+                inia = v0 ? inj.a : -KA_F;
+                iniga = v0 ? inj.ga : (vmid ? g : -KA_F);
+                inigb = v0 ? inj.gb : -KA_F;
+        };
+        // selects only (a branchy cell costs more than the arithmetic it skips); max(x, y) + c == max(x + c, y + c) bit for bit
+        // (rounding is monotonic), so the terminal and the inner form of the gb state share one expression
+        // (the terminal columns as lane constants: v == tc0 or v == tcN, plain compares -- no per-step boolean arithmetic)
+        auto cell = [&](const int v, const float a1, const float ga_in, const float upa, const float upgb, float& na, float& nga, float& ngb) {
+                const bool at0 = (v == 0);
+                const bool edge = at0 || (v == ncols);
+                const bool term = (v == tc0) || (v == tcN);
+                na = at0 ? -KA_F : a1;
+                nga = edge ? -KA_F : ga_in;
+                const float gbx = term ? tA : eA, gby = term ? tA : oA;
+                ngb = kmax(upgb + gbx, upa + gby);
+        };
+
+        int rq0 = 0, rq1 = 0;                                         // seq columns: the residues of the pair's two steps
+        if (KIND == KA_PP) { float nodep = 0.0f; pp_read(q[0], rec_addr(-ls), nodep); pp_read(q[1], rec_addr(1 - ls), nodep); }
+        else { rq0 = res_fetch(-ls); rq1 = res_fetch(1 - ls); }
 
         const int nsteps = ka_wave_max_i(live ? (ncols + max(nrows, 1)) : 0);
 
-        auto step = [&](const int t, auto par_tag) {
-                constexpr int P = decltype(par_tag)::value;
-                const int v = t - ls;
-                const bool vin = live && (v >= 0) && (v <= ncols);
-                if (KIND != KA_PP) resq[1 - P] = res_fetch(v + 1);
-
-                float copen, cext, ctext;
+        for (int t = 0; t < nsteps; t += 2) {
+                const int v0 = t - ls, v1 = v0 + 1;
+                // ---- 1. everything that does not wait for this pair's chains ----
+                float co0, ce0, ct0, co1, ce1, ct1;
+                float s0 = 0.0f, s1 = 0.0f;
+                int nq0 = 0, nq1 = 0;
                 if (KIND == KA_PP) {
-                        pp_wait(q[P]); copen = q[P][NV].x; cext = q[P][NV].y; ctext = q[P][NV].z;
-#if KA_SUB_EARLY
-                        // (the next step's record right behind this step's wait, as ka_wstrip's KA_W_EARLY: a whole step covers the reads)
-                        __builtin_amdgcn_sched_barrier(0);
-                        pp_read(q[1 - P], rec_addr(v + 1), copen);
-                        __builtin_amdgcn_sched_barrier(0);
-#endif
-                }
-                else { copen = X.kc_open; cext = X.kc_ext; ctext = X.kc_text; }
-                {
-                        const float gx = near_t ? ctext : cext, gy = near_t ? ctext : copen;
-                        const float g = kmax(iniga + gx, inia + gy);
-                        const bool v0 = (v == 0), vmid = (v < ncols);
-                        inia = v0 ? inj.a : -KA_F;
-                        iniga = v0 ? inj.ga : (vmid ? g : -KA_F);
-                        inigb = v0 ? inj.gb : -KA_F;
-                }
-                const float sha = wave_shr1(cAa), shga = wave_shr1(cAga), shgb = wave_shr1(cAgb);
-                const float upa = (ls == 0) ? inia : sha, upga = (ls == 0) ? iniga : shga, upgb = (ls == 0) ? inigb : shgb;
-
-                float a1 = kmax3(dga, dgga + copen_prev, dggb + orpA);
-                if (KIND == KA_SS) {
-                        a1 += tss[res1A + resq[P]];
-                } else if (KIND == KA_SP) {
-                        a1 += srowA[resq[P]];
+                        pp_wait(q[0]); co0 = q[0][NV].x; ce0 = q[0][NV].y; ct0 = q[0][NV].z;
+                        pp_wait(q[1]); co1 = q[1][NV].x; ce1 = q[1][NV].y; ct1 = q[1][NV].z;
                 } else {
-                        if (NRES & 1) a1 += p1last * q[P][(NRES - 1) >> 2][(NRES - 1) & 3];
-                        if (NPAIR > 0) {
-                                auto qpair = [&](int i) -> float2v {
-                                        const float4v& w = q[P][(2 * i) >> 2];
-                                        return ((2 * i) & 3) ? __builtin_shufflevector(w, w, 2, 3) : __builtin_shufflevector(w, w, 0, 1);
-                                };
-                                float2v prod = p1p[NPAIR - 1] * qpair(NPAIR - 1);
+                        nq0 = res_fetch(v0 + 2); nq1 = res_fetch(v1 + 2);
+                        s0 = score(rq0); s1 = score(rq1);
+                        co0 = co1 = X.kc_open; ce0 = ce1 = X.kc_ext; ct0 = ct1 = X.kc_text;
+                }
+                inject(t, co0, ce0, ct0);
+                const float ia0 = inia, iga0 = iniga, igb0 = inigb;
+                const float sha0 = wave_shr1(cAa), shga0 = wave_shr1(cAga), shgb0 = wave_shr1(cAgb);
+                const float upa0 = (ls == 0) ? ia0 : sha0, upga0 = (ls == 0) ? iga0 : shga0, upgb0 = (ls == 0) ? igb0 : shgb0;
+                const float gin0 = kmax(cAga + ce0, cAa + co0);
+                inject(t + 1, co1, ce1, ct1);
+                float a0 = kmax3(dga, dgga + copen_prev, dggb + orpA);
+                float a1 = kmax3(upa0, upga0 + co0, upgb0 + orpA);
+                float pl0 = 0.0f, pl1 = 0.0f;
+                float2v pr0[NPR], pr1[NPR];
+                if (KIND == KA_PP) {
+                        auto prods = [&](const float4v* qq, float2v* pr, float& pl) {
+                                if (NRES & 1) pl = p1last * qq[(NRES - 1) >> 2][(NRES - 1) & 3];
 #pragma unroll
-                                for (int i = NPAIR - 1; i >= 1; --i) {
-                                        const float2v nprod = p1p[i - 1] * qpair(i - 1);
-                                        a1 += prod.y;
-                                        a1 += prod.x;
-                                        prod = nprod;
+                                for (int i = 0; i < NPAIR; ++i) {
+                                        const float4v& w = qq[(2 * i) >> 2];
+                                        pr[i] = p1p[i] * (((2 * i) & 3) ? __builtin_shufflevector(w, w, 2, 3) : __builtin_shufflevector(w, w, 0, 1));
                                 }
-                                a1 += prod.y;
-                                a1 += prod.x;
+                        };
+                        prods(q[0], pr0, pl0);
+                        prods(q[1], pr1, pl1);
+                        // ---- 2. the next pair's records ----
+                        __builtin_amdgcn_sched_barrier(0);
+                        pp_read(q[0], rec_addr(v0 + 2), pr0[0]);
+                        pp_read(q[1], rec_addr(v1 + 2), pr1[0]);
+                        __builtin_amdgcn_sched_barrier(0);
+                }
+                // ---- 3. the two chains, add by add in the reference's order each ----
+                if (KIND != KA_PP) { a0 += s0; a1 += s1; }
+                else {
+                        if (NRES & 1) { a0 += pl0; a1 += pl1; }
+#pragma unroll
+                        for (int i = NPAIR - 1; i >= 0; --i) { a0 += pr0[i].y; a1 += pr1[i].y; a0 += pr0[i].x; a1 += pr1[i].x; }
+                }
+                if (NB) { a0 += bon.template at<true>(jb0 + vs * v0); a1 += bon.template at<true>(jb0 + vs * v1); }
+                float na0, nga0, ngb0;
+                cell(v0, a0, gin0, upa0, upgb0, na0, nga0, ngb0);
+                const float sha1 = wave_shr1(na0), shga1 = wave_shr1(nga0), shgb1 = wave_shr1(ngb0);
+                const float upa1 = (ls == 0) ? inia : sha1, upga1 = (ls == 0) ? iniga : shga1, upgb1 = (ls == 0) ? inigb : shgb1;
+                const float gin1 = kmax(nga0 + ce1, na0 + co1);
+                cell(v1, a1, gin1, upa1, upgb1, cAa, cAga, cAgb);
+                dga = upa1; dgga = upga1; dggb = upgb1;
+                copen_prev = co1;
+                if (KIND != KA_PP) { rq0 = nq0; rq1 = nq1; }
+                // ---- the row buffer ----
+                if (writer) {
+                        if (v0 >= 0 && v0 <= ncols) {
+                                ka_lf* w = wrow + 3 * vs * v0;
+                                w[0] = zr ? ia0 : na0; w[1] = zr ? iga0 : nga0; w[2] = zr ? igb0 : ngb0;
                         }
-#if !KA_SUB_EARLY
-                        __builtin_amdgcn_sched_barrier(0);
-                        pp_read(q[1 - P], rec_addr(v + 1), a1);
-                        __builtin_amdgcn_sched_barrier(0);
-#endif
+                        if (v1 >= 0 && v1 <= ncols) {
+                                ka_lf* w = wrow + 3 * vs * v1;
+                                w[0] = zr ? inia : cAa; w[1] = zr ? iniga : cAga; w[2] = zr ? inigb : cAgb;
+                        }
                 }
-                if (NB) { const int jb = (dir == KA_FWD) ? (X.b0 + sb + v) : (X.b0 + eb - v); a1 += bon.template at<true>(jb); }
-                const bool at0 = (v == 0), atN = (v == ncols);
-                const bool edge = at0 | atN;
-                const bool term = (at0 & near_t) | (atN & far_t);           // (bitwise: as short-circuit logic this became exec-masked branches in every edge step)
-                // selects only (a branchy cell costs more than the arithmetic it skips); max(x, y) + c == max(x + c, y + c) bit
-                // for bit (rounding is monotonic), so the terminal and the inner form of the gb state share one expression
-                const float nAa = at0 ? -KA_F : a1;
-                const float ga_in = kmax(cAga + cext, cAa + copen);
-                const float nAga = edge ? -KA_F : ga_in;
-                const float gbx = term ? tA : eA, gby = term ? tA : oA;
-                const float nAgb = kmax(upgb + gbx, upa + gby);
-                cAa = nAa; cAga = nAga; cAgb = nAgb;
-                dga = upa; dgga = upga; dggb = upgb;
-                copen_prev = copen;
-                const float wa = (nrows == 0) ? inia : cAa, wga = (nrows == 0) ? iniga : cAga, wgb = (nrows == 0) ? inigb : cAgb;
-                if (vin && writer) {
-                        ka_lf* w = rowbuf + 3 * SIDX(v);
-                        w[0] = wa; w[1] = wga; w[2] = wgb;
-                }
-        };
-        int t = 0;
-        for (; t + 1 < nsteps; t += 2) {
-                step(t, std::integral_constant<int, 0>());
-                step(t + 1, std::integral_constant<int, 1>());
         }
-        if (t < nsteps) step(t, std::integral_constant<int, 0>());
-        if (KIND == KA_PP) pp_wait(q[nsteps & 1]);                    // nothing of this pass is in flight when the LDS is reused
-#undef SREC
-#undef SIDX
+        if (KIND == KA_PP) { pp_wait(q[0]); pp_wait(q[1]); }          // nothing of this pass is in flight when the LDS is reused
 }
 
 // The meetups of sub-problems k0 .. k0 + 64/GL - 1 of the current level (GL lanes apiece) and their children
