@@ -442,6 +442,42 @@ int ka_multi_download(ka_multi* m, int numseq, const int* lens, int n_tasks, ka_
 ka_ctx* ka_multi_ctx(ka_multi* m, int rank);
 int ka_multi_adopt(ka_multi* m, const ka_task_rec* recs, const int* gaps);
 
+/* ---- the ensemble consensus stage (ka_ens.hip, ka_ens.cpp) --------------------------------------------------------------
+ * kalign_ensemble's tail (lib/src/ensemble.c:341-): scores of alignments against the members' residue pairs, the consensus
+ * alignment, per-residue and per-column confidence -- without the reference's POAR table.  The support of a residue pair
+ * (residue ri of sequence i, residue rj of sequence j) is the number of members that put them in one column; everything below is
+ * an integer count of it, computed on the device.  Sequences are in the order of the members' rows (input / rank order).
+ * A residue is an ASCII letter (isalpha in the C locale), every other byte a gap.
+ *   ka_ens_create       numseq sequences of lens[s] residues, n_runs members (1..32: one bit per member in the reference's table).
+ *                       The handle runs on ctx's device and stream: destroy it before ctx.
+ *                       Fails for a sequence of more than 4096 residues: the reference packs a pair as ri << 20 | rj in 32 bits,
+ *                       which aliases from residue index 4096 on, so its result there is not a defined contract.
+ *   ka_ens_add_member   member k's rows: numseq rows of alnlen bytes, row_stride apart.  Fails when alnlen does not fit the stride
+ *                       or a row's letter count differs from lens[s].  Every member must be added before the calls below.
+ *   ka_ens_score_rows   score_alignment_poar (consensus_msa.c:694-740) of any alignment of the sequences: sum_out = the exact sum
+ *                       over its residue pairs of (support - 1) (-1 for a pair no member has), score_out = sum / max(n_runs - 1, 1).
+ *                       The reference adds the terms one by one in double: equal within rounding, equal for equal pair sets.
+ *   ka_ens_consensus    build_consensus (consensus_msa.c:372-562) at min_support >= 1 (kalign_ensemble's automatic value is
+ *                       max(2, (n_runs + 2) / 3)); letters: the sequences' letters concatenated (sum of lens bytes), placed in
+ *                       the consensus columns.  KA_ERR_ROWS_STRIDE with alnlen_out filled when rows_out is NULL or row_stride <
+ *                       alnlen; asking again with the same arguments returns the kept result.
+ *   ka_ens_confidence   compute_residue_confidence (consensus_msa.c:564-692) of an alignment: res_conf_out[numseq][alnlen]
+ *                       (0 at gaps), col_conf_out[alnlen]; bit-identical to the reference.
+ *   ka_ens_stats        measurements of the last calls: stats_out[10] = device ms of the position maps, of the last score, of the
+ *                       consensus' count passes and write passes, host ms of the greedy and of the column order + fill, device ms of
+ *                       the last confidence, host ms spent waiting for candidates, number of candidate chunks, breadth-first
+ *                       searches that hit the 4096-set queue limit; level_counts_out[33] / level_ms_out[33]: candidates and device
+ *                       ms per support level of the last consensus.
+ */
+typedef struct ka_ens ka_ens;
+int  ka_ens_create(ka_ctx* ctx, int numseq, const int* lens, int n_runs, ka_ens** out);
+void ka_ens_destroy(ka_ens* e);
+int  ka_ens_add_member(ka_ens* e, int k, const uint8_t* rows, long long row_stride, int alnlen);
+int  ka_ens_score_rows(ka_ens* e, const uint8_t* rows, long long row_stride, int alnlen, long long* sum_out, double* score_out);
+int  ka_ens_consensus(ka_ens* e, int min_support, const uint8_t* letters, uint8_t* rows_out, long long row_stride, int* alnlen_out);
+int  ka_ens_confidence(ka_ens* e, const uint8_t* rows, long long row_stride, int alnlen, float* res_conf_out, float* col_conf_out);
+int  ka_ens_stats(ka_ens* e, double* stats_out, long long* level_counts_out, double* level_ms_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@ pairwise_align_map() (lib/src/anchor_consistency.c:246-267).
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -17,6 +18,7 @@ FLAG_DEVICE_GAPS = 4
 FLAG_KEEP_CONSISTENCY = 8
 FLAG_EXACT_CONFIDENCE = 16
 FLAG_LEAF_PROFILES = 32
+ERR_ROWS_STRIDE = 3             # KA_ERR_ROWS_STRIDE: the row buffer is too narrow, the width is reported
 
 
 class KalignAmdError(RuntimeError):
@@ -54,7 +56,8 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_dist_loopback_new", "ka_dist_loopback_free", "ka_dist_create_loopback",
            "ka_guide_last_bisect_ms", "ka_device_count", "ka_multi_create", "ka_multi_destroy", "ka_multi_world", "ka_multi_runs", "ka_multi_last_error",
            "ka_multi_consistency", "ka_multi_tree_run", "ka_multi_paths_size", "ka_multi_download", "ka_multi_ctx", "ka_multi_adopt",
-           "ka_tree_adopt_alignment"]
+           "ka_tree_adopt_alignment", "ka_ens_create", "ka_ens_destroy", "ka_ens_add_member", "ka_ens_score_rows", "ka_ens_consensus",
+           "ka_ens_confidence", "ka_ens_stats"]
 
 
 def lib_path():
@@ -176,6 +179,14 @@ def load_library():
     L.ka_tree_get_consistency.argtypes = [vp, vp, vp]
     L.ka_pairwise_batch.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp,
                                     C.c_float, C.c_float, C.c_float, vp, vp, vp]
+    L.ka_ens_create.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(vp)]
+    L.ka_ens_destroy.argtypes = [vp]
+    L.ka_ens_destroy.restype = None
+    L.ka_ens_add_member.argtypes = [vp, C.c_int, vp, C.c_longlong, C.c_int]
+    L.ka_ens_score_rows.argtypes = [vp, vp, C.c_longlong, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]
+    L.ka_ens_consensus.argtypes = [vp, C.c_int, vp, vp, C.c_longlong, C.POINTER(C.c_int)]
+    L.ka_ens_confidence.argtypes = [vp, vp, C.c_longlong, C.c_int, vp, vp]
+    L.ka_ens_stats.argtypes = [vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -219,6 +230,9 @@ class Context:
         return self
 
     def close(self):
+        # ensembles borrow this context's stream: they go first
+        for e in list(getattr(self, "_ensembles", ())):
+            e.close()
         if getattr(self, "h", None):
             if not getattr(self, "_borrowed", False):
                 self.L.ka_ctx_destroy(self.h)
@@ -609,6 +623,101 @@ def _run_encoded(self, tree_codes, codes, letters, subm, scal, n_anchors=0, weig
 
 
 Context.run_encoded = _run_encoded
+
+
+def _rows_array(rows, n):
+    """equal-length rows (bytes / str) -> (uint8[n, width], width)"""
+    rows = [x.encode() if isinstance(x, str) else bytes(x) for x in rows]
+    if len(rows) != n:
+        raise KalignAmdError("%d rows for %d sequences" % (len(rows), n))
+    width = len(rows[0]) if rows else 0
+    if any(len(r) != width for r in rows):
+        raise KalignAmdError("rows of one alignment have one length")
+    return np.frombuffer(b"".join(rows), np.uint8).reshape(n, width), width
+
+
+class Ensemble:
+    """The consensus stage of an ensemble (ka_ens): the members' rows on the device, then scores, the consensus alignment
+    and confidences of any alignment of the same sequences.  Rows are in the members' sequence order."""
+
+    def __init__(self, ctx, lens, n_runs):
+        self.ctx, self.L = ctx, ctx.L
+        self.lens = np.ascontiguousarray(lens, np.int32)
+        self.n, self.n_runs = len(self.lens), int(n_runs)
+        h = C.c_void_p()
+        self.h = None
+        if not ctx.h:
+            raise KalignAmdError("the context is closed")
+        ctx._chk(self.L.ka_ens_create(ctx.h, self.n, _ptr(self.lens), self.n_runs, C.byref(h)))
+        self.h = h
+        if not hasattr(ctx, "_ensembles"):
+            ctx._ensembles = weakref.WeakSet()
+        ctx._ensembles.add(self)
+
+    def close(self):
+        """frees the device state; a closed context has closed its ensembles already (Context.close)"""
+        if self.h:
+            self.L.ka_ens_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_member(self, k, rows):
+        a, w = _rows_array(rows, self.n)
+        self.ctx._chk(self.L.ka_ens_add_member(self.h, int(k), _ptr(a), w, w))
+
+    def score(self, rows):
+        """(sum of (support - 1) over the alignment's residue pairs, score_alignment_poar's value)"""
+        a, w = _rows_array(rows, self.n)
+        s, v = C.c_longlong(), C.c_double()
+        self.ctx._chk(self.L.ka_ens_score_rows(self.h, _ptr(a), w, w, C.byref(s), C.byref(v)))
+        return s.value, v.value
+
+    def consensus(self, letters, min_support):
+        """build_consensus at min_support: the consensus rows (bytes), letters = the sequences (str / bytes) placed in them"""
+        flat = np.frombuffer(b"".join(x.encode() if isinstance(x, str) else bytes(x) for x in letters), np.uint8)
+        if len(flat) != int(self.lens.sum()):
+            raise KalignAmdError("letters do not match the sequence lengths")
+        w = C.c_int()
+        rc = self.L.ka_ens_consensus(self.h, int(min_support), _ptr(flat), None, 0, C.byref(w))
+        if rc != ERR_ROWS_STRIDE:                                # asked for the width first
+            self.ctx._chk(rc)
+        out = np.zeros((self.n, max(w.value, 1)), np.uint8)
+        self.ctx._chk(self.L.ka_ens_consensus(self.h, int(min_support), _ptr(flat), _ptr(out), out.shape[1], C.byref(w)))
+        return [out[s, :w.value].tobytes() for s in range(self.n)]
+
+    def confidence(self, rows):
+        """compute_residue_confidence: (float32[n, width] per residue, 0 at gaps; float32[width] per column)"""
+        a, w = _rows_array(rows, self.n)
+        res = np.zeros((self.n, w), np.float32)
+        col = np.zeros(w, np.float32)
+        self.ctx._chk(self.L.ka_ens_confidence(self.h, _ptr(a), w, w, _ptr(res), _ptr(col)))
+        return res, col
+
+    def stats(self):
+        """measurements of the last calls (ka_ens_stats) as a dict"""
+        st = np.zeros(10, np.float64)
+        cnt = np.zeros(33, np.int64)
+        ms = np.zeros(33, np.float64)
+        self.ctx._chk(self.L.ka_ens_stats(self.h, _ptr(st), _ptr(cnt), _ptr(ms)))
+        keys = ["maps_ms", "score_ms", "count_ms", "write_ms", "greedy_host_ms", "columns_host_ms", "confidence_ms",
+                "wait_host_ms", "chunks", "bfs_truncations"]
+        out = dict(zip(keys, st.tolist()))
+        out["level_candidates"] = {L: int(cnt[L]) for L in range(33) if cnt[L]}
+        out["level_ms"] = {L: float(ms[L]) for L in range(33) if cnt[L] or ms[L]}
+        return out
+
+
+def _ens_create(self, lens, n_runs):
+    """ka_ens_create: an Ensemble for sequences of these lengths and n_runs members"""
+    return Ensemble(self, lens, n_runs)
+
+
+Context.ensemble = _ens_create
 
 
 def guide_tree_from(lens, dist, n_threads=1, dm_scale=None):

@@ -1,0 +1,545 @@
+// ka_ens.cpp -- host side of the ensemble consensus stage (kalign_ensemble's tail, lib/src/ensemble.c:341-): the ka_ens
+// handle of the C ABI, and the one part of the stage that stays sequential -- build_consensus' greedy union of the
+// candidate pairs (consensus_msa.c:372-562) and the column order after it.
+//
+// The device (ka_ens.hip) turns the members' rows into position maps and walks (i, j, ri) for scores, confidences and
+// candidates.  The candidates come one support level at a time, highest first, in the reference's order inside a level
+// (i, j, ri, rj ascending; the stable counting sort of consensus_msa.c:438-459 over the table order).  A level is cut
+// into chunks of whole rows i; while the greedy replays chunk c from pinned memory, the device writes chunk c + 1.
+//
+// The greedy is order-dependent in two ways and is replayed candidate by candidate:
+//   * a merge is refused when the two sets share a sequence, or when either set reaches the other in the column DAG
+//     (an edge from a residue's set to the set of the next residue of the same sequence);
+//   * that reachability search is a breadth-first search with a queue of 4096 sets that silently stops queueing when
+//     full (dag_reachable, consensus_msa.c:121-160) -- its answer depends on the order of the sets' member lists,
+//     i.e. on the merge history.  The lists are concatenated as the reference does (the absorbed set's list after the
+//     surviving root's), the root chosen by rank as it does.
+// The columns are numbered by the first residue (flat order) of each set, ordered by a DFS topological sort that skips
+// back edges (topo_sort, consensus_msa.c:255-370) and filled with the caller's letters.
+#include "ka_ctx.h"
+#include "ka_ens.h"
+
+int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
+
+namespace {
+
+struct Uf {
+        // union by rank with path halving; per-set member lists; sequence sets as bitmasks, kept for sets of two or
+        // more residues only (a singleton's set is the bit of its own sequence)
+        std::vector<int> parent, rnk, elemSeq, head, next, tail, maskOf;
+        std::vector<uint64_t> pool;
+        std::vector<int> freeSlots;
+        int mw = 1;
+        std::vector<long long> visited;
+        long long visit = 0;
+        long long truncations = 0;
+        const std::vector<int>* offs = nullptr;
+        const std::vector<int>* lens = nullptr;
+
+        void init(const std::vector<int>& o, const std::vector<int>& l, int T)
+        {
+                offs = &o; lens = &l;
+                const int N = (int)o.size();
+                mw = (N + 63) / 64;
+                parent.resize(T); rnk.assign(T, 0); elemSeq.resize(T); head.resize(T); next.assign(T, -1); tail.resize(T);
+                maskOf.assign(T, -1); visited.assign(T, 0);
+                pool.clear(); freeSlots.clear(); visit = 0; truncations = 0;
+                for (int e = 0; e < T; e++) { parent[e] = e; head[e] = e; tail[e] = e; }
+                for (int s = 0; s < N; s++)
+                        for (int p = 0; p < l[s]; p++) elemSeq[o[s] + p] = s;
+        }
+        int find(int x)
+        {
+                while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
+                return x;
+        }
+        bool hasSeq(int root, int s) const
+        {
+                const int m = maskOf[root];
+                if (m < 0) return elemSeq[root] == s;
+                return pool[(size_t)m * mw + s / 64] >> (s % 64) & 1u;
+        }
+        bool share(int a, int b) const
+        {
+                const int ma = maskOf[a], mb = maskOf[b];
+                if (ma < 0) return hasSeq(b, elemSeq[a]);
+                if (mb < 0) return hasSeq(a, elemSeq[b]);
+                for (int w = 0; w < mw; w++)
+                        if (pool[(size_t)ma * mw + w] & pool[(size_t)mb * mw + w]) return true;
+                return false;
+        }
+        int slot()
+        {
+                if (!freeSlots.empty()) { const int s = freeSlots.back(); freeSlots.pop_back(); std::fill_n(&pool[(size_t)s * mw], mw, 0); return s; }
+                pool.resize(pool.size() + mw, 0);
+                return (int)(pool.size() / mw) - 1;
+        }
+        // is `target` reachable from `start` through the column DAG?  Queue of 4096 sets, full = not queued (still marked)
+        bool reaches(int start, int target)
+        {
+                int queue[4096];
+                int qh = 0, qt = 0;
+                if (start == target) return true;
+                visit++;
+                queue[qt++] = start;
+                visited[start] = visit;
+                while (qh < qt) {
+                        const int cur = queue[qh++];
+                        for (int e = head[cur]; e >= 0; e = next[e]) {
+                                const int s = elemSeq[e];
+                                if (e - (*offs)[s] + 1 >= (*lens)[s]) continue;
+                                const int r = find(e + 1);
+                                if (r == target) return true;
+                                if (r != cur && visited[r] != visit) {
+                                        visited[r] = visit;
+                                        if (qt < 4096) queue[qt++] = r;
+                                        else truncations++;
+                                }
+                        }
+                }
+                return false;
+        }
+        void join(int a, int b)
+        {
+                const int ra = find(a), rb = find(b);
+                if (ra == rb) return;
+                if (share(ra, rb)) return;
+                if (reaches(ra, rb)) return;
+                if (reaches(rb, ra)) return;
+                int keep, gone;
+                if (rnk[ra] < rnk[rb]) { keep = rb; gone = ra; }
+                else { keep = ra; gone = rb; if (rnk[ra] == rnk[rb]) rnk[ra]++; }
+                parent[gone] = keep;
+                if (maskOf[keep] < 0) {
+                        const int s = slot();
+                        maskOf[keep] = s;
+                        pool[(size_t)s * mw + elemSeq[keep] / 64] |= 1ull << (elemSeq[keep] % 64);
+                }
+                uint64_t* km = &pool[(size_t)maskOf[keep] * mw];
+                if (maskOf[gone] < 0) km[elemSeq[gone] / 64] |= 1ull << (elemSeq[gone] % 64);
+                else {
+                        const uint64_t* gm = &pool[(size_t)maskOf[gone] * mw];
+                        for (int w = 0; w < mw; w++) km[w] |= gm[w];
+                        freeSlots.push_back(maskOf[gone]);
+                        maskOf[gone] = -1;
+                }
+                if (head[gone] >= 0) {
+                        if (head[keep] < 0) { head[keep] = head[gone]; tail[keep] = tail[gone]; }
+                        else { next[tail[keep]] = head[gone]; tail[keep] = tail[gone]; }
+                }
+                head[gone] = -1;
+        }
+};
+
+// DFS topological sort of the columns, back edges skipped; returns order[position] = column
+std::vector<int> topo_order(const std::vector<int>& colId, const std::vector<int>& offs, const std::vector<int>& lens, int nCols)
+{
+        std::vector<std::vector<int>> adj(nCols);
+        for (size_t s = 0; s < offs.size(); s++)
+                for (int p = 0; p + 1 < lens[s]; p++) {
+                        const int ca = colId[offs[s] + p], cb = colId[offs[s] + p + 1];
+                        if (ca == cb) continue;
+                        std::vector<int>& l = adj[ca];
+                        if (std::find(l.begin(), l.end(), cb) == l.end()) l.push_back(cb);
+                }
+        std::vector<int> out(nCols), state(nCols, 0), stack;
+        stack.reserve(2 * (size_t)nCols);
+        int at = nCols - 1;
+        for (int start = 0; start < nCols; start++) {
+                if (state[start]) continue;
+                stack.push_back(start); stack.push_back(0);
+                state[start] = 1;
+                while (!stack.empty()) {
+                        const int edge = stack.back(); stack.pop_back();
+                        const int node = stack.back(); stack.pop_back();
+                        bool pushed = false;
+                        for (int e = edge; e < (int)adj[node].size(); e++) {
+                                const int nx = adj[node][e];
+                                if (state[nx] == 0) {
+                                        stack.push_back(node); stack.push_back(e + 1);
+                                        stack.push_back(nx); stack.push_back(0);
+                                        state[nx] = 1;
+                                        pushed = true;
+                                        break;
+                                }
+                        }
+                        if (!pushed) { state[node] = 2; out[at--] = node; }
+                }
+        }
+        return out;
+}
+
+inline bool is_residue(uint8_t b) { return (unsigned)((b | 32u) - 'a') < 26u; }
+
+double ms_since(std::chrono::steady_clock::time_point t0)
+{
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+} // namespace
+
+struct ka_ens {
+        int device = 0;
+        hipStream_t stream = nullptr;
+        int N = 0, R = 0, T = 0, maxlen = 0;
+        std::vector<int> lens, offs, W;
+        std::vector<DevBuf<uint8_t>> rows;            // member k's rows, N x W[k]
+        DevBuf<int> dOffs, dLens, dCol, dColX, dCnt, dSup, dNp;
+        DevBuf<int16_t> dRes, dResX;
+        DevBuf<uint8_t> dRowsX;
+        DevBuf<long long> dPairOff, dRowTot, dRowBase[2];
+        DevBuf<unsigned long long> dScore;
+        DevBuf<int2> dOut[2];
+        DevBuf<float> dConf, dColConf;
+        int2* pinned[2] = { nullptr, nullptr };
+        long long pinnedCap = 0, chunkCap = 0;
+        hipEvent_t ready[2] = { nullptr, nullptr }, wBeg[2] = { nullptr, nullptr }, wEnd[2] = { nullptr, nullptr }, ev0 = nullptr, ev1 = nullptr;
+        bool mapsFresh = false;
+        long long generation = 0;
+        // the last consensus (a caller with a too narrow buffer asks again)
+        long long cacheGen = -1;
+        int cacheMin = -1, cacheW = 0;
+        std::vector<uint8_t> cacheRows;
+        std::vector<uint8_t> cacheLetters;
+        // measurements of the last call of each kind
+        double st[KA_ENS_STATS] = {};
+        long long levelCount[KA_ENS_MAX_RUNS + 1] = {};
+        double levelMs[KA_ENS_MAX_RUNS + 1] = {};
+
+        ~ka_ens()
+        {
+                for (int b = 0; b < 2; b++) {
+                        if (pinned[b]) (void)hipHostFree(pinned[b]);
+                        if (ready[b]) (void)hipEventDestroy(ready[b]);
+                        if (wBeg[b]) (void)hipEventDestroy(wBeg[b]);
+                        if (wEnd[b]) (void)hipEventDestroy(wEnd[b]);
+                        dOut[b].release(); dRowBase[b].release();
+                }
+                if (ev0) (void)hipEventDestroy(ev0);
+                if (ev1) (void)hipEventDestroy(ev1);
+                for (auto& r : rows) r.release();
+                dOffs.release(); dLens.release(); dCol.release(); dColX.release(); dCnt.release(); dSup.release(); dNp.release();
+                dRes.release(); dResX.release(); dRowsX.release(); dPairOff.release(); dRowTot.release(); dScore.release();
+                dConf.release(); dColConf.release();
+        }
+
+        float evMs() { float m = 0.0f; (void)hipEventElapsedTime(&m, ev0, ev1); return m; }
+
+        // rows of an alignment: every row's letter count must be its sequence's length
+        int check_rows(const char* who, const uint8_t* r, long long stride, int alnlen)
+        {
+                if (!r) return fail(std::string(who) + ": no rows");
+                if (alnlen <= 0 || stride < alnlen)
+                        return fail(std::string(who) + ": alignment width " + std::to_string(alnlen) + " does not fit row stride " + std::to_string(stride));
+                for (int s = 0; s < N; s++) {
+                        const uint8_t* row = r + (long long)s * stride;
+                        int n = 0;
+                        for (int c = 0; c < alnlen; c++) n += is_residue(row[c]);
+                        if (n != lens[s])
+                                return fail(std::string(who) + ": row " + std::to_string(s) + " holds " + std::to_string(n) + " letters, sequence has " + std::to_string(lens[s]));
+                }
+                return KA_OK;
+        }
+
+        int upload_rows(DevBuf<uint8_t>& d, const uint8_t* r, long long stride, int alnlen)
+        {
+                if (d.alloc((size_t)N * alnlen)) return fail("ka_ens: out of device memory (rows)");
+                HIPCHK(hipMemcpy2DAsync(d.p, alnlen, r, stride, alnlen, N, hipMemcpyHostToDevice, stream));
+                return KA_OK;
+        }
+
+        int ensure_maps()
+        {
+                if (mapsFresh) return KA_OK;
+                for (int k = 0; k < R; k++)
+                        if (W[k] <= 0) return fail("ka_ens: member " + std::to_string(k) + " not added (all n_runs members are needed)");
+                long long resTot = 0;
+                for (int k = 0; k < R; k++) resTot += (long long)N * W[k];
+                if (dCol.alloc((size_t)R * T) || dRes.alloc((size_t)resTot)) return fail("ka_ens: out of device memory (maps)");
+                HIPCHK(hipEventRecord(ev0, stream));
+                long long o = 0;
+                for (int k = 0; k < R; k++) {
+                        ka_ens_launch_maps(rows[k].p, W[k], W[k], N, dOffs.p, dLens.p, dCol.p + (long long)k * T, dRes.p + o, stream);
+                        o += (long long)N * W[k];
+                }
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipEventRecord(ev1, stream));
+                HIPCHK(hipEventSynchronize(ev1));
+                st[0] = evMs();
+                mapsFresh = true;
+                return KA_OK;
+        }
+
+        KaEnsArgs args()
+        {
+                KaEnsArgs a{};
+                a.offs = dOffs.p; a.lens = dLens.p; a.N = N; a.R = R; a.T = T; a.maxlen = maxlen;
+                a.col = dCol.p; a.res = dRes.p;
+                long long o = 0;
+                for (int k = 0; k < R; k++) { a.resOff[k] = o; a.W[k] = W[k]; o += (long long)N * W[k]; }
+                a.i0 = 0; a.i1 = N;
+                // the member columns of sequence i in LDS when they fit next to the three per-residue arrays (64 KiB)
+                a.colInLds = (long long)(3 + R) * maxlen * 4 <= 65536;
+                return a;
+        }
+
+        // an alignment X's maps in dColX / dResX
+        int maps_x(const uint8_t* r, long long stride, int alnlen, KaEnsArgs& a)
+        {
+                if (upload_rows(dRowsX, r, stride, alnlen)) return KA_FAIL;
+                if (dColX.alloc((size_t)std::max(T, 1)) || dResX.alloc((size_t)N * alnlen)) return fail("ka_ens: out of device memory");
+                ka_ens_launch_maps(dRowsX.p, alnlen, alnlen, N, dOffs.p, dLens.p, dColX.p, dResX.p, stream);
+                a.colX = dColX.p; a.resX = dResX.p; a.Wx = alnlen;
+                return KA_OK;
+        }
+
+        int consensus(int minSup, const uint8_t* letters);
+};
+
+int ka_ens::consensus(int minSup, const uint8_t* letters)
+{
+        using clk = std::chrono::steady_clock;
+        st[2] = st[3] = st[4] = st[5] = st[7] = st[8] = st[9] = 0.0;
+        std::fill_n(levelCount, KA_ENS_MAX_RUNS + 1, 0LL);
+        std::fill_n(levelMs, KA_ENS_MAX_RUNS + 1, 0.0);
+        if (ensure_maps()) return KA_FAIL;
+        KaEnsArgs a = args();
+        Uf uf;
+        uf.init(offs, lens, T);
+        // rows i per count pass: the pair counts and offsets of a block are rows x N entries
+        const int rb = std::max(1, std::min(N, (int)((1ll << 24) / std::max(N, 1))));
+        if (dCnt.alloc((size_t)rb * N) || dPairOff.alloc((size_t)rb * N) || dRowTot.alloc((size_t)rb)) return fail("ka_ens: out of device memory (counts)");
+        std::vector<long long> rowTot(rb);
+        std::vector<long long> rowBase[2];
+        for (int L = R; L >= std::max(minSup, 1); L--) {
+                a.level = L;
+                for (int b0 = 0; b0 < N; b0 += rb) {
+                        const int b1 = std::min(N, b0 + rb);
+                        a.i0 = b0; a.i1 = b1; a.cnt = dCnt.p;
+                        HIPCHK(hipEventRecord(ev0, stream));
+                        HIPCHK(hipMemsetAsync(dCnt.p, 0, sizeof(int) * (size_t)(b1 - b0) * N, stream));
+                        ka_ens_launch_walk(KA_ENS_COUNT, a, stream);
+                        ka_ens_launch_row_scan(dCnt.p, N, dPairOff.p, dRowTot.p, b1 - b0, stream);
+                        HIPCHK(hipGetLastError());
+                        HIPCHK(hipEventRecord(ev1, stream));
+                        HIPCHK(hipMemcpyAsync(rowTot.data(), dRowTot.p, sizeof(long long) * (b1 - b0), hipMemcpyDeviceToHost, stream));
+                        HIPCHK(hipStreamSynchronize(stream));
+                        const double cms = evMs();
+                        st[2] += cms; levelMs[L] += cms;
+                        // chunks of whole rows, each at most chunkCap candidates (a longer row is a chunk of its own)
+                        std::vector<int> cut{ b0 };
+                        std::vector<long long> tot;
+                        long long run = 0, biggest = 0;
+                        for (int i = b0; i < b1; i++) {
+                                const long long t = rowTot[i - b0];
+                                levelCount[L] += t;
+                                if (run > 0 && run + t > chunkCap) { cut.push_back(i); tot.push_back(run); biggest = std::max(biggest, run); run = 0; }
+                                run += t;
+                        }
+                        cut.push_back(b1); tot.push_back(run); biggest = std::max(biggest, run);
+                        if (biggest > pinnedCap) {
+                                HIPCHK(hipStreamSynchronize(stream));
+                                for (int q = 0; q < 2; q++) {
+                                        if (pinned[q]) (void)hipHostFree(pinned[q]);
+                                        pinned[q] = nullptr;
+                                        HIPCHK(hipHostMalloc((void**)&pinned[q], sizeof(int2) * (size_t)biggest));
+                                        if (dOut[q].alloc((size_t)biggest)) return fail("ka_ens: out of device memory (candidates)");
+                                }
+                                pinnedCap = biggest;
+                        }
+                        const int nChunks = (int)tot.size();
+                        auto enqueue = [&](int c) -> int {
+                                const int q = c & 1;
+                                if (tot[c] == 0) return KA_OK;
+                                rowBase[q].assign(cut[c + 1] - cut[c], 0);
+                                // rowBase[i - i0] + pairOff[(i - i0) * N + j]: the write pass indexes both by the launch's i0
+                                long long o = 0;
+                                for (int i = cut[c]; i < cut[c + 1]; i++) { rowBase[q][i - cut[c]] = o; o += rowTot[i - b0]; }
+                                if (dRowBase[q].alloc(rowBase[q].size())) return fail("ka_ens: out of device memory");
+                                HIPCHK(hipMemcpyAsync(dRowBase[q].p, rowBase[q].data(), sizeof(long long) * rowBase[q].size(), hipMemcpyHostToDevice, stream));
+                                KaEnsArgs w = a;
+                                w.i0 = cut[c]; w.i1 = cut[c + 1];
+                                w.pairOff = dPairOff.p + (long long)(cut[c] - b0) * N;
+                                w.rowBase = dRowBase[q].p; w.out = dOut[q].p;
+                                HIPCHK(hipEventRecord(wBeg[q], stream));
+                                ka_ens_launch_walk(KA_ENS_WRITE, w, stream);
+                                HIPCHK(hipGetLastError());
+                                HIPCHK(hipEventRecord(wEnd[q], stream));
+                                HIPCHK(hipMemcpyAsync(pinned[q], dOut[q].p, sizeof(int2) * (size_t)tot[c], hipMemcpyDeviceToHost, stream));
+                                HIPCHK(hipEventRecord(ready[q], stream));
+                                return KA_OK;
+                        };
+                        if (enqueue(0)) return KA_FAIL;
+                        for (int c = 0; c < nChunks; c++) {
+                                if (c + 1 < nChunks && enqueue(c + 1)) return KA_FAIL;
+                                if (tot[c] == 0) continue;
+                                const auto t0 = clk::now();
+                                HIPCHK(hipEventSynchronize(ready[c & 1]));
+                                st[7] += ms_since(t0);
+                                float wms = 0.0f;
+                                (void)hipEventElapsedTime(&wms, wBeg[c & 1], wEnd[c & 1]);
+                                st[3] += wms; levelMs[L] += wms;
+                                const auto t1 = clk::now();
+                                const int2* p = pinned[c & 1];
+                                for (long long x = 0; x < tot[c]; x++) uf.join(p[x].x, p[x].y);
+                                st[4] += ms_since(t1);
+                                st[8] += 1;
+                        }
+                }
+        }
+        st[9] = (double)uf.truncations;
+        // columns numbered by first residue, ordered, filled
+        const auto tt = clk::now();
+        std::vector<int> rootCol(T, -1), colId(T);
+        int nCols = 0;
+        for (int e = 0; e < T; e++) {
+                const int r = uf.find(e);
+                if (rootCol[r] < 0) rootCol[r] = nCols++;
+                colId[e] = rootCol[r];
+        }
+        const std::vector<int> order = topo_order(colId, offs, lens, nCols);
+        std::vector<int> pos(nCols);
+        for (int p = 0; p < nCols; p++) pos[order[p]] = p;
+        cacheRows.assign((size_t)N * nCols, '-');
+        for (int s = 0; s < N; s++)
+                for (int p = 0; p < lens[s]; p++) cacheRows[(size_t)s * nCols + pos[colId[offs[s] + p]]] = letters[offs[s] + p];
+        st[5] = ms_since(tt);
+        cacheW = nCols; cacheMin = minSup; cacheGen = generation;
+        cacheLetters.assign(letters, letters + T);
+        return KA_OK;
+}
+
+extern "C" int ka_ens_create(ka_ctx* ctx, int numseq, const int* lens, int n_runs, ka_ens** out)
+{
+        if (!ctx || !out || numseq < 1 || !lens) return fail("ka_ens_create: bad arguments");
+        if (n_runs < 1 || n_runs > KA_ENS_MAX_RUNS)
+                return fail("ka_ens_create: n_runs " + std::to_string(n_runs) + " outside 1.." + std::to_string(KA_ENS_MAX_RUNS) + " (one bit per member in the reference's POAR table)");
+        *out = nullptr;
+        std::unique_ptr<ka_ens> e(new ka_ens);
+        e->N = numseq; e->R = n_runs;
+        e->lens.assign(lens, lens + numseq);
+        e->offs.resize(numseq);
+        long long T = 0;
+        for (int s = 0; s < numseq; s++) {
+                if (lens[s] < 0) return fail("ka_ens_create: negative sequence length");
+                if (lens[s] > KA_ENS_MAX_RES)
+                        return fail("ka_ens_create: sequence " + std::to_string(s) + " has " + std::to_string(lens[s]) +
+                                    " residues; residue indices must stay below 4096 (the reference's POAR key ri << 20 | rj aliases beyond)");
+                e->offs[s] = (int)T;
+                T += lens[s];
+                e->maxlen = std::max(e->maxlen, lens[s]);
+        }
+        e->T = (int)T;
+        e->W.assign(n_runs, 0);
+        e->rows.resize(n_runs);
+        if (ka_ctx_device_stream(ctx, &e->device, &e->stream)) return fail("ka_ens_create: bad context");
+        HIPCHK(hipSetDevice(e->device));
+        const char* cc = std::getenv("KA_ENS_CHUNK");                    // candidates per chunk (tests force many chunks)
+        e->chunkCap = cc && std::atoll(cc) > 0 ? std::atoll(cc) : (1ll << 22);
+        if (e->dOffs.alloc(numseq) || e->dLens.alloc(numseq) || e->dScore.alloc(1)) return fail("ka_ens_create: out of device memory");
+        HIPCHK(hipMemcpy(e->dOffs.p, e->offs.data(), sizeof(int) * numseq, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->dLens.p, lens, sizeof(int) * numseq, hipMemcpyHostToDevice));
+        for (int b = 0; b < 2; b++) {
+                HIPCHK(hipEventCreateWithFlags(&e->ready[b], hipEventDisableTiming));
+                HIPCHK(hipEventCreate(&e->wBeg[b]));
+                HIPCHK(hipEventCreate(&e->wEnd[b]));
+        }
+        HIPCHK(hipEventCreate(&e->ev0));
+        HIPCHK(hipEventCreate(&e->ev1));
+        *out = e.release();
+        return KA_OK;
+}
+
+extern "C" void ka_ens_destroy(ka_ens* e)
+{
+        if (!e) return;
+        (void)hipSetDevice(e->device);
+        (void)hipStreamSynchronize(e->stream);
+        delete e;
+}
+
+extern "C" int ka_ens_add_member(ka_ens* e, int k, const uint8_t* rows, long long row_stride, int alnlen)
+{
+        if (!e || k < 0 || k >= e->R) return fail("ka_ens_add_member: bad arguments");
+        if (e->check_rows("ka_ens_add_member", rows, row_stride, alnlen)) return KA_FAIL;
+        HIPCHK(hipSetDevice(e->device));
+        if (e->upload_rows(e->rows[k], rows, row_stride, alnlen)) return KA_FAIL;
+        HIPCHK(hipStreamSynchronize(e->stream));
+        e->W[k] = alnlen;
+        e->mapsFresh = false;
+        e->generation++;
+        return KA_OK;
+}
+
+extern "C" int ka_ens_score_rows(ka_ens* e, const uint8_t* rows, long long row_stride, int alnlen, long long* sum_out, double* score_out)
+{
+        if (!e) return fail("ka_ens_score_rows: bad arguments");
+        if (e->check_rows("ka_ens_score_rows", rows, row_stride, alnlen)) return KA_FAIL;
+        HIPCHK(hipSetDevice(e->device));
+        if (e->ensure_maps()) return KA_FAIL;
+        KaEnsArgs a = e->args();
+        HIPCHK(hipEventRecord(e->ev0, e->stream));
+        if (e->maps_x(rows, row_stride, alnlen, a)) return KA_FAIL;
+        HIPCHK(hipMemsetAsync(e->dScore.p, 0, sizeof(unsigned long long), e->stream));
+        a.score = e->dScore.p;
+        ka_ens_launch_walk(KA_ENS_SCORE, a, e->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(e->ev1, e->stream));
+        unsigned long long s = 0;
+        HIPCHK(hipMemcpyAsync(&s, e->dScore.p, sizeof(s), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        e->st[1] = e->evMs();
+        const long long S = (long long)s;
+        if (sum_out) *sum_out = S;
+        if (score_out) *score_out = (double)S / (e->R > 1 ? (double)(e->R - 1) : 1.0);
+        return KA_OK;
+}
+
+extern "C" int ka_ens_consensus(ka_ens* e, int min_support, const uint8_t* letters, uint8_t* rows_out, long long row_stride, int* alnlen_out)
+{
+        if (!e || !letters || min_support < 1) return fail("ka_ens_consensus: bad arguments (min_support >= 1, letters)");
+        HIPCHK(hipSetDevice(e->device));
+        const bool cached = e->cacheGen == e->generation && e->cacheMin == min_support &&
+                            std::equal(e->cacheLetters.begin(), e->cacheLetters.end(), letters) && (int)e->cacheLetters.size() == e->T;
+        if (!cached && e->consensus(min_support, letters)) return KA_FAIL;
+        if (alnlen_out) *alnlen_out = e->cacheW;
+        if (!rows_out || row_stride < e->cacheW) return KA_ERR_ROWS_STRIDE;
+        for (int s = 0; s < e->N; s++)
+                std::memcpy(rows_out + (long long)s * row_stride, e->cacheRows.data() + (size_t)s * e->cacheW, e->cacheW);
+        return KA_OK;
+}
+
+extern "C" int ka_ens_confidence(ka_ens* e, const uint8_t* rows, long long row_stride, int alnlen, float* res_conf_out, float* col_conf_out)
+{
+        if (!e || !res_conf_out || !col_conf_out) return fail("ka_ens_confidence: bad arguments");
+        if (e->check_rows("ka_ens_confidence", rows, row_stride, alnlen)) return KA_FAIL;
+        HIPCHK(hipSetDevice(e->device));
+        if (e->ensure_maps()) return KA_FAIL;
+        KaEnsArgs a = e->args();
+        HIPCHK(hipEventRecord(e->ev0, e->stream));
+        if (e->maps_x(rows, row_stride, alnlen, a)) return KA_FAIL;
+        if (e->dSup.alloc((size_t)std::max(e->T, 1)) || e->dNp.alloc((size_t)std::max(e->T, 1)) ||
+            e->dConf.alloc((size_t)e->N * alnlen) || e->dColConf.alloc((size_t)alnlen))
+                return fail("ka_ens_confidence: out of device memory");
+        HIPCHK(hipMemsetAsync(e->dSup.p, 0, sizeof(int) * (size_t)std::max(e->T, 1), e->stream));
+        HIPCHK(hipMemsetAsync(e->dNp.p, 0, sizeof(int) * (size_t)std::max(e->T, 1), e->stream));
+        a.supSum = e->dSup.p; a.nPair = e->dNp.p;
+        ka_ens_launch_walk(KA_ENS_CONF, a, e->stream);
+        ka_ens_launch_conf(a, e->dConf.p, e->dColConf.p, e->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(e->ev1, e->stream));
+        HIPCHK(hipMemcpyAsync(res_conf_out, e->dConf.p, sizeof(float) * (size_t)e->N * alnlen, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(col_conf_out, e->dColConf.p, sizeof(float) * (size_t)alnlen, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        e->st[6] = e->evMs();
+        return KA_OK;
+}
+
+extern "C" int ka_ens_stats(ka_ens* e, double* stats_out, long long* level_counts_out, double* level_ms_out)
+{
+        if (!e) return fail("ka_ens_stats: bad arguments");
+        if (stats_out) std::copy_n(e->st, KA_ENS_STATS, stats_out);
+        if (level_counts_out) std::copy_n(e->levelCount, KA_ENS_MAX_RUNS + 1, level_counts_out);
+        if (level_ms_out) std::copy_n(e->levelMs, KA_ENS_MAX_RUNS + 1, level_ms_out);
+        return KA_OK;
+}

@@ -1,0 +1,41 @@
+// ka_ens.h -- the ensemble consensus stage (ka_ens.hip kernels, ka_ens.cpp host side): what the two units share.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define KA_ENS_MAX_RUNS 32
+#define KA_ENS_MAX_RES 4096        // residue index < 4096: the reference's POAR key ri << 20 | rj aliases from there on
+#define KA_ENS_STATS 10            // ka_ens_stats: see include/kalign_amd.h
+#define KA_ENS_JCHUNK 16           // j per workgroup of the support walk (4 waves, one j at a time each)
+
+enum { KA_ENS_SCORE = 0, KA_ENS_CONF = 1, KA_ENS_COUNT = 2, KA_ENS_WRITE = 3 };
+
+struct KaEnsArgs {
+        const int* offs;           // [N] first residue of sequence s in the flat residue numbering
+        const int* lens;           // [N]
+        int N, R, T, maxlen;       // sequences, members, residues, longest sequence
+        const int* col;            // [R][T]  col[k * T + offs[s] + r] = column of residue r of s in member k
+        const int16_t* res;        // member k at resOff[k]: [N][W[k]], residue of s at column c or -1
+        long long resOff[KA_ENS_MAX_RUNS];
+        int W[KA_ENS_MAX_RUNS];
+        // the alignment X of SCORE / CONF: its own tables
+        const int* colX;           // [T]
+        const int16_t* resX;       // [N][Wx]
+        int Wx;
+        int i0, i1;                // sequences i of this launch
+        int colInLds;              // member columns of sequence i staged in LDS (else read where they lie)
+        int level;                 // COUNT / WRITE: support value of the candidates
+        unsigned long long* score; // SCORE: sum of (support - 1), two's complement
+        int* supSum;               // CONF: [T] sum of support over the residue's partners
+        int* nPair;                // CONF: [T] number of partners
+        int* cnt;                  // COUNT: [N * N] candidates of pair (i, j)
+        const long long* pairOff;  // WRITE: [N * N] first slot of pair (i, j), relative to the row
+        const long long* rowBase;  // WRITE: [N] first slot of row i, relative to this chunk
+        int2* out;                 // WRITE: (element of i, element of j)
+};
+
+// ka_ens.hip
+void ka_ens_launch_maps(const uint8_t* rows, int stride, int W, int N, const int* offs, const int* lens, int* col, int16_t* res, hipStream_t s);
+void ka_ens_launch_walk(int mode, const KaEnsArgs& a, hipStream_t s);
+void ka_ens_launch_row_scan(const int* cnt, int N, long long* pairOff, long long* rowTot, int rows, hipStream_t s);
+void ka_ens_launch_conf(const KaEnsArgs& a, float* conf, float* colConf, hipStream_t s);

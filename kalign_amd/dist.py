@@ -372,8 +372,9 @@ def member_on_context(ctx, tree_codes, codes, letters, subm, n_anchors=0, weight
 
 def ensemble_members(run_member, members, rank, world, device="cpu"):
     """Member k runs on rank k % world (replicas with different parameters: no data-path collective); the aligned
-    rows of every member are gathered on every rank for the consensus stage, which stays on the host
-    (POAR tables, lib/src/ensemble.c:341-).  Returns rows[k] = list of bytes, one per sequence."""
+    rows of every member are gathered on every rank.  Returns rows[k] = list of bytes, one per sequence; the consensus
+    stage (lib/src/ensemble.c:341-: scores, selection, consensus, confidence) runs on them with
+    kalign_amd.ensemble.finish_ensemble."""
     mine = [k for k in range(len(members)) if k % world == rank]
     local = {k: run_member(members[k]) for k in mine}
     if world == 1:

@@ -1,0 +1,67 @@
+"""The end of an ensemble: kalign_ensemble's stage after the members (lib/src/ensemble.c:341-497) on the device.
+
+finish_ensemble takes the members' rows (dist.ensemble_members returns them) and does what the reference does with them:
+scores every member, picks one, tries the consensus alignment, refines the winner, and computes confidences."""
+import numpy as np
+
+from .api import KalignAmdError
+
+
+def auto_min_support(n_runs):
+    """kalign_ensemble's min_support when the caller gives none (ensemble.c:393-394)"""
+    return max(2, (n_runs + 2) // 3)
+
+
+def select(scores):
+    """score_alignments' choice (ensemble.c:121-127): member 0 unless a later one beats the best so far and member 0 by > 5 %"""
+    best = 0
+    for k in range(1, len(scores)):
+        if scores[k] > scores[best] and scores[k] > scores[0] * 1.05:
+            best = k
+    return best
+
+
+def finish_ensemble(ctx, member_rows, letters, min_support=0, rerun_refined=None):
+    """member_rows[k]: the rows of member k (bytes / str, one per sequence, input order); letters: the sequences.
+    min_support > 0: the consensus at that threshold, no selection (as kalign_ensemble with an explicit min_support).
+    min_support == 0: the consensus at auto_min_support(n_runs) wins if it scores higher than the selected member; else,
+    when rerun_refined is given, rerun_refined(best_k) must return member best_k's rows re-run with refine mode 2
+    (KALIGN_REFINE_CONFIDENT, the member's gap penalties and tree noise -- whose multipliers come from the caller's RNG)
+    and they replace the member if they score higher.
+    Returns a dict: rows (bytes), residue_confidence (float32[n, width]), column_confidence (float32[width]), scores
+    (per member), best_k, use_consensus, consensus_score (None when not computed), refined_score (None when not run),
+    refined (whether the refined rows were kept)."""
+    n_runs = len(member_rows)
+    if n_runs < 1:
+        raise KalignAmdError("an ensemble needs members")
+    letters = [x.encode() if isinstance(x, str) else bytes(x) for x in letters]
+    lens = np.array([sum(1 for b in s if chr(b).isascii() and chr(b).isalpha()) for s in letters], np.int32)
+    ens = ctx.ensemble(lens, n_runs)
+    try:
+        for k, rows in enumerate(member_rows):
+            ens.add_member(k, rows)
+        scores = [ens.score(rows)[1] for rows in member_rows]
+        best_k = select(scores)
+        out = dict(scores=scores, best_k=best_k, use_consensus=False, consensus_score=None, refined_score=None, refined=False)
+        chosen = [bytes(r.encode() if isinstance(r, str) else r) for r in member_rows[best_k]]
+        if min_support > 0:
+            chosen = ens.consensus(letters, int(min_support))
+            out["use_consensus"] = True
+        else:
+            cons = ens.consensus(letters, auto_min_support(n_runs))
+            out["consensus_score"] = ens.score(cons)[1]
+            if out["consensus_score"] > scores[best_k]:
+                chosen = cons
+                out["use_consensus"] = True
+        if not out["use_consensus"] and rerun_refined is not None:
+            refined = [bytes(r.encode() if isinstance(r, str) else r) for r in rerun_refined(best_k)]
+            out["refined_score"] = ens.score(refined)[1]
+            if out["refined_score"] > scores[best_k]:
+                chosen = refined
+                out["refined"] = True
+        out["rows"] = chosen
+        out["residue_confidence"], out["column_confidence"] = ens.confidence(chosen)
+        out["stats"] = ens.stats()
+        return out
+    finally:
+        ens.close()
