@@ -11,7 +11,13 @@ x ~400 aa (DSSim family), the reference's `--fast` mode, on the REFERENCE'S OWN 
 (build_tree_kmeans through ka_guide_tree; its time is reported separately).
 Secondary legs with their own roofline objects: C2 (1024 x 400) and C3 (4096 DNA x 2000).
 
-    python bench.py [--gpus N --steps K --warmup W] [--nseq 4096 --len 400 --dna]
+    python bench.py [--gpus N --steps K --warmup W] [--nseq 4096 --len 400 --dna] [--full]
+
+A plain run does what the headline line needs and no more: it builds the job, runs the W + K steps, writes the
+outputs of --dump-outputs and prints the line (value, ms_per_step, and the roofline objects of the timed steps).
+--full adds everything else, each outside the timed steps: the guide tree's time, the measured profile-profile rate,
+the CPU baselines (the reference itself, gaps compared), the legs (other workloads, modes and brackets) and, for N > 1,
+the whole-tree check and the weak-scaling replicas.  --no-cpu, --no-legs (--quick: both), --no-c3 and --no-c4 trim --full.
 
 --dump-outputs DIR: after the timed steps, what the last one returned (records, coded paths, gap arrays) as
 DIR/<name>.npy, to compare two builds output for output (see dump_outputs()).
@@ -120,21 +126,25 @@ def physical_cores():
         return None
 
 
-def make_job(ctx, nseq, length, dna, seed):
+def make_job(ctx, nseq, length, dna, seed, time_tree=True):
     """Letters -> what kalign_run hands create_msa_tree: the sequences in msa_sort_len_name order (longest first,
     msa_sort.c:62-80), encoded, and the reference's own guide tree (build_tree_kmeans, bisectingKmeans.c:177-271,
     through ka_guide_tree: distances on the device, 2-means / UPGMA on the host).  The tree's time is reported,
-    never part of a timed step ("tree building excluded")."""
+    never part of a timed step ("tree building excluded"); time_tree=False builds the tree once,
+    without the warm-up call its time needs, and leaves guide_tree_ms None."""
     from kalign_amd import guide
     inp = workload_letters(nseq, length, dna, seed)
     order = sorted(range(len(inp)), key=lambda i: (-len(inp[i]), i))
     seqs = [inp[i] for i in order]
     tcodes = guide.encode_tree(seqs, dna=dna)
     codes = guide.encode(seqs, dna=dna)
-    ctx.guide_tree(tcodes, n_threads=host_threads())               # warm-up (allocations)
+    gt_ms = None
+    if time_tree:
+        ctx.guide_tree(tcodes, n_threads=host_threads())           # warm-up (allocations)
     t0 = time.perf_counter()
     tasks, sd = ctx.guide_tree(tcodes, n_threads=host_threads())
-    gt_ms = (time.perf_counter() - t0) * 1e3
+    if time_tree:
+        gt_ms = (time.perf_counter() - t0) * 1e3
     return {"input": inp, "order": order, "seqs": seqs, "codes": codes, "tasks": tasks, "seq_distances": sd,
             "guide_tree_ms": gt_ms, "nseq": nseq, "len": length, "dna": dna}
 
@@ -887,7 +897,7 @@ def sharding_projection(ctx, job, subm, scal, lens, cons_ms, worlds=(2, 4, 8)):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -895,19 +905,27 @@ def main():
     ap.add_argument("--nseq", type=int, default=4096)
     ap.add_argument("--len", type=int, default=400)
     ap.add_argument("--dna", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="headline line only (profiling runs)")
-    ap.add_argument("--quick", action="store_true", help="= --no-legs --no-cpu: the headline line in seconds (profiling iterations)")
-    ap.add_argument("--no-c3", action="store_true")
-    ap.add_argument("--no-c4", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline line: guide-tree time, profile-profile rate, CPU baselines, legs; for N > 1 the "
+                         "whole-tree check and the weak-scaling replicas")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-legs", action="store_true", help="--full without the legs")
+    ap.add_argument("--quick", action="store_true", help="= --no-legs --no-cpu")
+    ap.add_argument("--no-c3", action="store_true", help="--full without the C3 leg")
+    ap.add_argument("--no-c4", action="store_true", help="--full without the C4 and C5 legs")
     ap.add_argument("--scale-workload", action="store_true", help="N > 1: shard --nseq x --len instead of C4 (tests)")
     ap.add_argument("--scale-fast", action="store_true", help="N > 1: --fast mode instead of the default mode")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed to DIR/<name>.npy")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-    if args.quick:
+    if args.quick or not args.full:
         args.no_legs = args.no_cpu = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     import torch
     import kalign_amd
@@ -925,7 +943,7 @@ def main():
 
     stream = torch.cuda.current_stream().cuda_stream
     ctx = kalign_amd.Context(local_rank, stream=stream)
-    job = make_job(ctx, args.nseq, args.len, args.dna, seed=1)
+    job = make_job(ctx, args.nseq, args.len, args.dna, seed=1, time_tree=args.full)
     subm, scal = scoring(args.dna)
 
     def barrier():
@@ -961,7 +979,8 @@ def main():
         "roofline": roofline_of(res, key, workload_name(job, res)),
         "roofline_valu": roofline_valu(res["recs"], cells * args.steps / elapsed / 1e9),
     }
-    out["config"]["gcups_profile_profile"] = pp_rate_leg(ctx, job, subm, scal)
+    if args.full:
+        out["config"]["gcups_profile_profile"] = pp_rate_leg(ctx, job, subm, scal)
     if not args.no_legs:
         # SURVEY.md 8(d)'s t_DP bracket (H2D of sequences and tasks + run + D2H of records and paths).  The bench contract
         # keeps `value` on inputs resident in HBM ("the PCIe-inclusive rate ... is never `value`"); the bracket the survey
@@ -1030,7 +1049,7 @@ def multi_gpu_main(args, rank, world, local_rank):
     # side, past the GPU's caches
     coll_dev = "cpu" if same_gpu else "cuda"
     nseq, length = (args.nseq, args.len) if args.scale_workload else (16384, 500)
-    job = make_job(ctx, nseq, length, False, seed=1)               # every rank: the same sequences, the same guide tree
+    job = make_job(ctx, nseq, length, False, seed=1, time_tree=args.full)     # every rank: the same sequences, the same guide tree
     subm, scal = scoring(False)
     lens = np.array([len(c) for c in job["codes"]], np.int64)
     anchors = 0 if args.scale_fast else 5
@@ -1105,11 +1124,12 @@ def multi_gpu_main(args, rank, world, local_rank):
     if anchors:
         ids = ctx.tree_consistency()[0] if ctx.tree_consistency() else []
         pair_cells = float(sum(int(lens[i]) * int(lens[a]) for i in range(len(lens)) for a in ids if a != i))
-    # every rank holds every record and path: a checksum over all of them must agree across the ranks
-    chk = int(np.asarray(paths, np.int64).sum() % (1 << 31)) ^ int(sum(r.plen for r in recs))
-    chk_max = kd.reduce_scalar(float(chk), "max", device=coll_dev)
-    same_as_one_gpu = None
-    if rank == 0:
+    same_on_all_ranks, same_as_one_gpu, single_ms = None, None, None
+    if args.full:
+        # every rank holds every record and path: a checksum over all of them must agree across the ranks
+        chk = int(np.asarray(paths, np.int64).sum() % (1 << 31)) ^ int(sum(r.plen for r in recs))
+        same_on_all_ranks = bool(kd.reduce_scalar(float(chk), "max", device=coll_dev) == float(chk))
+    if args.full and rank == 0:
         # the same job as ONE whole-tree run on this rank's GPU (outside the timed region): results must not depend on N
         def single():
             if anchors:
@@ -1133,27 +1153,28 @@ def multi_gpu_main(args, rank, world, local_rank):
     # guide tree's serial top costs -- one independent alignment per GPU (the headline tree, --fast: what a caller with many
     # alignments, or the members of an ensemble, see), no data-path collective, the same barrier and max-over-ranks timing.
     weak = None
-    try:
-        wjob = make_job(ctx, 4096, 400, False, seed=1)
-        ctx.tree_upload(wjob["codes"], wjob["tasks"], subm, scal, wjob["seq_distances"])
-        for _ in range(2):
-            ctx.tree_run()
-        ctx.tree_sync()
-        barrier()
-        tw = time.perf_counter()
-        wsteps = max(args.steps, 3)
-        for _ in range(wsteps):
-            ctx.tree_run()
-        ctx.tree_sync()
-        barrier()
-        w_elapsed = kd.reduce_scalar(time.perf_counter() - tw, "max", device=coll_dev)
-        wrecs, _, _ = ctx.tree_download(want_gaps=False)
-        wcells = float(sum(r.len_a * r.len_b for r in wrecs))
-        weak = {"workload": "one 4096 x ~400 protein tree (--fast) per GPU, independent replicas, no collective in the timed steps",
-                "scaling": "weak", "gcups": wcells * world * wsteps / w_elapsed / 1e9, "ms_per_step": w_elapsed / wsteps * 1e3,
-                "gcups_per_gpu": wcells * wsteps / w_elapsed / 1e9, "steps": wsteps}
-    except Exception as e:                                         # pragma: no cover
-        sys.stderr.write("rank %d: weak-scaling leg failed (%s)\n" % (rank, e))
+    if args.full:
+        try:
+            wjob = make_job(ctx, 4096, 400, False, seed=1)
+            ctx.tree_upload(wjob["codes"], wjob["tasks"], subm, scal, wjob["seq_distances"])
+            for _ in range(2):
+                ctx.tree_run()
+            ctx.tree_sync()
+            barrier()
+            tw = time.perf_counter()
+            wsteps = max(args.steps, 3)
+            for _ in range(wsteps):
+                ctx.tree_run()
+            ctx.tree_sync()
+            barrier()
+            w_elapsed = kd.reduce_scalar(time.perf_counter() - tw, "max", device=coll_dev)
+            wrecs, _, _ = ctx.tree_download(want_gaps=False)
+            wcells = float(sum(r.len_a * r.len_b for r in wrecs))
+            weak = {"workload": "one 4096 x ~400 protein tree (--fast) per GPU, independent replicas, no collective in the timed steps",
+                    "scaling": "weak", "gcups": wcells * world * wsteps / w_elapsed / 1e9, "ms_per_step": w_elapsed / wsteps * 1e3,
+                    "gcups_per_gpu": wcells * wsteps / w_elapsed / 1e9, "steps": wsteps}
+        except Exception as e:                                     # pragma: no cover
+            sys.stderr.write("rank %d: weak-scaling leg failed (%s)\n" % (rank, e))
     if rank == 0:
         kinds = np.bincount([r.kind for r in recs], minlength=3)
         real_stdout.write(json.dumps({
@@ -1169,13 +1190,13 @@ def multi_gpu_main(args, rank, world, local_rank):
                        "nseq": nseq, "len": length, "mode": "default (5 anchors)" if anchors else "--fast",
                        "useful_cells_tree": cells, "useful_cells_consistency_batch": pair_cells,
                        "guide_tree_ms_every_rank": job["guide_tree_ms"],
-                       "identical_results_on_all_ranks": bool(chk_max == float(chk)),
+                       "identical_results_on_all_ranks": same_on_all_ranks,
                        "identical_to_a_single_gpu_run": same_as_one_gpu,
                        "dist_layer": dist_layer},
             # the same job as one whole-tree run on rank 0's GPU (no sharding layer at all), timed after the steps; at
             # N = 1 (KA_BENCH_FORCE_MULTI=1) the difference is what the sharding layer itself costs
             "single_gpu_step_ms": single_ms,
-            "sharding_overhead_ms": (elapsed / args.steps * 1e3 - single_ms) if world == 1 else None,
+            "sharding_overhead_ms": (elapsed / args.steps * 1e3 - single_ms) if world == 1 and single_ms is not None else None,
             "weak_scaling_replicas": weak,
         }) + "\n")
         real_stdout.flush()

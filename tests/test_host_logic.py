@@ -149,3 +149,17 @@ def test_bench_dump_outputs_holds_what_the_tree_returned(oracle, tmp_path):
         a, rows = (np.load(str(tmp_path / "cut0" / (n + s))) for s in (".npy", "_rows.npy"))
         assert np.array_equal(a, np.load(str(tmp_path / "cut1" / (n + ".npy"))))
         assert len(rows) > 0 and np.array_equal(a, z[n][rows.astype(np.int64)])
+
+
+def test_bench_plain_run_leaves_every_leg_to_full():
+    """bench.py without --full: the headline line alone (no legs, no CPU baselines); --full runs them, and --no-legs /
+    --no-cpu / --quick trim it."""
+    import bench
+    plain = bench.parse_args(["--steps", "5", "--warmup", "2"])
+    assert (plain.full, plain.no_legs, plain.no_cpu) == (False, True, True)
+    assert (plain.steps, plain.warmup) == (5, 2)
+    full = bench.parse_args(["--full"])
+    assert (full.full, full.no_legs, full.no_cpu, full.no_c3, full.no_c4) == (True, False, False, False, False)
+    assert (bench.parse_args(["--full", "--no-cpu"]).no_legs, bench.parse_args(["--full", "--no-cpu"]).no_cpu) == (False, True)
+    quick = bench.parse_args(["--full", "--quick"])
+    assert (quick.no_legs, quick.no_cpu) == (True, True)
