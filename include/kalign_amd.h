@@ -478,6 +478,37 @@ int  ka_ens_consensus(ka_ens* e, int min_support, const uint8_t* letters, uint8_
 int  ka_ens_confidence(ka_ens* e, const uint8_t* rows, long long row_stride, int alnlen, float* res_conf_out, float* col_conf_out);
 int  ka_ens_stats(ka_ens* e, double* stats_out, long long* level_counts_out, double* level_ms_out);
 
+/* ---- scoring an alignment against a reference alignment (ka_cmp.hip, ka_cmp.cpp) -------------------------------------------
+ * kalign_msa_compare, kalign_msa_compare_detailed and kalign_msa_compare_with_mask (lib/src/msa_cmp.c) on the device.  Both
+ * alignments hold the same numseq sequences in the same row order (the reference pairs its rows after sorting both by name;
+ * the caller does that).  A residue is an ASCII letter (isalpha in the C locale), every other byte a gap.  Every count is
+ * exact and every double comes from the reference's expression: the results are bit-identical.
+ *   ka_cmp_create        the reference alignment: numseq >= 2 rows of alnlen bytes, row_stride apart, row s with lens[s] letters
+ *                        (at most 32767).  Builds its position maps once.  Runs on ctx's device and stream: destroy it before ctx.
+ *   ka_cmp_set_mask      the scored columns of the detailed counts: with mask NULL every column when max_gap_frac < 0, else a
+ *                        column whose (float)gaps / (float)numseq <= max_gap_frac (kalign_msa_compare_detailed); with a mask
+ *                        (n_cols must equal the reference's alnlen) the columns where it is non-zero (kalign_msa_compare_with_mask).
+ *                        Until it is called, every column is scored.
+ *   ka_cmp_score         one test alignment.  Fails when the width does not fit the stride or a row's letter count differs
+ *                        from lens[s].  counts_out[12] (optional): struct cmp_stats' six counts (ref_total_aligned_pairs,
+ *                        ref_total_gap_pairs, identical_aligned, identical_gaps, test_total_aligned_pairs, test_total_gap_pairs),
+ *                        the four detailed counts (ref_scored_pairs, test_pairs, common_scored, common_all), tc_correct, tc_total.
+ *                        scores_out[5] (optional): recall, precision, f1, tc (struct poar_score) and the SP score in double;
+ *                        sp_out (optional): the float kalign_msa_compare returns.
+ *   ka_cmp_score_batch   n_tests test alignments (their own widths and strides), counts_out[n_tests * 12], scores_out[n_tests * 5],
+ *                        sp_out[n_tests]: exactly what n_tests calls of ka_cmp_score return, with fewer launches.
+ *   ka_cmp_stats         device ms: stats_out[4] = the reference's maps (ka_cmp_create), the test maps, the pair walk and the TC
+ *                        pass of the last score call (summed over a batch).
+ */
+typedef struct ka_cmp ka_cmp;
+int  ka_cmp_create(ka_ctx* ctx, int numseq, const int* lens, const uint8_t* ref_rows, long long row_stride, int alnlen, ka_cmp** out);
+void ka_cmp_destroy(ka_cmp* h);
+int  ka_cmp_set_mask(ka_cmp* h, float max_gap_frac, const int* mask, int n_cols);
+int  ka_cmp_score(ka_cmp* h, const uint8_t* test_rows, long long row_stride, int alnlen, long long* counts_out, double* scores_out, float* sp_out);
+int  ka_cmp_score_batch(ka_cmp* h, int n_tests, const uint8_t* const* test_rows, const long long* row_strides, const int* alnlens,
+                        long long* counts_out, double* scores_out, float* sp_out);
+int  ka_cmp_stats(ka_cmp* h, double* stats_out);
+
 #ifdef __cplusplus
 }
 #endif

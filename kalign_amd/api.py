@@ -57,7 +57,8 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_guide_last_bisect_ms", "ka_device_count", "ka_multi_create", "ka_multi_destroy", "ka_multi_world", "ka_multi_runs", "ka_multi_last_error",
            "ka_multi_consistency", "ka_multi_tree_run", "ka_multi_paths_size", "ka_multi_download", "ka_multi_ctx", "ka_multi_adopt",
            "ka_tree_adopt_alignment", "ka_ens_create", "ka_ens_destroy", "ka_ens_add_member", "ka_ens_score_rows", "ka_ens_consensus",
-           "ka_ens_confidence", "ka_ens_stats"]
+           "ka_ens_confidence", "ka_ens_stats", "ka_cmp_create", "ka_cmp_destroy", "ka_cmp_set_mask", "ka_cmp_score",
+           "ka_cmp_score_batch", "ka_cmp_stats"]
 
 
 def lib_path():
@@ -187,6 +188,13 @@ def load_library():
     L.ka_ens_consensus.argtypes = [vp, C.c_int, vp, vp, C.c_longlong, C.POINTER(C.c_int)]
     L.ka_ens_confidence.argtypes = [vp, vp, C.c_longlong, C.c_int, vp, vp]
     L.ka_ens_stats.argtypes = [vp, vp, vp, vp]
+    L.ka_cmp_create.argtypes = [vp, C.c_int, vp, vp, C.c_longlong, C.c_int, C.POINTER(vp)]
+    L.ka_cmp_destroy.argtypes = [vp]
+    L.ka_cmp_destroy.restype = None
+    L.ka_cmp_set_mask.argtypes = [vp, C.c_float, vp, C.c_int]
+    L.ka_cmp_score.argtypes = [vp, vp, C.c_longlong, C.c_int, vp, vp, vp]
+    L.ka_cmp_score_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.ka_cmp_stats.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -230,8 +238,8 @@ class Context:
         return self
 
     def close(self):
-        # ensembles borrow this context's stream: they go first
-        for e in list(getattr(self, "_ensembles", ())):
+        # ensembles and comparers borrow this context's stream: they go first
+        for e in list(getattr(self, "_ensembles", ())) + list(getattr(self, "_comparers", ())):
             e.close()
         if getattr(self, "h", None):
             if not getattr(self, "_borrowed", False):
@@ -718,6 +726,107 @@ def _ens_create(self, lens, n_runs):
 
 
 Context.ensemble = _ens_create
+
+
+CMP_COUNTS = ["ref_total_aligned_pairs", "ref_total_gap_pairs", "identical_aligned", "identical_gaps",
+              "test_total_aligned_pairs", "test_total_gap_pairs", "ref_scored_pairs", "test_pairs", "common_scored",
+              "common_all", "tc_correct", "tc_total"]
+
+
+def _cmp_result(counts, scores, sp):
+    """one test's outputs of ka_cmp_score as a dict: python-kalign's keys (compare, compare_detailed), then the raw counts"""
+    d = dict(sp=float(sp), recall=float(scores[0]), precision=float(scores[1]), f1=float(scores[2]), tc=float(scores[3]),
+             ref_pairs=int(counts[6]), test_pairs=int(counts[7]), common_pairs=int(counts[8]), sp_double=float(scores[4]))
+    d.update({k: int(v) for k, v in zip(CMP_COUNTS, counts)})
+    return d
+
+
+class Comparer:
+    """A reference alignment on the device (ka_cmp) that test alignments of the same sequences are scored against, as
+    kalign_msa_compare (sp) and kalign_msa_compare_detailed / _with_mask (recall, precision, f1, tc) score them.  Rows
+    are paired by position: kalign_amd.compare pairs named rows the way the reference does."""
+
+    def __init__(self, ctx, ref_rows):
+        self.ctx, self.L = ctx, ctx.L
+        self.h = None
+        if not ctx.h:
+            raise KalignAmdError("the context is closed")
+        rows = [x.encode() if isinstance(x, str) else bytes(x) for x in ref_rows]
+        self.n = len(rows)
+        if self.n < 2:
+            raise KalignAmdError("a comparison needs two sequences at least (%d given)" % self.n)
+        a, w = _rows_array(rows, self.n)
+        self.width = w
+        self.lens = np.ascontiguousarray([sum(1 for b in r if 97 <= (b | 32) <= 122) for r in rows], np.int32)   # isalpha, C locale
+        h = C.c_void_p()
+        ctx._chk(self.L.ka_cmp_create(ctx.h, self.n, _ptr(self.lens), _ptr(a), w, w, C.byref(h)))
+        self.h = h
+        if not hasattr(ctx, "_comparers"):
+            ctx._comparers = weakref.WeakSet()
+        ctx._comparers.add(self)
+
+    def close(self):
+        """frees the device state; a closed context has closed its comparers already (Context.close)"""
+        if self.h:
+            self.L.ka_cmp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _set_mask(self, max_gap_frac, column_mask):
+        if column_mask is None:
+            self.ctx._chk(self.L.ka_cmp_set_mask(self.h, float(max_gap_frac), None, 0))
+        else:
+            m = np.ascontiguousarray(column_mask, np.int32).reshape(-1)
+            self.ctx._chk(self.L.ka_cmp_set_mask(self.h, float(max_gap_frac), _ptr(m), len(m)))
+
+    def _test_array(self, rows):
+        rows = [x.encode() if isinstance(x, str) else bytes(x) for x in rows]
+        if len(rows) != self.n:
+            raise KalignAmdError("the test alignment has %d rows, the reference %d" % (len(rows), self.n))
+        return _rows_array(rows, self.n)
+
+    def score(self, test_rows, max_gap_frac=-1.0, column_mask=None):
+        """one test alignment: column_mask (one int per reference column, non-zero = scored) as
+        kalign_msa_compare_with_mask, else max_gap_frac as kalign_msa_compare_detailed (< 0: every column)"""
+        return self.score_many([test_rows], max_gap_frac, column_mask)[0]
+
+    def score_many(self, tests, max_gap_frac=-1.0, column_mask=None):
+        """several test alignments of the same sequences against the reference (ka_cmp_score_batch): what score()
+        returns for each"""
+        if not self.h:
+            raise KalignAmdError("the comparer is closed")
+        self._set_mask(max_gap_frac, column_mask)
+        arrs = [self._test_array(t) for t in tests]
+        K = len(arrs)
+        if K == 0:
+            return []
+        ptrs = (C.c_void_p * K)(*[a.ctypes.data for a, _ in arrs])
+        strides = np.array([w for _, w in arrs], np.int64)
+        widths = np.array([w for _, w in arrs], np.int32)
+        counts = np.zeros((K, 12), np.int64)
+        scores = np.zeros((K, 5), np.float64)
+        sp = np.zeros(K, np.float32)
+        self.ctx._chk(self.L.ka_cmp_score_batch(self.h, K, ptrs, _ptr(strides), _ptr(widths), _ptr(counts), _ptr(scores), _ptr(sp)))
+        return [_cmp_result(counts[k], scores[k], sp[k]) for k in range(K)]
+
+    def stats(self):
+        """device ms (ka_cmp_stats): the reference's maps, then the test maps, the walk and TC of the last score call"""
+        st = np.zeros(4, np.float64)
+        self.ctx._chk(self.L.ka_cmp_stats(self.h, _ptr(st)))
+        return dict(zip(["ref_maps_ms", "maps_ms", "walk_ms", "tc_ms"], st.tolist()))
+
+
+def _cmp_create(self, ref_rows):
+    """ka_cmp_create: a Comparer holding ref_rows (one row per sequence) on this context's device"""
+    return Comparer(self, ref_rows)
+
+
+Context.comparer = _cmp_create
 
 
 def guide_tree_from(lens, dist, n_threads=1, dm_scale=None):
