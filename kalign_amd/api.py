@@ -239,7 +239,7 @@ class Context:
 
     def close(self):
         # ensembles and comparers borrow this context's stream: they go first
-        for e in list(getattr(self, "_ensembles", ())) + list(getattr(self, "_comparers", ())):
+        for e in list(getattr(self, "_children", ())):
             e.close()
         if getattr(self, "h", None):
             if not getattr(self, "_borrowed", False):
@@ -633,6 +633,40 @@ def _run_encoded(self, tree_codes, codes, letters, subm, scal, n_anchors=0, weig
 Context.run_encoded = _run_encoded
 
 
+def residue_lens(rows):
+    """letters per row (bytes / str, any lengths) as int32: a residue is an ASCII letter, every other byte a gap
+    (ka_msa_is_residue, csrc/ka_msa.h)"""
+    out = np.zeros(len(rows), np.int32)
+    for k, r in enumerate(rows):
+        b = np.frombuffer(r.encode() if isinstance(r, str) else bytes(r), np.uint8) | 32
+        out[k] = np.count_nonzero((b >= 97) & (b <= 122))
+    return out
+
+
+class _CtxChild:
+    """a handle that borrows its context's stream (Ensemble, Comparer): registered with the context, which closes it
+    before it closes itself (Context.close); _destroy names the C function that frees the handle"""
+    h = None
+
+    def _adopt(self, ctx, h):
+        self.h = h
+        if not hasattr(ctx, "_children"):
+            ctx._children = weakref.WeakSet()
+        ctx._children.add(self)
+
+    def close(self):
+        """frees the device state; a closed context has closed its children already"""
+        if self.h:
+            getattr(self.L, self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _rows_array(rows, n):
     """equal-length rows (bytes / str) -> (uint8[n, width], width)"""
     rows = [x.encode() if isinstance(x, str) else bytes(x) for x in rows]
@@ -644,35 +678,20 @@ def _rows_array(rows, n):
     return np.frombuffer(b"".join(rows), np.uint8).reshape(n, width), width
 
 
-class Ensemble:
+class Ensemble(_CtxChild):
     """The consensus stage of an ensemble (ka_ens): the members' rows on the device, then scores, the consensus alignment
     and confidences of any alignment of the same sequences.  Rows are in the members' sequence order."""
+    _destroy = "ka_ens_destroy"
 
     def __init__(self, ctx, lens, n_runs):
         self.ctx, self.L = ctx, ctx.L
         self.lens = np.ascontiguousarray(lens, np.int32)
         self.n, self.n_runs = len(self.lens), int(n_runs)
         h = C.c_void_p()
-        self.h = None
         if not ctx.h:
             raise KalignAmdError("the context is closed")
         ctx._chk(self.L.ka_ens_create(ctx.h, self.n, _ptr(self.lens), self.n_runs, C.byref(h)))
-        self.h = h
-        if not hasattr(ctx, "_ensembles"):
-            ctx._ensembles = weakref.WeakSet()
-        ctx._ensembles.add(self)
-
-    def close(self):
-        """frees the device state; a closed context has closed its ensembles already (Context.close)"""
-        if self.h:
-            self.L.ka_ens_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._adopt(ctx, h)
 
     def add_member(self, k, rows):
         a, w = _rows_array(rows, self.n)
@@ -741,41 +760,26 @@ def _cmp_result(counts, scores, sp):
     return d
 
 
-class Comparer:
+class Comparer(_CtxChild):
     """A reference alignment on the device (ka_cmp) that test alignments of the same sequences are scored against, as
     kalign_msa_compare (sp) and kalign_msa_compare_detailed / _with_mask (recall, precision, f1, tc) score them.  Rows
     are paired by position: kalign_amd.compare pairs named rows the way the reference does."""
+    _destroy = "ka_cmp_destroy"
 
     def __init__(self, ctx, ref_rows):
         self.ctx, self.L = ctx, ctx.L
-        self.h = None
         if not ctx.h:
             raise KalignAmdError("the context is closed")
-        rows = [x.encode() if isinstance(x, str) else bytes(x) for x in ref_rows]
+        rows = list(ref_rows)
         self.n = len(rows)
         if self.n < 2:
             raise KalignAmdError("a comparison needs two sequences at least (%d given)" % self.n)
         a, w = _rows_array(rows, self.n)
         self.width = w
-        self.lens = np.ascontiguousarray([sum(1 for b in r if 97 <= (b | 32) <= 122) for r in rows], np.int32)   # isalpha, C locale
+        self.lens = residue_lens(rows)
         h = C.c_void_p()
         ctx._chk(self.L.ka_cmp_create(ctx.h, self.n, _ptr(self.lens), _ptr(a), w, w, C.byref(h)))
-        self.h = h
-        if not hasattr(ctx, "_comparers"):
-            ctx._comparers = weakref.WeakSet()
-        ctx._comparers.add(self)
-
-    def close(self):
-        """frees the device state; a closed context has closed its comparers already (Context.close)"""
-        if self.h:
-            self.L.ka_cmp_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._adopt(ctx, h)
 
     def _set_mask(self, max_gap_frac, column_mask):
         if column_mask is None:
@@ -785,7 +789,7 @@ class Comparer:
             self.ctx._chk(self.L.ka_cmp_set_mask(self.h, float(max_gap_frac), _ptr(m), len(m)))
 
     def _test_array(self, rows):
-        rows = [x.encode() if isinstance(x, str) else bytes(x) for x in rows]
+        rows = list(rows)
         if len(rows) != self.n:
             raise KalignAmdError("the test alignment has %d rows, the reference %d" % (len(rows), self.n))
         return _rows_array(rows, self.n)

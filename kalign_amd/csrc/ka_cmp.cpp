@@ -9,12 +9,11 @@
 // (the reference reads out of bounds otherwise).  Two sequences at least.
 #include "ka_ctx.h"
 #include "ka_cmp.h"
+#include "ka_msa.h"
 
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
 
 namespace {
-
-inline bool is_residue(uint8_t b) { return (unsigned)((b | 32u) - 'a') < 26u; }
 
 constexpr int kGroup = 32;         // test alignments per device pass of ka_cmp_score_batch
 
@@ -23,10 +22,9 @@ constexpr int kGroup = 32;         // test alignments per device pass of ka_cmp_
 struct ka_cmp {
         int device = 0;
         hipStream_t stream = nullptr;
-        int N = 0, T = 0, WR = 0, WRp = 0;
-        long long sumL = 0;
-        std::vector<int> lens, offs;                   // offs[N] = T
-        DevBuf<int> dOffs, dLens, dSeqOf, dColR, dColCnt, dMask, dColT, dTWp;
+        KaSeqSet q;
+        int WR = 0, WRp = 0;
+        DevBuf<int> dSeqOf, dColR, dColCnt, dMask, dColT, dTWp;
         DevBuf<int16_t> dResR, dResT;
         DevBuf<uint8_t> dRows, dScored;
         DevBuf<long long> dTResOff, dSlab, dSums;
@@ -38,29 +36,13 @@ struct ka_cmp {
         {
                 for (auto& e : ev)
                         if (e) (void)hipEventDestroy(e);
-                dOffs.release(); dLens.release(); dSeqOf.release(); dColR.release(); dColCnt.release(); dMask.release();
+                q.release();
+                dSeqOf.release(); dColR.release(); dColCnt.release(); dMask.release();
                 dColT.release(); dTWp.release(); dResR.release(); dResT.release(); dRows.release(); dScored.release();
                 dTResOff.release(); dSlab.release(); dSums.release(); dTc.release();
         }
 
         float ms(int a, int b) { float m = 0.0f; (void)hipEventElapsedTime(&m, ev[a], ev[b]); return m; }
-
-        // rows of an alignment of the sequences: every row's letter count must be its sequence's length
-        int check_rows(const char* who, const uint8_t* r, long long stride, int alnlen)
-        {
-                if (!r) return fail(std::string(who) + ": no rows");
-                if (alnlen <= 0 || stride < alnlen)
-                        return fail(std::string(who) + ": alignment width " + std::to_string(alnlen) + " does not fit row stride " + std::to_string(stride));
-                for (int s = 0; s < N; s++) {
-                        const uint8_t* row = r + (long long)s * stride;
-                        int n = 0;
-                        for (int c = 0; c < alnlen; c++) n += is_residue(row[c]);
-                        if (n != lens[s])
-                                return fail(std::string(who) + ": row " + std::to_string(s) + " holds " + std::to_string(n) + " residues, the reference row " +
-                                            std::to_string(lens[s]) + " (both alignments must hold the same sequences)");
-                }
-                return KA_OK;
-        }
 
         int score(int K, const uint8_t* const* rows, const long long* strides, const int* alnlens, long long* counts, double* scores, float* sp);
 };
@@ -68,6 +50,7 @@ struct ka_cmp {
 // K <= kGroup test alignments, checked by the caller
 int ka_cmp::score(int K, const uint8_t* const* rows, const long long* strides, const int* alnlens, long long* counts, double* scores, float* sp)
 {
+        const int N = q.N, T = q.T;
         std::vector<long long> rowOff(K + 1, 0), resOff(K + 1, 0);
         std::vector<int> wp(K);
         int maxWTp = 0;
@@ -93,17 +76,17 @@ int ka_cmp::score(int K, const uint8_t* const* rows, const long long* strides, c
             dTc.alloc((size_t)2 * K))
                 return fail("ka_cmp_score: out of device memory");
         for (int k = 0; k < K; k++)
-                HIPCHK(hipMemcpy2DAsync(dRows.p + rowOff[k], alnlens[k], rows[k], strides[k], alnlens[k], N, hipMemcpyHostToDevice, stream));
+                if (ka_msa_upload_rows(q, dRows.p + rowOff[k], rows[k], strides[k], alnlens[k], stream)) return KA_FAIL;
         HIPCHK(hipMemcpyAsync(dTResOff.p, resOff.data(), sizeof(long long) * K, hipMemcpyHostToDevice, stream));
         HIPCHK(hipMemcpyAsync(dTWp.p, wp.data(), sizeof(int) * K, hipMemcpyHostToDevice, stream));
         HIPCHK(hipMemsetAsync(dTc.p, 0, sizeof(unsigned long long) * 2 * K, stream));
         HIPCHK(hipEventRecord(ev[0], stream));
         for (int k = 0; k < K; k++)
-                ka_cmp_launch_maps(dRows.p + rowOff[k], alnlens[k], wp[k], N, dOffs.p, dLens.p, dColT.p + (long long)k * T, dResT.p + resOff[k], stream);
+                ka_msa_launch_maps(dRows.p + rowOff[k], alnlens[k], alnlens[k], wp[k], q, dColT.p + (long long)k * T, dResT.p + resOff[k], stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev[1], stream));
         KaCmpArgs a{};
-        a.N = N; a.T = T; a.offs = dOffs.p; a.seqOf = dSeqOf.p;
+        a.N = N; a.T = T; a.offs = q.dOffs; a.seqOf = dSeqOf.p;
         a.colR = dColR.p; a.resR = dResR.p; a.WR = WR; a.WRp = WRp; a.scored = dScored.p;
         a.colT = dColT.p; a.resT = dResT.p; a.tResOff = dTResOff.p; a.tWp = dTWp.p; a.maxWTp = maxWTp;
         a.TJ = TJ; a.nTI = nTI; a.nTJ = nTJ;
@@ -121,7 +104,7 @@ int ka_cmp::score(int K, const uint8_t* const* rows, const long long* strides, c
         HIPCHK(hipStreamSynchronize(stream));
         st[1] += ms(0, 1); st[2] += ms(1, 2); st[3] += ms(2, 3);
         // every residue has N - 1 partners in each alignment: aligned or gap
-        const uint64_t all = (uint64_t)(N - 1) * (uint64_t)sumL;
+        const uint64_t all = (uint64_t)(N - 1) * (uint64_t)T;
         for (int k = 0; k < K; k++) {
                 const long long* w = &sums[(size_t)k * KA_CMP_WALK];
                 // struct cmp_stats, in its field order
@@ -163,41 +146,26 @@ extern "C" int ka_cmp_create(ka_ctx* ctx, int numseq, const int* lens, const uin
         *out = nullptr;
         if (numseq < 2) return fail("ka_cmp_create: " + std::to_string(numseq) + " sequences; a comparison needs two at least");
         std::unique_ptr<ka_cmp> h(new ka_cmp);
-        h->N = numseq;
-        h->lens.assign(lens, lens + numseq);
-        h->offs.resize(numseq + 1);
-        long long T = 0;
-        for (int s = 0; s < numseq; s++) {
-                if (lens[s] < 0) return fail("ka_cmp_create: negative sequence length");
-                if (lens[s] > KA_CMP_MAX_RES)
-                        return fail("ka_cmp_create: sequence " + std::to_string(s) + " has " + std::to_string(lens[s]) + " residues; the position maps hold at most " +
-                                    std::to_string(KA_CMP_MAX_RES));
-                h->offs[s] = (int)T;
-                T += lens[s];
-                if (T > INT32_MAX) return fail("ka_cmp_create: more than 2^31 - 1 residues");
-        }
-        h->offs[numseq] = (int)T;
-        h->T = (int)T;
-        h->sumL = T;
-        if (h->check_rows("ka_cmp_create", ref_rows, row_stride, alnlen)) return KA_FAIL;
+        if (ka_ctx_device_stream(ctx, &h->device, &h->stream)) return fail("ka_cmp_create: bad context");
+        HIPCHK(hipSetDevice(h->device));
+        const std::string why = "the position maps hold at most " + std::to_string(KA_CMP_MAX_RES);
+        if (h->q.init("ka_cmp_create", numseq, lens, KA_CMP_MAX_RES, why.c_str())) return KA_FAIL;
+        if (ka_msa_check_rows("ka_cmp_create", h->q, ref_rows, row_stride, alnlen)) return KA_FAIL;
         h->WR = alnlen;
         h->WRp = ka_cmp_pad(alnlen);
         if ((size_t)h->WRp * 2 * sizeof(int16_t) > KA_CMP_MAX_LDS - 1024)
                 return fail("ka_cmp_create: reference width " + std::to_string(alnlen) + " exceeds the LDS of one CU (a row of each alignment is staged)");
-        if (ka_ctx_device_stream(ctx, &h->device, &h->stream)) return fail("ka_cmp_create: bad context");
-        HIPCHK(hipSetDevice(h->device));
+        const int T = h->q.T;
         for (auto& e : h->ev) HIPCHK(hipEventCreate(&e));
-        std::vector<int> seqOf((size_t)std::max(T, 1LL), 0);
-        for (int s = 0; s < numseq; s++) std::fill_n(seqOf.begin() + h->offs[s], lens[s], s);
-        if (h->dOffs.alloc(numseq + 1) || h->dLens.alloc(numseq) || h->dSeqOf.alloc(seqOf.size()) || h->dColR.alloc((size_t)std::max(T, 1LL)) ||
+        std::vector<int> seqOf((size_t)std::max(T, 1), 0);
+        for (int s = 0; s < numseq; s++) std::fill_n(seqOf.begin() + h->q.offs[s], lens[s], s);
+        if (h->dSeqOf.alloc(seqOf.size()) || h->dColR.alloc((size_t)std::max(T, 1)) ||
             h->dResR.alloc((size_t)numseq * h->WRp) || h->dColCnt.alloc(alnlen) || h->dScored.alloc(alnlen) || h->dRows.alloc((size_t)numseq * alnlen))
                 return fail("ka_cmp_create: out of device memory");
-        HIPCHK(hipMemcpyAsync(h->dOffs.p, h->offs.data(), sizeof(int) * (numseq + 1), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->dLens.p, lens, sizeof(int) * numseq, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(h->dSeqOf.p, seqOf.data(), sizeof(int) * seqOf.size(), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpy2DAsync(h->dRows.p, alnlen, ref_rows, row_stride, alnlen, numseq, hipMemcpyHostToDevice, h->stream));
+        if (ka_msa_upload_rows(h->q, h->dRows.p, ref_rows, row_stride, alnlen, h->stream)) return KA_FAIL;
         HIPCHK(hipEventRecord(h->ev[0], h->stream));
-        ka_cmp_launch_maps(h->dRows.p, alnlen, h->WRp, numseq, h->dOffs.p, h->dLens.p, h->dColR.p, h->dResR.p, h->stream);
+        ka_msa_launch_maps(h->dRows.p, alnlen, alnlen, h->WRp, h->q, h->dColR.p, h->dResR.p, h->stream);
         ka_cmp_launch_col_count(h->dResR.p, alnlen, h->WRp, numseq, h->dColCnt.p, h->stream);
         ka_cmp_launch_mask(h->dColCnt.p, alnlen, numseq, -1.0f, nullptr, h->dScored.p, h->stream);
         HIPCHK(hipGetLastError());
@@ -226,7 +194,7 @@ extern "C" int ka_cmp_set_mask(ka_cmp* h, float max_gap_frac, const int* mask, i
                 if (h->dMask.alloc(h->WR)) return fail("ka_cmp_set_mask: out of device memory");
                 HIPCHK(hipMemcpyAsync(h->dMask.p, mask, sizeof(int) * h->WR, hipMemcpyHostToDevice, h->stream));
         }
-        ka_cmp_launch_mask(h->dColCnt.p, h->WR, h->N, max_gap_frac, mask ? h->dMask.p : nullptr, h->dScored.p, h->stream);
+        ka_cmp_launch_mask(h->dColCnt.p, h->WR, h->q.N, max_gap_frac, mask ? h->dMask.p : nullptr, h->dScored.p, h->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->stream));
         return KA_OK;
@@ -238,7 +206,7 @@ extern "C" int ka_cmp_score_batch(ka_cmp* h, int n_tests, const uint8_t* const* 
         if (!h || n_tests < 0 || (n_tests > 0 && (!test_rows || !row_strides || !alnlens))) return fail("ka_cmp_score_batch: bad arguments");
         for (int k = 0; k < n_tests; k++) {
                 const std::string who = "ka_cmp_score: test " + std::to_string(k);
-                if (h->check_rows(who.c_str(), test_rows[k], row_strides[k], alnlens[k])) return KA_FAIL;
+                if (ka_msa_check_rows(who.c_str(), h->q, test_rows[k], row_strides[k], alnlens[k])) return KA_FAIL;
         }
         HIPCHK(hipSetDevice(h->device));
         h->st[1] = h->st[2] = h->st[3] = 0.0;

@@ -48,7 +48,6 @@ struct KaCmpArgs {
 };
 
 // ka_cmp.hip
-void ka_cmp_launch_maps(const uint8_t* rows, int W, int Wp, int N, const int* offs, const int* lens, int* col, int16_t* res, hipStream_t s);
 void ka_cmp_launch_col_count(const int16_t* res, int W, int Wp, int N, int* colCnt, hipStream_t s);
 void ka_cmp_launch_mask(const int* colCnt, int W, int N, float maxGapFrac, const int* mask, uint8_t* scored, hipStream_t s);
 int ka_cmp_launch_walk(const KaCmpArgs& a, int K, int gridX, size_t lds, hipStream_t s);

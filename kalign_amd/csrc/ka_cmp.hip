@@ -7,7 +7,6 @@
 //     pR = resR[j][colR[i][ri]]   and   pT = resT[j][colT[i][ri]]
 // (ka_cmp.h lists them).  All are exact integer counts, so the device reproduces the reference bit for bit.
 //
-//   cmp_maps       a wave per row: the two position maps, the residue rank of a column from a ballot prefix
 //   cmp_col_count  a wave per reference column: its residues (the column mask's gap fraction, TC's "two residues")
 //   cmp_mask       the column mask: the reference's float rule on the gap fraction, or the caller's array
 //   cmp_walk       the pair walk: a workgroup takes tiles of KA_CMP_TI sequences i x TJ sequences j; the tile's res rows
@@ -15,48 +14,15 @@
 //                  and scored bit in registers) and gathers its partners in every j from LDS
 //   cmp_reduce     the workgroups' slabs summed per test
 //   cmp_tc         a wave per scored reference column with two residues or more: do they all sit in one test column?
+// The position maps themselves are built by ka_msa.hip, the res rows padded to ka_cmp_pad entries.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <algorithm>
 #include "ka_cmp.h"
+#include "ka_msa.h"
 
 #define CMP_THREADS 256
 #define CMP_WAVES (CMP_THREADS / 64)
-
-__device__ __forceinline__ long long cmp_wave_sum(long long v)
-{
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        return v;
-}
-
-// a residue is an ASCII letter (isalpha in the C locale); every other byte is a gap
-__device__ __forceinline__ bool cmp_is_residue(unsigned b) { return (b | 32u) - 'a' < 26u; }
-
-// one wave per row: res[s][c] for every padded column (-1 at gaps and padding), col[offs[s] + r] for every residue.
-// The host has checked every row's letter count against lens[s]; the rank guard keeps the writes in place regardless.
-__global__ __launch_bounds__(CMP_THREADS) void cmp_maps(const uint8_t* rows, int W, int Wp, int N, const int* offs, const int* lens,
-                                                        int* col, int16_t* res)
-{
-        const int s = blockIdx.x * CMP_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-        if (s >= N) return;
-        const uint8_t* row = rows + (long long)s * W;
-        int16_t* rs = res + (long long)s * Wp;
-        int* cs = col + offs[s];
-        const int len = lens[s];
-        const unsigned long long below = (1ull << lane) - 1ull;
-        int run = 0;
-        for (int cb = 0; cb < Wp; cb += 64) {
-                const int c = cb + lane;
-                const bool isr = c < W && cmp_is_residue(row[c]);
-                const unsigned long long m = __ballot(isr);
-                const int r = run + __popcll(m & below);
-                const bool put = isr && r < len;
-                if (c < Wp) rs[c] = put ? (int16_t)r : (int16_t)-1;
-                if (put) cs[r] = c;
-                run += __popcll(m);
-        }
-}
 
 __global__ __launch_bounds__(CMP_THREADS) void cmp_col_count(const int16_t* res, int W, int Wp, int N, int* colCnt)
 {
@@ -64,7 +30,7 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_col_count(const int16_t* res,
         for (int c = blockIdx.x * CMP_WAVES + (threadIdx.x >> 6); c < W; c += gridDim.x * CMP_WAVES) {
                 long long n = 0;
                 for (int s = lane; s < N; s += 64) n += res[(long long)s * Wp + c] >= 0;
-                n = cmp_wave_sum(n);
+                n = ka_msa_wave_sum(n);
                 if (lane == 0) colCnt[c] = (int)n;
         }
 }
@@ -136,7 +102,7 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_walk(KaCmpArgs a)
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
         for (int q = 0; q < KA_CMP_WALK; q++) {
-                const long long t = cmp_wave_sum(acc[q]);
+                const long long t = ka_msa_wave_sum(acc[q]);
                 if (lane == 0) wsum[wave][q] = t;
         }
         __syncthreads();
@@ -158,7 +124,7 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_reduce(const long long* slab,
                 for (int q = 0; q < KA_CMP_WALK; q++) acc[q] += slab[((long long)k * gridX + g) * KA_CMP_WALK + q];
 #pragma unroll
         for (int q = 0; q < KA_CMP_WALK; q++) {
-                const long long t = cmp_wave_sum(acc[q]);
+                const long long t = ka_msa_wave_sum(acc[q]);
                 if (lane == 0) wsum[wave][q] = t;
         }
         __syncthreads();
@@ -199,11 +165,6 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_tc(KaCmpArgs a)
                 atomicAdd(&a.tc[2 * k], correct);
                 atomicAdd(&a.tc[2 * k + 1], total);
         }
-}
-
-void ka_cmp_launch_maps(const uint8_t* rows, int W, int Wp, int N, const int* offs, const int* lens, int* col, int16_t* res, hipStream_t s)
-{
-        cmp_maps<<<(N + CMP_WAVES - 1) / CMP_WAVES, CMP_THREADS, 0, s>>>(rows, W, Wp, N, offs, lens, col, res);
 }
 
 void ka_cmp_launch_col_count(const int16_t* res, int W, int Wp, int N, int* colCnt, hipStream_t s)

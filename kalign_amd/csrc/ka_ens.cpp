@@ -18,6 +18,7 @@
 // back edges (topo_sort, consensus_msa.c:255-370) and filled with the caller's letters.
 #include "ka_ctx.h"
 #include "ka_ens.h"
+#include "ka_msa.h"
 
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
 
@@ -39,7 +40,7 @@ struct Uf {
         void init(const std::vector<int>& o, const std::vector<int>& l, int T)
         {
                 offs = &o; lens = &l;
-                const int N = (int)o.size();
+                const int N = (int)l.size();
                 mw = (N + 63) / 64;
                 parent.resize(T); rnk.assign(T, 0); elemSeq.resize(T); head.resize(T); next.assign(T, -1); tail.resize(T);
                 maskOf.assign(T, -1); visited.assign(T, 0);
@@ -135,7 +136,7 @@ struct Uf {
 std::vector<int> topo_order(const std::vector<int>& colId, const std::vector<int>& offs, const std::vector<int>& lens, int nCols)
 {
         std::vector<std::vector<int>> adj(nCols);
-        for (size_t s = 0; s < offs.size(); s++)
+        for (size_t s = 0; s < lens.size(); s++)
                 for (int p = 0; p + 1 < lens[s]; p++) {
                         const int ca = colId[offs[s] + p], cb = colId[offs[s] + p + 1];
                         if (ca == cb) continue;
@@ -169,8 +170,6 @@ std::vector<int> topo_order(const std::vector<int>& colId, const std::vector<int
         return out;
 }
 
-inline bool is_residue(uint8_t b) { return (unsigned)((b | 32u) - 'a') < 26u; }
-
 double ms_since(std::chrono::steady_clock::time_point t0)
 {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -181,10 +180,11 @@ double ms_since(std::chrono::steady_clock::time_point t0)
 struct ka_ens {
         int device = 0;
         hipStream_t stream = nullptr;
-        int N = 0, R = 0, T = 0, maxlen = 0;
-        std::vector<int> lens, offs, W;
+        KaSeqSet q;
+        int R = 0;
+        std::vector<int> W;
         std::vector<DevBuf<uint8_t>> rows;            // member k's rows, N x W[k]
-        DevBuf<int> dOffs, dLens, dCol, dColX, dCnt, dSup, dNp;
+        DevBuf<int> dCol, dColX, dCnt, dSup, dNp;
         DevBuf<int16_t> dRes, dResX;
         DevBuf<uint8_t> dRowsX;
         DevBuf<long long> dPairOff, dRowTot, dRowBase[2];
@@ -218,48 +218,27 @@ struct ka_ens {
                 if (ev0) (void)hipEventDestroy(ev0);
                 if (ev1) (void)hipEventDestroy(ev1);
                 for (auto& r : rows) r.release();
-                dOffs.release(); dLens.release(); dCol.release(); dColX.release(); dCnt.release(); dSup.release(); dNp.release();
+                q.release();
+                dCol.release(); dColX.release(); dCnt.release(); dSup.release(); dNp.release();
                 dRes.release(); dResX.release(); dRowsX.release(); dPairOff.release(); dRowTot.release(); dScore.release();
                 dConf.release(); dColConf.release();
         }
 
         float evMs() { float m = 0.0f; (void)hipEventElapsedTime(&m, ev0, ev1); return m; }
 
-        // rows of an alignment: every row's letter count must be its sequence's length
-        int check_rows(const char* who, const uint8_t* r, long long stride, int alnlen)
-        {
-                if (!r) return fail(std::string(who) + ": no rows");
-                if (alnlen <= 0 || stride < alnlen)
-                        return fail(std::string(who) + ": alignment width " + std::to_string(alnlen) + " does not fit row stride " + std::to_string(stride));
-                for (int s = 0; s < N; s++) {
-                        const uint8_t* row = r + (long long)s * stride;
-                        int n = 0;
-                        for (int c = 0; c < alnlen; c++) n += is_residue(row[c]);
-                        if (n != lens[s])
-                                return fail(std::string(who) + ": row " + std::to_string(s) + " holds " + std::to_string(n) + " letters, sequence has " + std::to_string(lens[s]));
-                }
-                return KA_OK;
-        }
-
-        int upload_rows(DevBuf<uint8_t>& d, const uint8_t* r, long long stride, int alnlen)
-        {
-                if (d.alloc((size_t)N * alnlen)) return fail("ka_ens: out of device memory (rows)");
-                HIPCHK(hipMemcpy2DAsync(d.p, alnlen, r, stride, alnlen, N, hipMemcpyHostToDevice, stream));
-                return KA_OK;
-        }
-
         int ensure_maps()
         {
                 if (mapsFresh) return KA_OK;
                 for (int k = 0; k < R; k++)
                         if (W[k] <= 0) return fail("ka_ens: member " + std::to_string(k) + " not added (all n_runs members are needed)");
+                const int N = q.N, T = q.T;
                 long long resTot = 0;
                 for (int k = 0; k < R; k++) resTot += (long long)N * W[k];
                 if (dCol.alloc((size_t)R * T) || dRes.alloc((size_t)resTot)) return fail("ka_ens: out of device memory (maps)");
                 HIPCHK(hipEventRecord(ev0, stream));
                 long long o = 0;
                 for (int k = 0; k < R; k++) {
-                        ka_ens_launch_maps(rows[k].p, W[k], W[k], N, dOffs.p, dLens.p, dCol.p + (long long)k * T, dRes.p + o, stream);
+                        ka_msa_launch_maps(rows[k].p, W[k], W[k], W[k], q, dCol.p + (long long)k * T, dRes.p + o, stream);
                         o += (long long)N * W[k];
                 }
                 HIPCHK(hipGetLastError());
@@ -273,22 +252,23 @@ struct ka_ens {
         KaEnsArgs args()
         {
                 KaEnsArgs a{};
-                a.offs = dOffs.p; a.lens = dLens.p; a.N = N; a.R = R; a.T = T; a.maxlen = maxlen;
+                a.offs = q.dOffs; a.lens = q.dLens; a.N = q.N; a.R = R; a.T = q.T; a.maxlen = q.maxlen;
                 a.col = dCol.p; a.res = dRes.p;
                 long long o = 0;
-                for (int k = 0; k < R; k++) { a.resOff[k] = o; a.W[k] = W[k]; o += (long long)N * W[k]; }
-                a.i0 = 0; a.i1 = N;
+                for (int k = 0; k < R; k++) { a.resOff[k] = o; a.W[k] = W[k]; o += (long long)q.N * W[k]; }
+                a.i0 = 0; a.i1 = q.N;
                 // the member columns of sequence i in LDS when they fit next to the three per-residue arrays (64 KiB)
-                a.colInLds = (long long)(3 + R) * maxlen * 4 <= 65536;
+                a.colInLds = (long long)(3 + R) * q.maxlen * 4 <= 65536;
                 return a;
         }
 
         // an alignment X's maps in dColX / dResX
         int maps_x(const uint8_t* r, long long stride, int alnlen, KaEnsArgs& a)
         {
-                if (upload_rows(dRowsX, r, stride, alnlen)) return KA_FAIL;
-                if (dColX.alloc((size_t)std::max(T, 1)) || dResX.alloc((size_t)N * alnlen)) return fail("ka_ens: out of device memory");
-                ka_ens_launch_maps(dRowsX.p, alnlen, alnlen, N, dOffs.p, dLens.p, dColX.p, dResX.p, stream);
+                if (dRowsX.alloc((size_t)q.N * alnlen) || dColX.alloc((size_t)std::max(q.T, 1)) || dResX.alloc((size_t)q.N * alnlen))
+                        return fail("ka_ens: out of device memory");
+                if (ka_msa_upload_rows(q, dRowsX.p, r, stride, alnlen, stream)) return KA_FAIL;
+                ka_msa_launch_maps(dRowsX.p, alnlen, alnlen, alnlen, q, dColX.p, dResX.p, stream);
                 a.colX = dColX.p; a.resX = dResX.p; a.Wx = alnlen;
                 return KA_OK;
         }
@@ -299,6 +279,9 @@ struct ka_ens {
 int ka_ens::consensus(int minSup, const uint8_t* letters)
 {
         using clk = std::chrono::steady_clock;
+        const int N = q.N, T = q.T;
+        const std::vector<int>& lens = q.lens;
+        const std::vector<int>& offs = q.offs;
         st[2] = st[3] = st[4] = st[5] = st[7] = st[8] = st[9] = 0.0;
         std::fill_n(levelCount, KA_ENS_MAX_RUNS + 1, 0LL);
         std::fill_n(levelMs, KA_ENS_MAX_RUNS + 1, 0.0);
@@ -416,29 +399,17 @@ extern "C" int ka_ens_create(ka_ctx* ctx, int numseq, const int* lens, int n_run
                 return fail("ka_ens_create: n_runs " + std::to_string(n_runs) + " outside 1.." + std::to_string(KA_ENS_MAX_RUNS) + " (one bit per member in the reference's POAR table)");
         *out = nullptr;
         std::unique_ptr<ka_ens> e(new ka_ens);
-        e->N = numseq; e->R = n_runs;
-        e->lens.assign(lens, lens + numseq);
-        e->offs.resize(numseq);
-        long long T = 0;
-        for (int s = 0; s < numseq; s++) {
-                if (lens[s] < 0) return fail("ka_ens_create: negative sequence length");
-                if (lens[s] > KA_ENS_MAX_RES)
-                        return fail("ka_ens_create: sequence " + std::to_string(s) + " has " + std::to_string(lens[s]) +
-                                    " residues; residue indices must stay below 4096 (the reference's POAR key ri << 20 | rj aliases beyond)");
-                e->offs[s] = (int)T;
-                T += lens[s];
-                e->maxlen = std::max(e->maxlen, lens[s]);
-        }
-        e->T = (int)T;
+        e->R = n_runs;
         e->W.assign(n_runs, 0);
         e->rows.resize(n_runs);
         if (ka_ctx_device_stream(ctx, &e->device, &e->stream)) return fail("ka_ens_create: bad context");
         HIPCHK(hipSetDevice(e->device));
+        if (e->q.init("ka_ens_create", numseq, lens, KA_ENS_MAX_RES,
+                      "residue indices must stay below 4096 (the reference's POAR key ri << 20 | rj aliases beyond)"))
+                return KA_FAIL;
         const char* cc = std::getenv("KA_ENS_CHUNK");                    // candidates per chunk (tests force many chunks)
         e->chunkCap = cc && std::atoll(cc) > 0 ? std::atoll(cc) : (1ll << 22);
-        if (e->dOffs.alloc(numseq) || e->dLens.alloc(numseq) || e->dScore.alloc(1)) return fail("ka_ens_create: out of device memory");
-        HIPCHK(hipMemcpy(e->dOffs.p, e->offs.data(), sizeof(int) * numseq, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->dLens.p, lens, sizeof(int) * numseq, hipMemcpyHostToDevice));
+        if (e->dScore.alloc(1)) return fail("ka_ens_create: out of device memory");
         for (int b = 0; b < 2; b++) {
                 HIPCHK(hipEventCreateWithFlags(&e->ready[b], hipEventDisableTiming));
                 HIPCHK(hipEventCreate(&e->wBeg[b]));
@@ -461,9 +432,10 @@ extern "C" void ka_ens_destroy(ka_ens* e)
 extern "C" int ka_ens_add_member(ka_ens* e, int k, const uint8_t* rows, long long row_stride, int alnlen)
 {
         if (!e || k < 0 || k >= e->R) return fail("ka_ens_add_member: bad arguments");
-        if (e->check_rows("ka_ens_add_member", rows, row_stride, alnlen)) return KA_FAIL;
+        if (ka_msa_check_rows("ka_ens_add_member", e->q, rows, row_stride, alnlen)) return KA_FAIL;
         HIPCHK(hipSetDevice(e->device));
-        if (e->upload_rows(e->rows[k], rows, row_stride, alnlen)) return KA_FAIL;
+        if (e->rows[k].alloc((size_t)e->q.N * alnlen)) return fail("ka_ens_add_member: out of device memory");
+        if (ka_msa_upload_rows(e->q, e->rows[k].p, rows, row_stride, alnlen, e->stream)) return KA_FAIL;
         HIPCHK(hipStreamSynchronize(e->stream));
         e->W[k] = alnlen;
         e->mapsFresh = false;
@@ -474,7 +446,7 @@ extern "C" int ka_ens_add_member(ka_ens* e, int k, const uint8_t* rows, long lon
 extern "C" int ka_ens_score_rows(ka_ens* e, const uint8_t* rows, long long row_stride, int alnlen, long long* sum_out, double* score_out)
 {
         if (!e) return fail("ka_ens_score_rows: bad arguments");
-        if (e->check_rows("ka_ens_score_rows", rows, row_stride, alnlen)) return KA_FAIL;
+        if (ka_msa_check_rows("ka_ens_score_rows", e->q, rows, row_stride, alnlen)) return KA_FAIL;
         HIPCHK(hipSetDevice(e->device));
         if (e->ensure_maps()) return KA_FAIL;
         KaEnsArgs a = e->args();
@@ -500,11 +472,11 @@ extern "C" int ka_ens_consensus(ka_ens* e, int min_support, const uint8_t* lette
         if (!e || !letters || min_support < 1) return fail("ka_ens_consensus: bad arguments (min_support >= 1, letters)");
         HIPCHK(hipSetDevice(e->device));
         const bool cached = e->cacheGen == e->generation && e->cacheMin == min_support &&
-                            std::equal(e->cacheLetters.begin(), e->cacheLetters.end(), letters) && (int)e->cacheLetters.size() == e->T;
+                            std::equal(e->cacheLetters.begin(), e->cacheLetters.end(), letters) && (int)e->cacheLetters.size() == e->q.T;
         if (!cached && e->consensus(min_support, letters)) return KA_FAIL;
         if (alnlen_out) *alnlen_out = e->cacheW;
         if (!rows_out || row_stride < e->cacheW) return KA_ERR_ROWS_STRIDE;
-        for (int s = 0; s < e->N; s++)
+        for (int s = 0; s < e->q.N; s++)
                 std::memcpy(rows_out + (long long)s * row_stride, e->cacheRows.data() + (size_t)s * e->cacheW, e->cacheW);
         return KA_OK;
 }
@@ -512,23 +484,23 @@ extern "C" int ka_ens_consensus(ka_ens* e, int min_support, const uint8_t* lette
 extern "C" int ka_ens_confidence(ka_ens* e, const uint8_t* rows, long long row_stride, int alnlen, float* res_conf_out, float* col_conf_out)
 {
         if (!e || !res_conf_out || !col_conf_out) return fail("ka_ens_confidence: bad arguments");
-        if (e->check_rows("ka_ens_confidence", rows, row_stride, alnlen)) return KA_FAIL;
+        if (ka_msa_check_rows("ka_ens_confidence", e->q, rows, row_stride, alnlen)) return KA_FAIL;
         HIPCHK(hipSetDevice(e->device));
         if (e->ensure_maps()) return KA_FAIL;
         KaEnsArgs a = e->args();
         HIPCHK(hipEventRecord(e->ev0, e->stream));
         if (e->maps_x(rows, row_stride, alnlen, a)) return KA_FAIL;
-        if (e->dSup.alloc((size_t)std::max(e->T, 1)) || e->dNp.alloc((size_t)std::max(e->T, 1)) ||
-            e->dConf.alloc((size_t)e->N * alnlen) || e->dColConf.alloc((size_t)alnlen))
+        if (e->dSup.alloc((size_t)std::max(e->q.T, 1)) || e->dNp.alloc((size_t)std::max(e->q.T, 1)) ||
+            e->dConf.alloc((size_t)e->q.N * alnlen) || e->dColConf.alloc((size_t)alnlen))
                 return fail("ka_ens_confidence: out of device memory");
-        HIPCHK(hipMemsetAsync(e->dSup.p, 0, sizeof(int) * (size_t)std::max(e->T, 1), e->stream));
-        HIPCHK(hipMemsetAsync(e->dNp.p, 0, sizeof(int) * (size_t)std::max(e->T, 1), e->stream));
+        HIPCHK(hipMemsetAsync(e->dSup.p, 0, sizeof(int) * (size_t)std::max(e->q.T, 1), e->stream));
+        HIPCHK(hipMemsetAsync(e->dNp.p, 0, sizeof(int) * (size_t)std::max(e->q.T, 1), e->stream));
         a.supSum = e->dSup.p; a.nPair = e->dNp.p;
         ka_ens_launch_walk(KA_ENS_CONF, a, e->stream);
         ka_ens_launch_conf(a, e->dConf.p, e->dColConf.p, e->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(e->ev1, e->stream));
-        HIPCHK(hipMemcpyAsync(res_conf_out, e->dConf.p, sizeof(float) * (size_t)e->N * alnlen, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(res_conf_out, e->dConf.p, sizeof(float) * (size_t)e->q.N * alnlen, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipMemcpyAsync(col_conf_out, e->dColConf.p, sizeof(float) * (size_t)alnlen, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
         e->st[6] = e->evMs();

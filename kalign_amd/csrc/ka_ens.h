@@ -11,7 +11,7 @@
 enum { KA_ENS_SCORE = 0, KA_ENS_CONF = 1, KA_ENS_COUNT = 2, KA_ENS_WRITE = 3 };
 
 struct KaEnsArgs {
-        const int* offs;           // [N] first residue of sequence s in the flat residue numbering
+        const int* offs;           // [N + 1] first residue of sequence s in the flat residue numbering
         const int* lens;           // [N]
         int N, R, T, maxlen;       // sequences, members, residues, longest sequence
         const int* col;            // [R][T]  col[k * T + offs[s] + r] = column of residue r of s in member k
@@ -35,7 +35,6 @@ struct KaEnsArgs {
 };
 
 // ka_ens.hip
-void ka_ens_launch_maps(const uint8_t* rows, int stride, int W, int N, const int* offs, const int* lens, int* col, int16_t* res, hipStream_t s);
 void ka_ens_launch_walk(int mode, const KaEnsArgs& a, hipStream_t s);
 void ka_ens_launch_row_scan(const int* cnt, int N, long long* pairOff, long long* rowTot, int rows, hipStream_t s);
 void ka_ens_launch_conf(const KaEnsArgs& a, float* conf, float* colConf, hipStream_t s);

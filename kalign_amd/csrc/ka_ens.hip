@@ -16,15 +16,9 @@
 // lookups, which stay in L1/L2.
 #include <hip/hip_runtime.h>
 #include "ka_ens.h"
+#include "ka_msa.h"
 
 #define ENS_THREADS 256
-
-__device__ __forceinline__ long long ens_wave_sum(long long v)
-{
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        return v;
-}
 
 __device__ __forceinline__ int ens_wave_incl_scan(int v, int lane)
 {
@@ -34,24 +28,6 @@ __device__ __forceinline__ int ens_wave_incl_scan(int v, int lane)
                 if (lane >= o) v += t;
         }
         return v;
-}
-
-// one thread per row: column of every residue, residue of every column (pos_matrix_from_msa, poar.c:143-174: a
-// residue is an ASCII letter, isalpha in the C locale).  The host has checked the letter counts against lens[].
-__global__ void ens_maps(const uint8_t* rows, int stride, int W, int N, const int* offs, const int* lens, int* col, int16_t* res)
-{
-        const int s = blockIdx.x * blockDim.x + threadIdx.x;
-        if (s >= N) return;
-        const uint8_t* row = rows + (long long)s * stride;
-        int16_t* rs = res + (long long)s * W;
-        int* cs = col + offs[s];
-        const int len = lens[s];
-        int r = 0;
-        for (int c = 0; c < W; c++) {
-                const unsigned b = row[c];
-                if ((unsigned)((b | 32u) - 'a') < 26u && r < len) { cs[r] = c; rs[c] = (int16_t)r; r++; }
-                else rs[c] = -1;
-        }
 }
 
 template <int MODE, int RM>
@@ -143,12 +119,12 @@ __global__ __launch_bounds__(ENS_THREADS) void ens_walk(KaEnsArgs a)
                         }
                 }
                 if (MODE == KA_ENS_COUNT) {
-                        const long long t = ens_wave_sum(cntj);
+                        const long long t = ka_msa_wave_sum(cntj);
                         if (lane == 0) a.cnt[(long long)(i - a.i0) * a.N + j] = (int)t;
                 }
         }
         if (MODE == KA_ENS_SCORE) {
-                const long long t = ens_wave_sum(acc);
+                const long long t = ka_msa_wave_sum(acc);
                 if (lane == 0 && t) atomicAdd(a.score, (unsigned long long)t);
         }
         if (MODE == KA_ENS_CONF) {
@@ -209,11 +185,6 @@ __global__ void ens_conf_col(KaEnsArgs a, const float* conf, float* colConf)
         for (int s = 0; s < a.N; s++)
                 if (a.resX[(long long)s * a.Wx + c] >= 0) { sum += conf[(long long)s * a.Wx + c]; count++; }
         colConf[c] = count > 0 ? (float)(sum / count) : 0.0f;
-}
-
-void ka_ens_launch_maps(const uint8_t* rows, int stride, int W, int N, const int* offs, const int* lens, int* col, int16_t* res, hipStream_t s)
-{
-        ens_maps<<<(N + 63) / 64, 64, 0, s>>>(rows, stride, W, N, offs, lens, col, res);
 }
 
 template <int MODE>

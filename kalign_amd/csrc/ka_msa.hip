@@ -1,0 +1,90 @@
+// ka_msa.hip -- rows of a finished alignment -> position maps (ka_msa.h): the sequence set, the host's row check, the
+// upload and the one kernel that turns uploaded rows into col[] and res[].
+#include "ka_ctx.h"
+#include "ka_msa.h"
+
+#define MSA_THREADS 256
+#define MSA_WAVES (MSA_THREADS / 64)
+
+// one wave per row: res[s][c] for every column of the res row (-1 at gaps and padding), col[offs[s] + r] for every
+// residue, the residue rank of a column from a ballot prefix.  The host has checked every row's letter count against
+// lens[s]; the rank guard keeps the writes in place regardless.
+__global__ __launch_bounds__(MSA_THREADS) void msa_maps(const uint8_t* rows, int rowStride, int W, int resStride, int N, const int* offs,
+                                                        const int* lens, int* col, int16_t* res)
+{
+        const int s = blockIdx.x * MSA_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+        if (s >= N) return;
+        const uint8_t* row = rows + (long long)s * rowStride;
+        int16_t* rs = res + (long long)s * resStride;
+        int* cs = col + offs[s];
+        const int len = lens[s];
+        const unsigned long long below = (1ull << lane) - 1ull;
+        int run = 0;
+        for (int cb = 0; cb < resStride; cb += 64) {
+                const int c = cb + lane;
+                const bool isr = c < W && ka_msa_is_residue(row[c]);
+                const unsigned long long m = __ballot(isr);
+                const int r = run + __popcll(m & below);
+                const bool put = isr && r < len;
+                if (c < resStride) rs[c] = put ? (int16_t)r : (int16_t)-1;
+                if (put) cs[r] = c;
+                run += __popcll(m);
+        }
+}
+
+void ka_msa_launch_maps(const uint8_t* rows, int rowStride, int W, int resStride, const KaSeqSet& q, int* col, int16_t* res, hipStream_t s)
+{
+        msa_maps<<<(q.N + MSA_WAVES - 1) / MSA_WAVES, MSA_THREADS, 0, s>>>(rows, rowStride, W, resStride, q.N, q.dOffs, q.dLens, col, res);
+}
+
+int KaSeqSet::init(const char* who, int numseq, const int* l, int max_res, const char* why)
+{
+        const std::string w(who);
+        N = numseq;
+        lens.assign(l, l + numseq);
+        offs.resize(numseq + 1);
+        long long t = 0;
+        for (int s = 0; s < numseq; s++) {
+                if (l[s] < 0) return fail(w + ": negative sequence length");
+                if (l[s] > max_res) return fail(w + ": sequence " + std::to_string(s) + " has " + std::to_string(l[s]) + " residues; " + why);
+                offs[s] = (int)t;
+                t += l[s];
+                maxlen = std::max(maxlen, l[s]);
+                if (t > INT32_MAX) return fail(w + ": more than 2^31 - 1 residues");
+        }
+        offs[numseq] = T = (int)t;
+        if (hipMalloc((void**)&dOffs, sizeof(int) * (numseq + 1)) != hipSuccess || hipMalloc((void**)&dLens, sizeof(int) * numseq) != hipSuccess)
+                return fail(w + ": out of device memory");
+        HIPCHK(hipMemcpy(dOffs, offs.data(), sizeof(int) * (numseq + 1), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dLens, lens.data(), sizeof(int) * numseq, hipMemcpyHostToDevice));
+        return KA_OK;
+}
+
+void KaSeqSet::release()
+{
+        if (dOffs) (void)hipFree(dOffs);
+        if (dLens) (void)hipFree(dLens);
+        dOffs = dLens = nullptr;
+}
+
+int ka_msa_check_rows(const char* who, const KaSeqSet& q, const uint8_t* rows, long long stride, int alnlen)
+{
+        if (!rows) return fail(std::string(who) + ": no rows");
+        if (alnlen <= 0 || stride < alnlen)
+                return fail(std::string(who) + ": alignment width " + std::to_string(alnlen) + " does not fit row stride " + std::to_string(stride));
+        for (int s = 0; s < q.N; s++) {
+                const uint8_t* row = rows + (long long)s * stride;
+                int n = 0;
+                for (int c = 0; c < alnlen; c++) n += ka_msa_is_residue(row[c]);
+                if (n != q.lens[s])
+                        return fail(std::string(who) + ": row " + std::to_string(s) + " holds " + std::to_string(n) + " letters, its sequence " +
+                                    std::to_string(q.lens[s]) + " (every alignment must hold the same sequences)");
+        }
+        return KA_OK;
+}
+
+int ka_msa_upload_rows(const KaSeqSet& q, uint8_t* dst, const uint8_t* rows, long long stride, int alnlen, hipStream_t s)
+{
+        HIPCHK(hipMemcpy2DAsync(dst, alnlen, rows, stride, alnlen, q.N, hipMemcpyHostToDevice, s));
+        return KA_OK;
+}

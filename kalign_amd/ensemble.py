@@ -2,9 +2,7 @@
 
 finish_ensemble takes the members' rows (dist.ensemble_members returns them) and does what the reference does with them:
 scores every member, picks one, tries the consensus alignment, refines the winner, and computes confidences."""
-import numpy as np
-
-from .api import KalignAmdError
+from .api import KalignAmdError, residue_lens
 
 
 def auto_min_support(n_runs):
@@ -35,7 +33,7 @@ def finish_ensemble(ctx, member_rows, letters, min_support=0, rerun_refined=None
     if n_runs < 1:
         raise KalignAmdError("an ensemble needs members")
     letters = [x.encode() if isinstance(x, str) else bytes(x) for x in letters]
-    lens = np.array([sum(1 for b in s if chr(b).isascii() and chr(b).isalpha()) for s in letters], np.int32)
+    lens = residue_lens(letters)
     ens = ctx.ensemble(lens, n_runs)
     try:
         for k, rows in enumerate(member_rows):

@@ -117,12 +117,32 @@ def test_consensus_in_many_chunks(ctx, monkeypatch):
     e.close()
 
 
-@pytest.mark.parametrize("seed,n,length,runs", [(11, 64, 80, 8), (12, 128, 60, 5), (13, 40, 100, 16)])
+def _check_letter_case_and_gap_byte(ctx, seqs, members):
+    """lower-case letters and '.' gaps are the same residues and gaps: equal scores, confidences and consensus columns"""
+    other = [[r.lower().replace("-", ".") for r in m] for m in members]
+    a, b = _ens(ctx, seqs, members), _ens(ctx, seqs, other)
+    for rows, orows in zip(members, other):
+        assert a.score(rows) == b.score(orows) == a.score(orows)
+    ra, ca = a.confidence(members[0])
+    rb, cb = b.confidence(other[0])
+    assert np.array_equal(ra, rb) and np.array_equal(ca, cb)
+    assert a.consensus(seqs, 2) == b.consensus(seqs, 2)
+    a.close()
+    b.close()
+
+
+# alignment widths by seed: the last block of 64 columns partly filled (11, 12, 13) and full (14)
+LIVE_WIDTH = {11: 100, 12: 77, 13: 125, 14: 128}
+
+
+@pytest.mark.parametrize("seed,n,length,runs", [(11, 64, 80, 8), (12, 128, 60, 5), (13, 40, 100, 16), (14, 48, 101, 6)])
 def test_stage_live_against_the_reference(ctx, seed, n, length, runs):
     import make_golden_ensemble as mg
     if not mg.available():
         pytest.skip("oracle/_ref not built")
     seqs, members = mg.synthetic(n, length, runs, seed, moves=10)
+    assert len(members[0][0]) == LIVE_WIDTH[seed]
+    _check_letter_case_and_gap_byte(ctx, seqs, members)
     mins = sorted({1, 2, ensemble_auto(runs), runs})
     want = mg.reference_stage(seqs, members, mins)
     _check_stage(ctx, want, seqs, members)

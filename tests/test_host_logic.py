@@ -163,3 +163,14 @@ def test_bench_plain_run_leaves_every_leg_to_full():
     assert (bench.parse_args(["--full", "--no-cpu"]).no_legs, bench.parse_args(["--full", "--no-cpu"]).no_cpu) == (False, True)
     quick = bench.parse_args(["--full", "--quick"])
     assert (quick.no_legs, quick.no_cpu) == (True, True)
+
+
+def test_residue_lens_is_the_per_byte_rule_on_every_byte_value():
+    """kalign_amd.api.residue_lens against the rule stated byte by byte: an ASCII letter is a residue, nothing else is"""
+    from kalign_amd.api import residue_lens
+    for b in range(256):
+        want = int(chr(b).isascii() and chr(b).isalpha())
+        assert residue_lens([bytes([b])])[0] == want == int(97 <= (b | 32) <= 122 and b < 128), b
+    every = bytes(range(256))
+    assert residue_lens([every, b"", "aC-.x", b"--"]).tolist() == [52, 0, 3, 0]
+    assert residue_lens([]).dtype == np.int32
