@@ -233,6 +233,25 @@ int ka_debug_trace(ka_ctx* ctx, int* out64);
 /* Launches of the throughput kernel (round 6: unit 10, ka_task_kernel_tp; opt-in, KA_TP=1 in the environment) since the library was
  * loaded -- tests assert that the path they mean to test is the one that ran. */
 long long ka_debug_tp_launches(void);
+/* Tests only: ONE level of the device 2-means bisection (ka_kmeans.hip), launched by the function the product's level loop
+ * calls, with everything it computed handed back candidate by candidate.  dm[numrows][32]: distances to the 32 anchors;
+ * samples[n_samples]: the level's sample buffer (row indices); sets_start_n[2 * n_sets]: the sets to split, (start, n)
+ * slices of it, n >= 2.  force_big != 0: the 512-thread shape whatever the sizes (the product takes it for every set of a
+ * level that holds one above 1024 samples).  Set k has tries_k = min(40, n_k) candidates (seed c * (n_k / tries_k)); with
+ * slot = sum of tries before k + c and B = sum of tries_j * n_j before k + c * n_k:
+ *   score[slot], counts[2 * slot + {0, 1}] = n_left, n_right; lists[2 * B ..]: n_k ints of the left list, then n_k of the
+ *   right one (valid up to their counts); mind[B ..]: n_k floats, min(dl, dr) of every sample in the candidate's last
+ *   iteration; wmean[32 * k ..]: the set's centroid; winner[k]: the candidate the acceptance rule picks;
+ *   *big_out (may be NULL): whether the 512-thread shape ran. */
+int ka_debug_kmeans_level(ka_ctx* ctx, const float* dm, int numrows, const int* samples, int n_samples,
+                          const int* sets_start_n, int n_sets, int force_big,
+                          float* score, int* counts, int* lists, float* mind, float* wmean, int* winner, int* big_out);
+/* Tests only, no GPU: the host's split2 (ka_guide.cpp) on the set samples[n] from the seed samples[seed_pick]:
+ * *score, counts[2], lists[2 * n] (left list at 0, right list at n), mind[n] and wmean[32] as above, counters[4] =
+ * iterations run, samples decided by the index parity rule summed over all iterations, the same in the last iteration,
+ * whether the degenerate cut (one side empty) was taken. */
+int ka_debug_kmeans_host(const float* dm, int numrows, const int* samples, int n, int seed_pick,
+                         float* score, int* counts, int* lists, float* mind, float* wmean, int* counters);
 /* Work done by the last run: sum over tasks of len_a*len_b ("useful cells") */
 double ka_tree_cells(ka_ctx* ctx);
 /* Milliseconds spent in the DP kernels of the last ka_tree_run, measured with HIP events

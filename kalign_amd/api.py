@@ -43,7 +43,7 @@ class TaskRec(C.Structure):
 DIST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
 
 EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_consistency_part",
-           "ka_tree_consistency_part_range", "ka_tree_consistency_maps_dev", "ka_debug_set_hooks", "ka_debug_reload_env", "ka_debug_tp_launches", "ka_ctx_fallback_runs", "ka_ctx_helped_tasks", "ka_ctx_create", "ka_ctx_destroy", "ka_ctx_set_stream", "ka_ctx_set_shared", "ka_last_error", "ka_abi_version",
+           "ka_tree_consistency_part_range", "ka_tree_consistency_maps_dev", "ka_debug_set_hooks", "ka_debug_reload_env", "ka_debug_tp_launches", "ka_debug_kmeans_level", "ka_debug_kmeans_host", "ka_ctx_fallback_runs", "ka_ctx_helped_tasks", "ka_ctx_create", "ka_ctx_destroy", "ka_ctx_set_stream", "ka_ctx_set_shared", "ka_last_error", "ka_abi_version",
            "ka_msa_tree", "ka_tree_upload", "ka_tree_run", "ka_tree_refine", "ka_tree_sync", "ka_tree_paths_size",
            "ka_tree_download", "ka_tree_get_profile", "ka_tree_get_timing", "ka_debug_trace", "ka_tree_cells", "ka_tree_kernel_ms", "ka_tree_launch_ms",
            "ka_pairwise_batch", "ka_pairwise_kernel_ms", "ka_tree_build_consistency", "ka_tree_get_consistency",
@@ -96,6 +96,8 @@ def load_library():
     L.ka_ctx_helped_tasks.restype = C.c_longlong
     L.ka_debug_tp_launches.argtypes = []
     L.ka_debug_tp_launches.restype = C.c_longlong
+    L.ka_debug_kmeans_level.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
+    L.ka_debug_kmeans_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.ka_abi_version.restype = C.c_int
     L.ka_msa_tree.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int,
                               C.POINTER(TaskRec), vp, C.c_longlong, vp]
@@ -579,6 +581,64 @@ def _guide_tree(self, codes, n_threads=1, dm_scale=None):
 
 
 Context.guide_tree = _guide_tree
+
+
+def _kmeans_level(self, dm, samples, sets, force_big=False):
+    """tests only: ka_debug_kmeans_level -- ONE level of the device bisection as ka_kmeans_device launches it.
+    dm[numrows, 32] float32, samples = the level's sample buffer (row indices), sets = [(start, n), ...] slices of it.
+    Returns (per set: dict(score[tries], counts[tries, 2], lists[tries, 2, n] (sl / sr valid up to their counts),
+    mind[tries, n], wmean[32], winner)), big) -- big: the <512, 512> shape ran."""
+    dm = np.ascontiguousarray(dm, np.float32)
+    samples = np.ascontiguousarray(samples, np.int32)
+    sets = np.ascontiguousarray(sets, np.int32).reshape(-1, 2)
+    if dm.ndim != 2 or dm.shape[1] != 32:
+        raise KalignAmdError("dm needs 32 columns")
+    tries = np.minimum(40, sets[:, 1]).astype(np.int64)
+    per = tries * sets[:, 1]                                  # samples x candidates of every set
+    before = np.concatenate([[0], np.cumsum(per)])
+    cand0 = np.concatenate([[0], np.cumsum(tries)])
+    score = np.zeros(int(cand0[-1]), np.float32)
+    counts = np.zeros((int(cand0[-1]), 2), np.int32)
+    lists = np.full(2 * int(before[-1]), -1, np.int32)
+    mind = np.zeros(int(before[-1]), np.float32)
+    wmean = np.zeros((len(sets), 32), np.float32)
+    winner = np.zeros(len(sets), np.int32)
+    big = C.c_int(0)
+    self._chk(self.L.ka_debug_kmeans_level(self.h, _ptr(dm), dm.shape[0], _ptr(samples), len(samples), _ptr(sets), len(sets), int(bool(force_big)),
+                                           _ptr(score), _ptr(counts), _ptr(lists), _ptr(mind), _ptr(wmean), _ptr(winner), C.byref(big)))
+    out = []
+    for k, (start, n) in enumerate(sets):
+        t, b = int(tries[k]), int(before[k])
+        out.append(dict(score=score[cand0[k]:cand0[k] + t], counts=counts[cand0[k]:cand0[k] + t],
+                        lists=lists[2 * b:2 * b + 2 * t * n].reshape(t, 2, n), mind=mind[b:b + t * n].reshape(t, n),
+                        wmean=wmean[k], winner=int(winner[k])))
+    return out, bool(big.value)
+
+
+Context.kmeans_level = _kmeans_level
+
+
+def kmeans_host(dm, samples, seed_pick):
+    """tests only: ka_debug_kmeans_host -- the host's split2 (ka_guide.cpp) on one set from one seed; no GPU needed.
+    dict(score, counts[2], sl, sr, mind[n] (min(dl, dr) of the last iteration), wmean[32], iterations, parity_total /
+    parity_last (samples decided by the index parity rule over all iterations / in the last one), degenerate)."""
+    L = load_library()
+    dm = np.ascontiguousarray(dm, np.float32)
+    samples = np.ascontiguousarray(samples, np.int32)
+    if dm.ndim != 2 or dm.shape[1] != 32:
+        raise KalignAmdError("dm needs 32 columns")
+    n = len(samples)
+    score = np.zeros(1, np.float32)
+    counts = np.zeros(2, np.int32)
+    lists = np.full((2, n), -1, np.int32)
+    mind = np.zeros(n, np.float32)
+    wmean = np.zeros(32, np.float32)
+    counters = np.zeros(4, np.int32)
+    if L.ka_debug_kmeans_host(_ptr(dm), dm.shape[0], _ptr(samples), n, int(seed_pick), _ptr(score), _ptr(counts), _ptr(lists),
+                              _ptr(mind), _ptr(wmean), _ptr(counters)):
+        raise KalignAmdError(L.ka_last_error().decode())
+    return dict(score=score[0], counts=counts, sl=lists[0, :counts[0]].copy(), sr=lists[1, :counts[1]].copy(), mind=mind, wmean=wmean,
+                iterations=int(counters[0]), parity_total=int(counters[1]), parity_last=int(counters[2]), degenerate=bool(counters[3]))
 
 
 def _aln_guide_tree(self, rows=None, n=None, gap=b"-", want_dm=False):

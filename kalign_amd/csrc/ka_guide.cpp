@@ -91,8 +91,18 @@ inline int cmp_floats(float a, float b)          // bisectingKmeans.c:63-73
 
 struct Split { std::vector<int> sl, sr; float score = FLT_MAX; };
 
-// split2 (bisectingKmeans.c:766-971): 2-means from one seed sample and its mirror image through the centroid
-void split2(const float* dm, int padded, const std::vector<int>& samples, int num_anchors, int seed_pick, Split& res)
+// What a split2 went through, for the tests (ka_debug_kmeans_host): the set's centroid, min(dl, dr) of every sample in the
+// last iteration, and the counters that show which branches an input reached.
+struct SplitTrace {
+        std::vector<float> w, mind;
+        int iterations = 0, parity_total = 0, parity_last = 0;      // samples decided by the index parity rule (c == 0)
+        bool degenerate = false;
+};
+
+// split2 (bisectingKmeans.c:766-971): 2-means from one seed sample and its mirror image through the centroid.
+// TRACE: the tests' instantiation fills `tr`; the product's (TRACE = false) carries none of it.
+template <bool TRACE = false>
+void split2(const float* dm, int padded, const std::vector<int>& samples, int num_anchors, int seed_pick, Split& res, SplitTrace* tr = nullptr)
 {
         const int num_samples = (int)samples.size();
         std::vector<float> w(padded, 0.0f), wl(padded, 0.0f), wr(padded, 0.0f), cl(padded, 0.0f), cr(padded, 0.0f);
@@ -101,6 +111,7 @@ void split2(const float* dm, int padded, const std::vector<int>& samples, int nu
                 for (int j = 0; j < num_anchors; j++) w[j] += row[j];
         }
         for (int j = 0; j < num_anchors; j++) w[j] /= (float)num_samples;
+        if (TRACE) { tr->w = w; tr->mind.assign(num_samples, 0.0f); }
         {
                 const float* row = dm + (size_t)samples[seed_pick] * padded;
                 for (int j = 0; j < num_anchors; j++) cl[j] = row[j];
@@ -115,6 +126,7 @@ void split2(const float* dm, int padded, const std::vector<int>& samples, int nu
                 num_l = num_r = 0;
                 for (int i = 0; i < num_anchors; i++) { pwr[i] = 0.0f; pwl[i] = 0.0f; }
                 score = 0.0f;
+                if (TRACE) { tr->iterations++; tr->parity_last = 0; }
                 for (int i = 0; i < num_samples; i++) {
                         const int s = samples[i];
                         const float* row = dm + (size_t)s * padded;
@@ -122,12 +134,14 @@ void split2(const float* dm, int padded, const std::vector<int>& samples, int nu
                         const float dr = edist(row, pcr, padded);
                         score += (dl < dr) ? dl : dr;
                         const int c = cmp_floats(dr, dl);
+                        if (TRACE) { tr->mind[i] = (dl < dr) ? dl : dr; if (c == 0) { tr->parity_total++; tr->parity_last++; } }
                         float* acc;
                         if (c == -1 || (c == 0 && (i & 1))) { acc = pwr; res.sr[num_r++] = s; }
                         else { acc = pwl; res.sl[num_l++] = s; }
                         for (int j = 0; j < num_anchors; j++) acc[j] += row[j];
                 }
                 if (num_l == 0 || num_r == 0) {                  // degenerate: cut the list in the middle, score 0
+                        if (TRACE) tr->degenerate = true;
                         score = 0.0f;
                         num_l = num_r = 0;
                         for (int i = 0; i < num_samples / 2; i++) res.sl[num_l++] = samples[i];
@@ -436,6 +450,31 @@ static int guide_tree_from(int numseq, const int* lens, ka_dist_fn dist, void* u
         return KA_OK;
 }
 
+// Tests only: the host's split2 on one set from one seed, with what it went through.  dm[numrows][32]; lists: sl at 0, sr at n.
+extern "C" int ka_debug_kmeans_host(const float* dm, int numrows, const int* samples, int n, int seed_pick,
+                                    float* score, int* counts, int* lists, float* mind, float* wmean, int* counters)
+{
+        if (!dm || !samples || numrows < 1 || n < 1 || seed_pick < 0 || seed_pick >= n || !score || !counts || !lists || !mind || !wmean || !counters)
+                return ka_fail_message("ka_debug_kmeans_host: bad arguments");
+        for (int i = 0; i < n; i++)
+                if (samples[i] < 0 || samples[i] >= numrows) return ka_fail_message("ka_debug_kmeans_host: sample out of range");
+        try {
+                Split res;
+                SplitTrace tr;
+                split2<true>(dm, KA_MAX_ANCHORS, std::vector<int>(samples, samples + n), KA_MAX_ANCHORS, seed_pick, res, &tr);
+                *score = res.score;
+                counts[0] = (int)res.sl.size(); counts[1] = (int)res.sr.size();
+                std::copy(res.sl.begin(), res.sl.end(), lists);
+                std::copy(res.sr.begin(), res.sr.end(), lists + n);
+                std::copy(tr.mind.begin(), tr.mind.end(), mind);
+                std::copy(tr.w.begin(), tr.w.end(), wmean);
+                counters[0] = tr.iterations; counters[1] = tr.parity_total; counters[2] = tr.parity_last; counters[3] = tr.degenerate ? 1 : 0;
+        } catch (const std::exception& e) {
+                return ka_fail_message((std::string("ka_debug_kmeans_host: ") + e.what()).c_str());
+        }
+        return KA_OK;
+}
+
 // upgma()'s bookkeeping (bisectingKmeans.c:996-1047) for a merge sequence found on the device: merge k joins the
 // current subtrees of slots a < b into slot a; the last merge's slot holds the root.  Library-internal.
 __attribute__((visibility("hidden"))) int ka_tasks_from_merges(int numseq, const int* merges_ab, int* tasks_abc)
@@ -475,4 +514,23 @@ extern "C" int ka_guide_tree(ka_ctx* ctx, int numseq, const uint8_t* codes, cons
         const int rc = ka_guide_tree_from(numseq, lens, device_dist, &D, n_threads, dm_scale, tasks_abc, seq_distances);
         g_km = KmDevice();
         return rc;
+}
+
+// Tests only: one level of the device bisection through the function ka_kmeans_device calls for it (ka_kmeans.hip: km_level).
+extern "C" int ka_debug_kmeans_level(ka_ctx* ctx, const float* dm, int numrows, const int* samples, int n_samples,
+                                     const int* sets_start_n, int n_sets, int force_big,
+                                     float* score, int* counts, int* lists, float* mind, float* wmean, int* winner, int* big_out)
+{
+        int device = 0;
+        hipStream_t stream = nullptr;
+        if (!ctx || ka_ctx_device_stream(ctx, &device, &stream)) return ka_fail_message("ka_debug_kmeans_level: bad context");
+        if (!score || !counts || !lists || !mind || !wmean || !winner) return ka_fail_message("ka_debug_kmeans_level: bad arguments");
+        try {
+                std::string why;
+                if (ka_kmeans_debug_level(device, stream, dm, numrows, samples, n_samples, sets_start_n, n_sets, force_big,
+                                          score, counts, lists, mind, wmean, winner, big_out, why)) return ka_fail_message(why.c_str());
+        } catch (const std::exception& e) {
+                return ka_fail_message((std::string("ka_debug_kmeans_level: ") + e.what()).c_str());
+        }
+        return KA_OK;
 }

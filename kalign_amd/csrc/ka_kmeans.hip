@@ -16,9 +16,11 @@
 //     wave walks both lists at once -- lanes 0..31 carry the 32 chains of the left centroid, lanes 32..63 those of the right
 //     one.  The score is only ever read after the last iteration: its chain runs once, at the end.
 // Host side (ka_kmeans_device): level-synchronous over the recursion -- per level one launch for the centroids of the level's
-// sets, one for all candidates, the acceptance rule on the host (40 scores per set), one launch that gathers the winners'
-// lists into the next level's sample buffer.
+// sets, one for all candidates (km_level), the acceptance rule on the host (km_accept: 40 scores per set), one launch that
+// gathers the winners' lists into the next level's sample buffer.  ka_kmeans_debug_level hands the tests what km_level left on
+// the device for one level, candidate by candidate.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <mutex>
 #include <cfloat>
 #include <chrono>
@@ -304,10 +306,109 @@ struct Buf {
         Buf(const Buf&) = delete;
         Buf& operator=(const Buf&) = delete;
 };
-}  // namespace
 
 #define KM_MAX_DEVICES 64
 #define KMCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return 1; } } while (0)
+
+// One pool of buffers and one LDS opt-in PER DEVICE, process-wide, used under the device's lock: the guide tree may be asked
+// for from several threads and devices at once (ka_multi_*, ensemble members side by side), the opt-in is a per-device
+// attribute, and buffers owned by a thread would be freed from its destructors -- possibly after the runtime is gone.
+// (Never freed: they live as long as the process, like the runtime they belong to; a guide tree is built per alignment, the
+// allocations cost more than a level.)
+struct Pool {
+        Buf<float> d_dm, d_wmean, d_mind, d_score;
+        Buf<int> d_samples[2], d_lists, d_cand_set;
+        Buf<KmSet> d_sets;
+        Buf<long long> d_list_off, d_src_off, d_dst_off;
+        Buf<unsigned char> d_assign;
+        Buf<int2> d_cand_n, d_src_n;
+};
+std::mutex km_dev_mu[KM_MAX_DEVICES];
+bool km_dev_opted[KM_MAX_DEVICES];
+Pool* km_pools[KM_MAX_DEVICES];
+
+// the device's pool (under km_dev_mu[device]), its per-sample buffers sized for N samples
+int km_pool(int device, size_t N, Pool*& out, std::string& err)
+{
+        if (!km_dev_opted[device]) {
+                // the row tiles of the big shape take 128 KiB of dynamic LDS
+                KMCHK(hipFuncSetAttribute((const void*)km_centroid_kernel<512, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * KM_PAD * sizeof(float)));
+                KMCHK(hipFuncSetAttribute((const void*)km_split_kernel<512, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * KM_PAD * sizeof(float)));
+                km_dev_opted[device] = true;
+        }
+        if (!km_pools[device]) km_pools[device] = new Pool();
+        Pool& pool = *km_pools[device];
+        if (!pool.d_dm.alloc(N * KM_PAD) || !pool.d_samples[0].alloc(N) || !pool.d_samples[1].alloc(N) || !pool.d_lists.alloc(2 * N * KM_TRIES) ||
+            !pool.d_assign.alloc(N * KM_TRIES) || !pool.d_mind.alloc(N * KM_TRIES)) { err = "hipMalloc failed (2-means bisection)"; return 1; }
+        out = &pool;
+        return 0;
+}
+
+struct Open { int node, start, n; };            // a set that still has to be split: a slice of the level's sample buffer
+
+// What one level's launches were given, as the host keeps it: candidate slot c of set k is sets[k].cand0 + c, its two lists
+// lie at list_off[slot] (sl) and list_off[slot] + n (sr) ints into d_lists, its n bytes / floats of scratch at list_off[slot] / 2.
+struct Level {
+        std::vector<KmSet> sets;
+        std::vector<int> cand_set;
+        std::vector<long long> list_off;
+        int nslots = 0;
+        bool big = false;                        // the <512, 512> shape ran
+};
+
+// ONE level of the bisection, enqueued on `stream` (nothing is waited for): the centroid of every set of `split` (slices of
+// d_samples) and all their candidates.  The sets' sizes must add up to no more than the pool was sized for.  force_big: the
+// <512, 512> shape whatever the sizes (the product takes it for every set of a level that holds one above 1024).
+int km_level(Pool& pool, hipStream_t stream, const int* d_samples, const std::vector<Open>& split, bool force_big, Level& L, std::string& err)
+{
+        const int nsets = (int)split.size();
+        L.sets.resize(nsets);
+        L.cand_set.clear();
+        L.list_off.clear();
+        long long before = 0;
+        for (int k = 0; k < nsets; k++) {
+                const int tries = std::min(KM_TRIES, split[k].n);
+                L.sets[k] = KmSet{ split[k].start, split[k].n, (int)L.cand_set.size(), 0 };
+                for (int c = 0; c < tries; c++) { L.cand_set.push_back(k); L.list_off.push_back(2 * before); before += split[k].n; }
+        }
+        const int nslots = L.nslots = (int)L.cand_set.size();
+        if (!pool.d_sets.alloc(nsets) || !pool.d_cand_set.alloc(nslots) || !pool.d_list_off.alloc(nslots) || !pool.d_wmean.alloc((size_t)nsets * KM_PAD) ||
+            !pool.d_score.alloc(nslots) || !pool.d_cand_n.alloc(nslots)) { err = "hipMalloc failed (2-means bisection)"; return 1; }
+        KMCHK(hipMemcpyAsync(pool.d_sets.p, L.sets.data(), sizeof(KmSet) * nsets, hipMemcpyHostToDevice, stream));
+        KMCHK(hipMemcpyAsync(pool.d_cand_set.p, L.cand_set.data(), sizeof(int) * nslots, hipMemcpyHostToDevice, stream));
+        KMCHK(hipMemcpyAsync(pool.d_list_off.p, L.list_off.data(), sizeof(long long) * nslots, hipMemcpyHostToDevice, stream));
+        int largest = 0;
+        for (const Open& o : split) largest = std::max(largest, o.n);
+        L.big = force_big || largest > 1024;
+        if (L.big) {
+                hipLaunchKernelGGL((km_centroid_kernel<512, 512>), dim3(nsets), dim3(512), 2 * 512 * KM_PAD * sizeof(float), stream, pool.d_dm.p, d_samples, pool.d_sets.p, pool.d_wmean.p);
+                hipLaunchKernelGGL((km_split_kernel<512, 512>), dim3(nslots), dim3(512), 2 * 512 * KM_PAD * sizeof(float), stream, pool.d_dm.p, d_samples, pool.d_sets.p, pool.d_cand_set.p, pool.d_wmean.p,
+                                   pool.d_lists.p, pool.d_list_off.p, pool.d_assign.p, pool.d_mind.p, pool.d_score.p, pool.d_cand_n.p);
+        } else {
+                hipLaunchKernelGGL((km_centroid_kernel<128, 32>), dim3(nsets), dim3(128), 2 * 32 * KM_PAD * sizeof(float), stream, pool.d_dm.p, d_samples, pool.d_sets.p, pool.d_wmean.p);
+                hipLaunchKernelGGL((km_split_kernel<128, 32>), dim3(nslots), dim3(128), 2 * 32 * KM_PAD * sizeof(float), stream, pool.d_dm.p, d_samples, pool.d_sets.p, pool.d_cand_set.p, pool.d_wmean.p,
+                                   pool.d_lists.p, pool.d_list_off.p, pool.d_assign.p, pool.d_mind.p, pool.d_score.p, pool.d_cand_n.p);
+        }
+        KMCHK(hipGetLastError());
+        return 0;
+}
+
+// the reference's acceptance rule (:318-352): seeds in groups of four, a candidate replaces the best one on a strictly lower
+// score, the first group that changes nothing ends the search.  Returns the winner's slot.
+int km_accept(const float* score, int cand0, int tries)
+{
+        int best = -1;
+        for (int i = 0; i < tries; i += 4) {
+                int change = 0;
+                for (int j = 0; j < 4 && i + j < tries; j++) {
+                        const int c = cand0 + i + j;
+                        if (best < 0 || score[best] > score[c]) { best = c; change++; }
+                }
+                if (!change) break;
+        }
+        return best;
+}
+}  // namespace
 
 // dm: numseq x 32 floats (host).  nodes[0] is the root; a node with left < 0 is a leaf cluster (its members in `cluster`, in
 // the reference's order).  Returns 0, or 1 with `err` set.
@@ -315,41 +416,13 @@ int ka_kmeans_device(int device, hipStream_t stream, const float* dm, int numseq
 {
         KMCHK(hipSetDevice(device));
         if (device < 0 || device >= KM_MAX_DEVICES) { err = "ka_kmeans_device: device index out of range"; return 1; }
-        // One pool of buffers and one LDS opt-in PER DEVICE, process-wide, used under the device's lock: the guide tree may be asked
-        // for from several threads and devices at once (ka_multi_*, ensemble members side by side), the opt-in is a per-device
-        // attribute, and buffers owned by a thread would be freed from its destructors -- possibly after the runtime is gone.
-        // (Never freed: they live as long as the process, like the runtime they belong to.)
-        static std::mutex dev_mu[KM_MAX_DEVICES];
-        static bool dev_opted[KM_MAX_DEVICES];
-        std::lock_guard<std::mutex> dev_lock(dev_mu[device]);
-        if (!dev_opted[device]) {
-                // the row tiles of the big shape take 128 KiB of dynamic LDS
-                KMCHK(hipFuncSetAttribute((const void*)km_centroid_kernel<512, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * KM_PAD * sizeof(float)));
-                KMCHK(hipFuncSetAttribute((const void*)km_split_kernel<512, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * KM_PAD * sizeof(float)));
-                dev_opted[device] = true;
-        }
-        // (the buffers live as long as the process: a guide tree is built per alignment, the allocations cost more than a level)
-        struct Pool {
-                Buf<float> d_dm, d_wmean, d_mind, d_score;
-                Buf<int> d_samples[2], d_lists, d_cand_set;
-                Buf<KmSet> d_sets;
-                Buf<long long> d_list_off, d_src_off, d_dst_off;
-                Buf<unsigned char> d_assign;
-                Buf<int2> d_cand_n, d_src_n;
-        };
-        static Pool* pools[KM_MAX_DEVICES];
-        if (!pools[device]) pools[device] = new Pool();
-        Pool& pool = *pools[device];
-        Buf<float>&d_dm = pool.d_dm, &d_wmean = pool.d_wmean, &d_mind = pool.d_mind, &d_score = pool.d_score;
-        Buf<int>(&d_samples)[2] = pool.d_samples; Buf<int>&d_lists = pool.d_lists, &d_cand_set = pool.d_cand_set;
-        Buf<KmSet>& d_sets = pool.d_sets;
-        Buf<long long>&d_list_off = pool.d_list_off, &d_src_off = pool.d_src_off, &d_dst_off = pool.d_dst_off;
-        Buf<unsigned char>& d_assign = pool.d_assign;
-        Buf<int2>&d_cand_n = pool.d_cand_n, &d_src_n = pool.d_src_n;
+        std::lock_guard<std::mutex> dev_lock(km_dev_mu[device]);
         const size_t N = (size_t)numseq;
-        if (!d_dm.alloc(N * KM_PAD) || !d_samples[0].alloc(N) || !d_samples[1].alloc(N) || !d_lists.alloc(2 * N * KM_TRIES) ||
-            !d_assign.alloc(N * KM_TRIES) || !d_mind.alloc(N * KM_TRIES)) { err = "hipMalloc failed (2-means bisection)"; return 1; }
-        KMCHK(hipMemcpyAsync(d_dm.p, dm, sizeof(float) * N * KM_PAD, hipMemcpyHostToDevice, stream));
+        Pool* pool_p = nullptr;
+        if (km_pool(device, N, pool_p, err)) return 1;
+        Pool& pool = *pool_p;
+        Buf<int>(&d_samples)[2] = pool.d_samples;
+        KMCHK(hipMemcpyAsync(pool.d_dm.p, dm, sizeof(float) * N * KM_PAD, hipMemcpyHostToDevice, stream));
         std::vector<int> level_samples(N);
         for (int i = 0; i < numseq; i++) level_samples[i] = i;
         KMCHK(hipMemcpyAsync(d_samples[0].p, level_samples.data(), sizeof(int) * N, hipMemcpyHostToDevice, stream));
@@ -357,9 +430,9 @@ int ka_kmeans_device(int device, hipStream_t stream, const float* dm, int numseq
         const auto t_start = std::chrono::steady_clock::now();
         nodes.clear();
         nodes.push_back(KaKmNode());
-        struct Open { int node, start, n; };
         std::vector<Open> open(1, Open{ 0, 0, numseq });               // the level's sets that still have to be split
         int cur = 0;
+        Level L;
         for (int depth = 0; !open.empty(); depth++) {
                 if (depth > 4096) { err = "bisecting k-means degenerated (recursion deeper than 4096)"; return 1; }
                 // sets below the threshold are leaf clusters: their members come from the level's sample buffer
@@ -374,33 +447,9 @@ int ka_kmeans_device(int device, hipStream_t stream, const float* dm, int numseq
                 }
                 if (split.empty()) break;
                 const int nsets = (int)split.size();
-                std::vector<KmSet> sets(nsets);
-                std::vector<int> cand_set;
-                std::vector<long long> list_off;
-                long long before = 0;
-                for (int k = 0; k < nsets; k++) {
-                        const int tries = std::min(KM_TRIES, split[k].n);
-                        sets[k] = KmSet{ split[k].start, split[k].n, (int)cand_set.size(), 0 };
-                        for (int c = 0; c < tries; c++) { cand_set.push_back(k); list_off.push_back(2 * before); before += split[k].n; }
-                }
-                const int nslots = (int)cand_set.size();
-                if (!d_sets.alloc(nsets) || !d_cand_set.alloc(nslots) || !d_list_off.alloc(nslots) || !d_wmean.alloc((size_t)nsets * KM_PAD) ||
-                    !d_score.alloc(nslots) || !d_cand_n.alloc(nslots) || !d_src_off.alloc(nsets) || !d_src_n.alloc(nsets) || !d_dst_off.alloc(2 * (size_t)nsets)) { err = "hipMalloc failed (2-means bisection)"; return 1; }
-                KMCHK(hipMemcpyAsync(d_sets.p, sets.data(), sizeof(KmSet) * nsets, hipMemcpyHostToDevice, stream));
-                KMCHK(hipMemcpyAsync(d_cand_set.p, cand_set.data(), sizeof(int) * nslots, hipMemcpyHostToDevice, stream));
-                KMCHK(hipMemcpyAsync(d_list_off.p, list_off.data(), sizeof(long long) * nslots, hipMemcpyHostToDevice, stream));
-                int largest = 0;
-                for (const Open& o : split) largest = std::max(largest, o.n);
-                if (largest > 1024) {
-                        hipLaunchKernelGGL((km_centroid_kernel<512, 512>), dim3(nsets), dim3(512), 2 * 512 * KM_PAD * sizeof(float), stream, d_dm.p, d_samples[cur].p, d_sets.p, d_wmean.p);
-                        hipLaunchKernelGGL((km_split_kernel<512, 512>), dim3(nslots), dim3(512), 2 * 512 * KM_PAD * sizeof(float), stream, d_dm.p, d_samples[cur].p, d_sets.p, d_cand_set.p, d_wmean.p,
-                                           d_lists.p, d_list_off.p, d_assign.p, d_mind.p, d_score.p, d_cand_n.p);
-                } else {
-                        hipLaunchKernelGGL((km_centroid_kernel<128, 32>), dim3(nsets), dim3(128), 2 * 32 * KM_PAD * sizeof(float), stream, d_dm.p, d_samples[cur].p, d_sets.p, d_wmean.p);
-                        hipLaunchKernelGGL((km_split_kernel<128, 32>), dim3(nslots), dim3(128), 2 * 32 * KM_PAD * sizeof(float), stream, d_dm.p, d_samples[cur].p, d_sets.p, d_cand_set.p, d_wmean.p,
-                                           d_lists.p, d_list_off.p, d_assign.p, d_mind.p, d_score.p, d_cand_n.p);
-                }
-                KMCHK(hipGetLastError());
+                if (!pool.d_src_off.alloc(nsets) || !pool.d_src_n.alloc(nsets) || !pool.d_dst_off.alloc(2 * (size_t)nsets)) { err = "hipMalloc failed (2-means bisection)"; return 1; }
+                if (km_level(pool, stream, d_samples[cur].p, split, false, L, err)) return 1;
+                const int nslots = L.nslots;
                 if (getenv("KA_KMEANS_VERBOSE")) {
                         KMCHK(hipStreamSynchronize(stream));
                         int mx = 0; for (const Open& o : split) mx = std::max(mx, o.n);
@@ -409,27 +458,16 @@ int ka_kmeans_device(int device, hipStream_t stream, const float* dm, int numseq
                 }
                 std::vector<float> score(nslots);
                 std::vector<int2> cn(nslots);
-                KMCHK(hipMemcpyAsync(score.data(), d_score.p, sizeof(float) * nslots, hipMemcpyDeviceToHost, stream));
-                KMCHK(hipMemcpyAsync(cn.data(), d_cand_n.p, sizeof(int2) * nslots, hipMemcpyDeviceToHost, stream));
+                KMCHK(hipMemcpyAsync(score.data(), pool.d_score.p, sizeof(float) * nslots, hipMemcpyDeviceToHost, stream));
+                KMCHK(hipMemcpyAsync(cn.data(), pool.d_cand_n.p, sizeof(int2) * nslots, hipMemcpyDeviceToHost, stream));
                 KMCHK(hipStreamSynchronize(stream));
-                // the reference's acceptance rule (:318-352): seeds in groups of four, a candidate replaces the best one on a
-                // strictly lower score, the first group that changes nothing ends the search
                 std::vector<long long> src_off(nsets), dst_off(2 * (size_t)nsets);
                 std::vector<int2> src_n(nsets);
                 std::vector<Open> next;
                 long long fill = 0;
                 for (int k = 0; k < nsets; k++) {
-                        const int tries = std::min(KM_TRIES, split[k].n);
-                        int best = -1;
-                        for (int i = 0; i < tries; i += 4) {
-                                int change = 0;
-                                for (int j = 0; j < 4 && i + j < tries; j++) {
-                                        const int c = sets[k].cand0 + i + j;
-                                        if (best < 0 || score[best] > score[c]) { best = c; change++; }
-                                }
-                                if (!change) break;
-                        }
-                        src_off[k] = list_off[best]; src_n[k] = cn[best];
+                        const int best = km_accept(score.data(), L.sets[k].cand0, std::min(KM_TRIES, split[k].n));
+                        src_off[k] = L.list_off[best]; src_n[k] = cn[best];
                         const int nl = cn[best].x, nr = cn[best].y;
                         const int ln = (int)nodes.size();
                         nodes.push_back(KaKmNode()); nodes.push_back(KaKmNode());
@@ -437,14 +475,57 @@ int ka_kmeans_device(int device, hipStream_t stream, const float* dm, int numseq
                         dst_off[2 * k] = fill; next.push_back(Open{ ln, (int)fill, nl }); fill += nl;
                         dst_off[2 * k + 1] = fill; next.push_back(Open{ ln + 1, (int)fill, nr }); fill += nr;
                 }
-                KMCHK(hipMemcpyAsync(d_src_off.p, src_off.data(), sizeof(long long) * nsets, hipMemcpyHostToDevice, stream));
-                KMCHK(hipMemcpyAsync(d_src_n.p, src_n.data(), sizeof(int2) * nsets, hipMemcpyHostToDevice, stream));
-                KMCHK(hipMemcpyAsync(d_dst_off.p, dst_off.data(), sizeof(long long) * 2 * nsets, hipMemcpyHostToDevice, stream));
-                hipLaunchKernelGGL(km_gather_kernel, dim3(nsets), dim3(256), 0, stream, d_lists.p, d_src_off.p, d_src_n.p, d_dst_off.p, d_samples[cur ^ 1].p);
+                KMCHK(hipMemcpyAsync(pool.d_src_off.p, src_off.data(), sizeof(long long) * nsets, hipMemcpyHostToDevice, stream));
+                KMCHK(hipMemcpyAsync(pool.d_src_n.p, src_n.data(), sizeof(int2) * nsets, hipMemcpyHostToDevice, stream));
+                KMCHK(hipMemcpyAsync(pool.d_dst_off.p, dst_off.data(), sizeof(long long) * 2 * nsets, hipMemcpyHostToDevice, stream));
+                hipLaunchKernelGGL(km_gather_kernel, dim3(nsets), dim3(256), 0, stream, pool.d_lists.p, pool.d_src_off.p, pool.d_src_n.p, pool.d_dst_off.p, d_samples[cur ^ 1].p);
                 KMCHK(hipGetLastError());
                 KMCHK(hipStreamSynchronize(stream));                    // (the host vectors above are about to go out of scope)
                 cur ^= 1;
                 open.swap(next);
         }
+        return 0;
+}
+
+// Tests only (ka_debug_kmeans_level): ONE level through km_level, the function the loop above calls, and everything it left
+// on the device -- per candidate slot the score, (n_left, n_right), both lists and the `mind` scratch of its last iteration,
+// per set the centroid and the slot the acceptance rule picks.  Layout as on the device: see struct Level.
+int ka_kmeans_debug_level(int device, hipStream_t stream, const float* dm, int numrows, const int* samples, int n_samples,
+                          const int* sets_start_n, int n_sets, int force_big,
+                          float* score, int* counts, int* lists, float* mind, float* wmean, int* winner, int* big_out, std::string& err)
+{
+        if (!dm || !samples || !sets_start_n || numrows < 1 || n_samples < 1 || n_sets < 1) { err = "ka_debug_kmeans_level: bad arguments"; return 1; }
+        // everything a kernel indexes with is checked here: rows of dm, slices of the sample buffer
+        for (int i = 0; i < n_samples; i++)
+                if (samples[i] < 0 || samples[i] >= numrows) { err = "ka_debug_kmeans_level: sample out of range"; return 1; }
+        std::vector<Open> split(n_sets);
+        size_t total = 0;
+        for (int k = 0; k < n_sets; k++) {
+                const int start = sets_start_n[2 * k], n = sets_start_n[2 * k + 1];
+                if (start < 0 || n < 2 || n > n_samples || start > n_samples - n) { err = "ka_debug_kmeans_level: set out of range"; return 1; }
+                split[k] = Open{ -1, start, n };
+                total += (size_t)n;
+        }
+        KMCHK(hipSetDevice(device));
+        if (device < 0 || device >= KM_MAX_DEVICES) { err = "ka_debug_kmeans_level: device index out of range"; return 1; }
+        std::lock_guard<std::mutex> dev_lock(km_dev_mu[device]);
+        const size_t N = std::max(std::max((size_t)numrows, (size_t)n_samples), total);
+        Pool* pool_p = nullptr;
+        if (km_pool(device, N, pool_p, err)) return 1;
+        Pool& pool = *pool_p;
+        KMCHK(hipMemcpyAsync(pool.d_dm.p, dm, sizeof(float) * (size_t)numrows * KM_PAD, hipMemcpyHostToDevice, stream));
+        KMCHK(hipMemcpyAsync(pool.d_samples[0].p, samples, sizeof(int) * (size_t)n_samples, hipMemcpyHostToDevice, stream));
+        Level L;
+        if (km_level(pool, stream, pool.d_samples[0].p, split, force_big != 0, L, err)) return 1;
+        size_t cells = 0;                                             // samples x candidates over all sets
+        for (int k = 0; k < n_sets; k++) cells += (size_t)std::min(KM_TRIES, split[k].n) * (size_t)split[k].n;
+        KMCHK(hipMemcpyAsync(score, pool.d_score.p, sizeof(float) * L.nslots, hipMemcpyDeviceToHost, stream));
+        KMCHK(hipMemcpyAsync(counts, pool.d_cand_n.p, sizeof(int2) * L.nslots, hipMemcpyDeviceToHost, stream));
+        KMCHK(hipMemcpyAsync(lists, pool.d_lists.p, sizeof(int) * 2 * cells, hipMemcpyDeviceToHost, stream));
+        KMCHK(hipMemcpyAsync(mind, pool.d_mind.p, sizeof(float) * cells, hipMemcpyDeviceToHost, stream));
+        KMCHK(hipMemcpyAsync(wmean, pool.d_wmean.p, sizeof(float) * (size_t)n_sets * KM_PAD, hipMemcpyDeviceToHost, stream));
+        KMCHK(hipStreamSynchronize(stream));
+        for (int k = 0; k < n_sets; k++) winner[k] = km_accept(score, L.sets[k].cand0, std::min(KM_TRIES, split[k].n)) - L.sets[k].cand0;
+        if (big_out) *big_out = L.big ? 1 : 0;
         return 0;
 }

@@ -84,8 +84,32 @@ def lib():
         L.refh_bpm_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.refh_kalign.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
                                   C.c_float, C.c_float, C.c_float, C.POINTER(C.c_char_p), C.POINTER(C.c_int)]
+        if hasattr(L, "refh_split_all"):             # (a libkalign_ref.so built before ref_split_harness.c existed has none)
+            L.refh_split_all.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
+
+
+def has_split():
+    return available() and hasattr(lib(), "refh_split_all")
+
+
+def split_all(dm, samples):
+    """The reference's own split2 (bisectingKmeans.c:766-971, static there; oracle/ref_split_harness.c) for every seed
+    k * step bisecting_kmeans tries on this set: dm[numrows, 32] float32, samples = row indices.
+    Returns (score[tries], counts[tries, 2], lists[tries, 2, n]) -- sl / sr valid up to their counts."""
+    dm = np.ascontiguousarray(dm, np.float32)
+    samples = np.ascontiguousarray(samples, np.int32)
+    n = len(samples)
+    tries = min(40, n)
+    score = np.zeros(tries, np.float32)
+    counts = np.zeros((tries, 2), np.int32)
+    lists = np.full((tries, 2, n), -1, np.int32)
+    if lib().refh_split_all(_ptr(dm), dm.shape[0], dm.shape[1], _ptr(samples), n, tries, n // tries,
+                            _ptr(score), _ptr(counts), _ptr(lists)):
+        raise RuntimeError("split2 failed")
+    return score, counts, lists
 
 
 def noise_multipliers(seed, sigma, n):
