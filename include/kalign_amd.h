@@ -497,6 +497,41 @@ int  ka_ens_consensus(ka_ens* e, int min_support, const uint8_t* letters, uint8_
 int  ka_ens_confidence(ka_ens* e, const uint8_t* rows, long long row_stride, int alnlen, float* res_conf_out, float* col_conf_out);
 int  ka_ens_stats(ka_ens* e, double* stats_out, long long* level_counts_out, double* level_ms_out);
 
+/* ---- the ensemble's POAR table as a file (ka_poar.hip, ka_poar.cpp, ka_ens.cpp) ------------------------------------------------
+ * kalign_ensemble's save_poar_path and kalign_consensus_from_poar (lib/src/ensemble.c:349-355, 500-543): the table of pairs of
+ * aligned residues the members hold, written and read as poar_table_write / poar_table_read do (lib/src/poar.c:203-325), byte for
+ * byte.  All words are 32-bit little endian:
+ *     "POAR" (0x524F4150) | version = 1 | numseq | n_alignments
+ *     for every pair i < j (i ascending, then j):  n_entries | n_entries x { key = ri << 20 | rj ; mask (bit k: member k aligns
+ *     residue ri of i with residue rj of j) }, keys ascending
+ * The stage itself never needs the table (support comes from the members' position maps); it is built when asked for.
+ *   ka_ens_table_size        the file's size in bytes and its number of entries, on a handle with every member added or on a handle
+ *                            opened from a table.
+ *   ka_ens_table_write       the file at `path`; ka_ens_table_image: the same bytes at out (cap >= the size, else an error).
+ *                            A handle opened from a table gives back what it read.
+ *   ka_ens_open_table        a handle whose support comes from a file (ka_ens_open_table_image: from the file's bytes in memory)
+ *                            instead of members: n_runs is the file's n_alignments; ka_ens_score_rows, ka_ens_consensus,
+ *                            ka_ens_confidence and ka_ens_stats work as on a handle with members, ka_ens_add_member fails.
+ *                            The table is kept on the device (first entry of every pair, entries).
+ *   ka_ens_n_runs            members of the handle (the file's n_alignments for an opened table).
+ *   ka_ens_table_stats       out6 = device ms of the last table's count passes and of its write passes, host ms spent writing /
+ *                            copying it out (ka_ens_table_write / _image) or reading and checking it (ka_ens_open_table*), entries,
+ *                            chunks the table left the device in, host ms spent waiting for them.  ka_ens_stats is unchanged.
+ *   ka_poar_check_image      the reader's checks alone, on the host: needs no context and no GPU.  Stricter than the reference,
+ *                            which trusts the file.  Errors (ka_last_error names the cause): wrong magic; version other than 1;
+ *                            numseq different from the caller's; n_alignments outside 1..32; fewer or more bytes than the counts
+ *                            imply; a key with ri >= lens[i] or rj >= lens[j]; keys of a pair not strictly ascending; a mask that is
+ *                            0 or has a bit at or above n_alignments.  n_runs_out / entries_out (optional) on success.
+ */
+int  ka_ens_table_size(ka_ens* e, long long* bytes_out, long long* entries_out);
+int  ka_ens_table_write(ka_ens* e, const char* path);
+int  ka_ens_table_image(ka_ens* e, uint8_t* out, long long cap);
+int  ka_ens_open_table(ka_ctx* ctx, int numseq, const int* lens, const char* path, ka_ens** out);
+int  ka_ens_open_table_image(ka_ctx* ctx, int numseq, const int* lens, const uint8_t* image, long long n_bytes, ka_ens** out);
+int  ka_ens_n_runs(ka_ens* e);
+int  ka_ens_table_stats(ka_ens* e, double* out6);
+int  ka_poar_check_image(const uint8_t* image, long long n_bytes, int numseq, const int* lens, int* n_runs_out, long long* entries_out);
+
 /* ---- scoring an alignment against a reference alignment (ka_cmp.hip, ka_cmp.cpp) -------------------------------------------
  * kalign_msa_compare, kalign_msa_compare_detailed and kalign_msa_compare_with_mask (lib/src/msa_cmp.c) on the device.  Both
  * alignments hold the same numseq sequences in the same row order (the reference pairs its rows after sorting both by name;

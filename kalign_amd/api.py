@@ -57,7 +57,8 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_guide_last_bisect_ms", "ka_device_count", "ka_multi_create", "ka_multi_destroy", "ka_multi_world", "ka_multi_runs", "ka_multi_last_error",
            "ka_multi_consistency", "ka_multi_tree_run", "ka_multi_paths_size", "ka_multi_download", "ka_multi_ctx", "ka_multi_adopt",
            "ka_tree_adopt_alignment", "ka_ens_create", "ka_ens_destroy", "ka_ens_add_member", "ka_ens_score_rows", "ka_ens_consensus",
-           "ka_ens_confidence", "ka_ens_stats", "ka_cmp_create", "ka_cmp_destroy", "ka_cmp_set_mask", "ka_cmp_score",
+           "ka_ens_confidence", "ka_ens_stats", "ka_ens_table_size", "ka_ens_table_write", "ka_ens_table_image", "ka_ens_open_table",
+           "ka_ens_open_table_image", "ka_ens_n_runs", "ka_ens_table_stats", "ka_poar_check_image", "ka_cmp_create", "ka_cmp_destroy", "ka_cmp_set_mask", "ka_cmp_score",
            "ka_cmp_score_batch", "ka_cmp_stats"]
 
 
@@ -190,6 +191,14 @@ def load_library():
     L.ka_ens_consensus.argtypes = [vp, C.c_int, vp, vp, C.c_longlong, C.POINTER(C.c_int)]
     L.ka_ens_confidence.argtypes = [vp, vp, C.c_longlong, C.c_int, vp, vp]
     L.ka_ens_stats.argtypes = [vp, vp, vp, vp]
+    L.ka_ens_table_size.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.ka_ens_table_write.argtypes = [vp, C.c_char_p]
+    L.ka_ens_table_image.argtypes = [vp, vp, C.c_longlong]
+    L.ka_ens_open_table.argtypes = [vp, C.c_int, vp, C.c_char_p, C.POINTER(vp)]
+    L.ka_ens_open_table_image.argtypes = [vp, C.c_int, vp, vp, C.c_longlong, C.POINTER(vp)]
+    L.ka_ens_n_runs.argtypes = [vp]
+    L.ka_ens_table_stats.argtypes = [vp, vp]
+    L.ka_poar_check_image.argtypes = [vp, C.c_longlong, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
     L.ka_cmp_create.argtypes = [vp, C.c_int, vp, vp, C.c_longlong, C.c_int, C.POINTER(vp)]
     L.ka_cmp_destroy.argtypes = [vp]
     L.ka_cmp_destroy.restype = None
@@ -740,18 +749,30 @@ def _rows_array(rows, n):
 
 class Ensemble(_CtxChild):
     """The consensus stage of an ensemble (ka_ens): the members' rows on the device, then scores, the consensus alignment
-    and confidences of any alignment of the same sequences.  Rows are in the members' sequence order."""
+    and confidences of any alignment of the same sequences.  Rows are in the members' sequence order.
+    With table= (a POAR file's path, or its bytes) the support comes from that table instead of members
+    (Context.ensemble_from_table): n_runs is the file's, add_member fails, everything else works the same."""
     _destroy = "ka_ens_destroy"
 
-    def __init__(self, ctx, lens, n_runs):
+    def __init__(self, ctx, lens, n_runs=None, table=None):
         self.ctx, self.L = ctx, ctx.L
         self.lens = np.ascontiguousarray(lens, np.int32)
-        self.n, self.n_runs = len(self.lens), int(n_runs)
+        self.n = len(self.lens)
         h = C.c_void_p()
         if not ctx.h:
             raise KalignAmdError("the context is closed")
-        ctx._chk(self.L.ka_ens_create(ctx.h, self.n, _ptr(self.lens), self.n_runs, C.byref(h)))
+        if table is None and n_runs is None:
+            raise KalignAmdError("an Ensemble takes n_runs members or a POAR table")
+        if table is None:
+            ctx._chk(self.L.ka_ens_create(ctx.h, self.n, _ptr(self.lens), int(n_runs), C.byref(h)))
+        elif isinstance(table, (bytes, bytearray, memoryview, np.ndarray)):
+            img = np.frombuffer(bytes(table), np.uint8)
+            ctx._chk(self.L.ka_ens_open_table_image(ctx.h, self.n, _ptr(self.lens), _ptr(img if len(img) else np.zeros(1, np.uint8)),
+                                                    len(img), C.byref(h)))
+        else:
+            ctx._chk(self.L.ka_ens_open_table(ctx.h, self.n, _ptr(self.lens), os.fsencode(table), C.byref(h)))
         self._adopt(ctx, h)
+        self.n_runs = int(self.L.ka_ens_n_runs(h))
 
     def add_member(self, k, rows):
         a, w = _rows_array(rows, self.n)
@@ -796,7 +817,28 @@ class Ensemble(_CtxChild):
         out = dict(zip(keys, st.tolist()))
         out["level_candidates"] = {L: int(cnt[L]) for L in range(33) if cnt[L]}
         out["level_ms"] = {L: float(ms[L]) for L in range(33) if cnt[L] or ms[L]}
+        tab = np.zeros(6, np.float64)
+        self.ctx._chk(self.L.ka_ens_table_stats(self.h, _ptr(tab)))
+        out.update(zip(["table_count_ms", "table_write_ms", "table_host_ms", "table_entries", "table_chunks", "table_wait_host_ms"],
+                       tab.tolist()))
         return out
+
+    # ---- the POAR table as a file (poar_table_write / poar_table_read, lib/src/poar.c:203-325) ----
+    def table_size(self):
+        """(bytes of the POAR file, its entries)"""
+        b, n = C.c_longlong(), C.c_longlong()
+        self.ctx._chk(self.L.ka_ens_table_size(self.h, C.byref(b), C.byref(n)))
+        return b.value, n.value
+
+    def write_table(self, path):
+        """the file poar_table_write writes for these members (kalign_ensemble's save_poar_path), byte for byte"""
+        self.ctx._chk(self.L.ka_ens_table_write(self.h, os.fsencode(path)))
+
+    def table_image(self):
+        """the same bytes in memory"""
+        out = np.zeros(self.table_size()[0], np.uint8)
+        self.ctx._chk(self.L.ka_ens_table_image(self.h, _ptr(out), len(out)))
+        return out.tobytes()
 
 
 def _ens_create(self, lens, n_runs):
@@ -805,6 +847,33 @@ def _ens_create(self, lens, n_runs):
 
 
 Context.ensemble = _ens_create
+
+
+def _ens_from_table(self, lens, path=None, image=None):
+    """ka_ens_open_table: an Ensemble whose support comes from a POAR file (path) or its bytes (image)"""
+    if (path is None) == (image is None):
+        raise KalignAmdError("ensemble_from_table takes a path or an image")
+    return Ensemble(self, lens, table=path if image is None else bytes(image))
+
+
+Context.ensemble_from_table = _ens_from_table
+
+
+def check_table(image_or_path, lens):
+    """ka_poar_check_image: the reader's checks of a POAR file (its bytes, or its path) against sequences of these lengths,
+    on the host alone; returns (n_runs, entries) or raises with the cause"""
+    L = load_library()
+    if isinstance(image_or_path, (bytes, bytearray, memoryview, np.ndarray)):
+        data = bytes(image_or_path)
+    else:
+        with open(image_or_path, "rb") as f:
+            data = f.read()
+    img = np.frombuffer(data, np.uint8)
+    lens = np.ascontiguousarray(lens, np.int32)
+    r, n = C.c_int(), C.c_longlong()
+    if L.ka_poar_check_image(_ptr(img if len(img) else np.zeros(1, np.uint8)), len(img), len(lens), _ptr(lens), C.byref(r), C.byref(n)):
+        raise KalignAmdError(L.ka_last_error().decode())
+    return r.value, n.value
 
 
 CMP_COUNTS = ["ref_total_aligned_pairs", "ref_total_gap_pairs", "identical_aligned", "identical_gaps",

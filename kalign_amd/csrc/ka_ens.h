@@ -2,10 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 
 #define KA_ENS_MAX_RUNS 32
 #define KA_ENS_MAX_RES 4096        // residue index < 4096: the reference's POAR key ri << 20 | rj aliases from there on
 #define KA_ENS_STATS 10            // ka_ens_stats: see include/kalign_amd.h
+#define KA_ENS_TABLE_STATS 6       // ka_ens_table_stats
 #define KA_ENS_JCHUNK 16           // j per workgroup of the support walk (4 waves, one j at a time each)
 
 enum { KA_ENS_SCORE = 0, KA_ENS_CONF = 1, KA_ENS_COUNT = 2, KA_ENS_WRITE = 3 };
@@ -32,9 +34,33 @@ struct KaEnsArgs {
         const long long* pairOff;  // WRITE: [N * N] first slot of pair (i, j), relative to the row
         const long long* rowBase;  // WRITE: [N] first slot of row i, relative to this chunk
         int2* out;                 // WRITE: (element of i, element of j)
+        // the POAR table (ka_poar.hip): built from the members, or the source of support of a handle opened from one
+        uint2* entOut;             // table WRITE: (key = ri << 20 | rj, mask: bit k = member k holds the pair)
+        const long long* pairStart;// [N * (N - 1) / 2 + 1] first entry of pair (i, j), i < j, pairs in (i, j) order
+        const uint2* ent;          // the entries, keys ascending inside a pair
 };
+
+__device__ __forceinline__ int ens_wave_incl_scan(int v, int lane)
+{
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+                const int t = __shfl_up(v, o, 64);
+                if (lane >= o) v += t;
+        }
+        return v;
+}
+
+// index of pair (i, j), i < j, in the table's order (poar.c's pair_index)
+__host__ __device__ inline long long ka_poar_pair(int i, int j, int N) { return (long long)i * N - (long long)i * (i + 1) / 2 + (j - i - 1); }
 
 // ka_ens.hip
 void ka_ens_launch_walk(int mode, const KaEnsArgs& a, hipStream_t s);
 void ka_ens_launch_row_scan(const int* cnt, int N, long long* pairOff, long long* rowTot, int rows, hipStream_t s);
 void ka_ens_launch_conf(const KaEnsArgs& a, float* conf, float* colConf, hipStream_t s);
+// ka_poar.hip: the same modes and launch geometry as ka_ens_launch_walk
+void ka_poar_launch_table(int mode, const KaEnsArgs& a, hipStream_t s);       // COUNT / WRITE: the members' table, pair by pair
+void ka_poar_launch_level(int mode, const KaEnsArgs& a, hipStream_t s);       // COUNT / WRITE over a loaded table: the entries with
+                                                                              // popcount == level as candidates; level 0: every entry, as it is
+void ka_poar_launch_lookup(int mode, const KaEnsArgs& a, hipStream_t s);      // SCORE / CONF with support read from a loaded table
+// ka_poar.cpp: the checks of ka_poar_check_image; also fills the pairs' first entries (n_pairs + 1) when asked
+int ka_poar_parse(const uint8_t* image, long long nBytes, int numseq, const int* lens, int* nRuns, long long* entries, std::vector<long long>* pairStart);

@@ -20,16 +20,6 @@
 
 #define ENS_THREADS 256
 
-__device__ __forceinline__ int ens_wave_incl_scan(int v, int lane)
-{
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(v, o, 64);
-                if (lane >= o) v += t;
-        }
-        return v;
-}
-
 template <int MODE, int RM>
 __global__ __launch_bounds__(ENS_THREADS) void ens_walk(KaEnsArgs a)
 {

@@ -19,13 +19,15 @@ def select(scores):
     return best
 
 
-def finish_ensemble(ctx, member_rows, letters, min_support=0, rerun_refined=None):
+def finish_ensemble(ctx, member_rows, letters, min_support=0, rerun_refined=None, save_poar_path=None):
     """member_rows[k]: the rows of member k (bytes / str, one per sequence, input order); letters: the sequences.
     min_support > 0: the consensus at that threshold, no selection (as kalign_ensemble with an explicit min_support).
     min_support == 0: the consensus at auto_min_support(n_runs) wins if it scores higher than the selected member; else,
     when rerun_refined is given, rerun_refined(best_k) must return member best_k's rows re-run with refine mode 2
     (KALIGN_REFINE_CONFIDENT, the member's gap penalties and tree noise -- whose multipliers come from the caller's RNG)
     and they replace the member if they score higher.
+    save_poar_path: the members' POAR table goes to that file after the member scores, where kalign_ensemble writes it
+    (ensemble.c:349-355; poar_table_write's bytes); consensus_from_poar reads it back.  Nothing else changes.
     Returns a dict: rows (bytes), residue_confidence (float32[n, width]), column_confidence (float32[width]), scores
     (per member), best_k, use_consensus, consensus_score (None when not computed), refined_score (None when not run),
     refined (whether the refined rows were kept)."""
@@ -40,6 +42,8 @@ def finish_ensemble(ctx, member_rows, letters, min_support=0, rerun_refined=None
             ens.add_member(k, rows)
         scores = [ens.score(rows)[1] for rows in member_rows]
         best_k = select(scores)
+        if save_poar_path is not None:
+            ens.write_table(save_poar_path)
         out = dict(scores=scores, best_k=best_k, use_consensus=False, consensus_score=None, refined_score=None, refined=False)
         chosen = [bytes(r.encode() if isinstance(r, str) else r) for r in member_rows[best_k]]
         if min_support > 0:
@@ -61,5 +65,21 @@ def finish_ensemble(ctx, member_rows, letters, min_support=0, rerun_refined=None
         out["residue_confidence"], out["column_confidence"] = ens.confidence(chosen)
         out["stats"] = ens.stats()
         return out
+    finally:
+        ens.close()
+
+
+def consensus_from_poar(ctx, letters, poar_path, min_support):
+    """kalign_consensus_from_poar (ensemble.c:500-543): the consensus alignment at min_support and its confidences from a
+    saved POAR table, no members at hand.  letters: the sequences, in the order of the run that wrote the table.
+    Returns a dict: rows (bytes), residue_confidence, column_confidence, n_runs (the file's), stats."""
+    if int(min_support) < 1:
+        raise KalignAmdError("min_support must be >= 1")
+    letters = [x.encode() if isinstance(x, str) else bytes(x) for x in letters]
+    ens = ctx.ensemble_from_table(residue_lens(letters), path=poar_path)
+    try:
+        rows = ens.consensus(letters, int(min_support))
+        res, col = ens.confidence(rows)
+        return dict(rows=rows, residue_confidence=res, column_confidence=col, n_runs=ens.n_runs, stats=ens.stats())
     finally:
         ens.close()
