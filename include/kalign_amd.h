@@ -522,6 +522,17 @@ int  ka_ens_stats(ka_ens* e, double* stats_out, long long* level_counts_out, dou
  *                            numseq different from the caller's; n_alignments outside 1..32; fewer or more bytes than the counts
  *                            imply; a key with ri >= lens[i] or rj >= lens[j]; keys of a pair not strictly ascending; a mask that is
  *                            0 or has a bit at or above n_alignments.  n_runs_out / entries_out (optional) on success.
+ * Two operations make new tables from tables, on the device (poar_merge / poar_select, ka_poar.hip).  An operand is a handle
+ * opened from a table or a handle with every member added (its table is then built in device memory in full first; when that
+ * allocation fails the error says so); operands are not modified and stay usable whether the call succeeds or not.  *out is a new
+ * handle like one from ka_ens_open_table_image -- everything above works on it, ka_ens_add_member fails -- and is untouched on
+ * failure.  On it ka_ens_table_stats gives the device ms of the operation's count and write passes in [0] and [1] and its
+ * entries in [3].
+ *   ka_ens_merge             the union of two tables of the same sequences (same context, numseq and lens): a's members keep their
+ *                            bits, b's member k becomes member n_runs(a) + k; n_runs = n_runs(a) + n_runs(b) <= 32.  The table of
+ *                            members 0..s-1 merged with the table of members s..R-1 is, byte for byte, the table of all R members.
+ *   ka_ens_select            the table of members[0..n) of e, in that order (distinct indices below n_runs(e), 1 <= n <= n_runs(e)):
+ *                            new member t is old member members[t]; an entry none of them holds is dropped.
  */
 int  ka_ens_table_size(ka_ens* e, long long* bytes_out, long long* entries_out);
 int  ka_ens_table_write(ka_ens* e, const char* path);
@@ -531,6 +542,8 @@ int  ka_ens_open_table_image(ka_ctx* ctx, int numseq, const int* lens, const uin
 int  ka_ens_n_runs(ka_ens* e);
 int  ka_ens_table_stats(ka_ens* e, double* out6);
 int  ka_poar_check_image(const uint8_t* image, long long n_bytes, int numseq, const int* lens, int* n_runs_out, long long* entries_out);
+int  ka_ens_merge(ka_ens* a, ka_ens* b, ka_ens** out);
+int  ka_ens_select(ka_ens* e, const int* members, int n, ka_ens** out);
 
 /* ---- scoring an alignment against a reference alignment (ka_cmp.hip, ka_cmp.cpp) -------------------------------------------
  * kalign_msa_compare, kalign_msa_compare_detailed and kalign_msa_compare_with_mask (lib/src/msa_cmp.c) on the device.  Both

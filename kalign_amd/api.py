@@ -58,7 +58,7 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_multi_consistency", "ka_multi_tree_run", "ka_multi_paths_size", "ka_multi_download", "ka_multi_ctx", "ka_multi_adopt",
            "ka_tree_adopt_alignment", "ka_ens_create", "ka_ens_destroy", "ka_ens_add_member", "ka_ens_score_rows", "ka_ens_consensus",
            "ka_ens_confidence", "ka_ens_stats", "ka_ens_table_size", "ka_ens_table_write", "ka_ens_table_image", "ka_ens_open_table",
-           "ka_ens_open_table_image", "ka_ens_n_runs", "ka_ens_table_stats", "ka_poar_check_image", "ka_cmp_create", "ka_cmp_destroy", "ka_cmp_set_mask", "ka_cmp_score",
+           "ka_ens_open_table_image", "ka_ens_n_runs", "ka_ens_table_stats", "ka_poar_check_image", "ka_ens_merge", "ka_ens_select", "ka_cmp_create", "ka_cmp_destroy", "ka_cmp_set_mask", "ka_cmp_score",
            "ka_cmp_score_batch", "ka_cmp_stats"]
 
 
@@ -198,6 +198,8 @@ def load_library():
     L.ka_ens_open_table_image.argtypes = [vp, C.c_int, vp, vp, C.c_longlong, C.POINTER(vp)]
     L.ka_ens_n_runs.argtypes = [vp]
     L.ka_ens_table_stats.argtypes = [vp, vp]
+    L.ka_ens_merge.argtypes = [vp, vp, C.POINTER(vp)]
+    L.ka_ens_select.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
     L.ka_poar_check_image.argtypes = [vp, C.c_longlong, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
     L.ka_cmp_create.argtypes = [vp, C.c_int, vp, vp, C.c_longlong, C.c_int, C.POINTER(vp)]
     L.ka_cmp_destroy.argtypes = [vp]
@@ -839,6 +841,31 @@ class Ensemble(_CtxChild):
         out = np.zeros(self.table_size()[0], np.uint8)
         self.ctx._chk(self.L.ka_ens_table_image(self.h, _ptr(out), len(out)))
         return out.tobytes()
+
+    # ---- new tables from tables (ka_ens_merge / ka_ens_select): the operands stay as they are, the result is a new Ensemble ----
+    def _derived(self, h):
+        e = object.__new__(Ensemble)
+        e.ctx, e.L, e.lens, e.n = self.ctx, self.L, self.lens, self.n
+        e._adopt(self.ctx, h)
+        e.n_runs = int(self.L.ka_ens_n_runs(h))
+        return e
+
+    def merge(self, other):
+        """a table-backed Ensemble of this one's members followed by other's (member k of other becomes n_runs + k): the
+        union of the two POAR tables.  Both hold the same sequences in one context, every member added or opened from a table."""
+        if not isinstance(other, Ensemble):
+            raise KalignAmdError("merge takes another Ensemble")
+        h = C.c_void_p()
+        self.ctx._chk(self.L.ka_ens_merge(self.h, other.h, C.byref(h)))
+        return self._derived(h)
+
+    def select(self, members):
+        """a table-backed Ensemble of members[0], members[1], ... of this one, in that order (distinct indices); the
+        entries of the table that none of them holds are dropped"""
+        m = np.ascontiguousarray(list(members), np.int32)
+        h = C.c_void_p()
+        self.ctx._chk(self.L.ka_ens_select(self.h, _ptr(m if len(m) else np.zeros(1, np.int32)), len(m), C.byref(h)))
+        return self._derived(h)
 
 
 def _ens_create(self, lens, n_runs):

@@ -181,6 +181,7 @@ double ms_since(std::chrono::steady_clock::time_point t0)
 } // namespace
 
 struct ka_ens {
+        ka_ctx* ctx = nullptr;
         int device = 0;
         hipStream_t stream = nullptr;
         KaSeqSet q;
@@ -301,6 +302,11 @@ struct ka_ens {
         int table_count(long long* entries);
         int table_emit(Sink* sink);
         int load_table(const uint8_t* image, long long nBytes);
+        struct TabRef { const long long* pairStart; const uint2* ent; long long entries; };
+        int pair_starts(int b0, int b1, const std::vector<long long>& rowTot, long long* run, long long* pairStart);
+        int table_on_device(DevBuf<long long>& ps, DevBuf<uint2>& ent, TabRef* t);
+        template <class Launch>
+        int derive_table(const char* who, KaEnsArgs a, Launch launch);
 };
 
 // rows i per count pass: the pair counts and offsets of a block are rows x N entries
@@ -561,10 +567,87 @@ int ka_ens::load_table(const uint8_t* image, long long nBytes)
         return KA_OK;
 }
 
+// rows b0 .. b1 as count_rows left them (dPairOff, rowTot): the first entry of each of their pairs into pairStart, where *run
+// entries lie before row b0; the rows' own first entries stay in dRowBase[0], and *run moves on to row b1
+int ka_ens::pair_starts(int b0, int b1, const std::vector<long long>& rowTot, long long* run, long long* pairStart)
+{
+        std::vector<long long> base((size_t)(b1 - b0));
+        for (int i = b0; i < b1; i++) { base[i - b0] = *run; *run += rowTot[i - b0]; }
+        if (dRowBase[0].alloc(base.size())) return fail("ka_ens: out of device memory");
+        HIPCHK(hipMemcpyAsync(dRowBase[0].p, base.data(), sizeof(long long) * base.size(), hipMemcpyHostToDevice, stream));
+        ka_poar_launch_pair_start(dPairOff.p, dRowBase[0].p, b0, b1, q.N, pairStart, stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        return KA_OK;
+}
+
+// the handle's table where a kernel can read it: a table-backed handle's own; the members' table built into ps / ent in full
+// (the table passes of table_emit, without the chunked hand-over to the host)
+int ka_ens::table_on_device(DevBuf<long long>& ps, DevBuf<uint2>& ent, TabRef* t)
+{
+        if (fromTable) { *t = TabRef{ dPairStart.p, dEnt.p, tabEntries }; return KA_OK; }
+        long long total = 0;
+        if (table_count(&total)) return KA_FAIL;
+        const int N = q.N, rb = ens_count_block(N);
+        const long long nPairs = (long long)N * (N - 1) / 2;
+        if (ps.alloc((size_t)nPairs + 1) || ent.alloc((size_t)std::max(total, 1LL)))
+                return fail("ka_ens: out of device memory (the table of a member-backed operand, " + std::to_string(total) + " entries)");
+        KaEnsArgs a = args();
+        std::vector<long long> rowTot;
+        long long run = 0;
+        double ms = 0.0;
+        for (int b0 = 0; b0 < N; b0 += rb) {
+                const int b1 = std::min(N, b0 + rb);
+                if (count_rows(a, b0, b1, [&](const KaEnsArgs& x) { ka_poar_launch_table(KA_ENS_COUNT, x, stream); }, rowTot, nullptr, &ms)) return KA_FAIL;
+                if (pair_starts(b0, b1, rowTot, &run, ps.p)) return KA_FAIL;
+                KaEnsArgs w = a;
+                w.pairOff = dPairOff.p; w.rowBase = dRowBase[0].p; w.entOut = ent.p;
+                ka_poar_launch_table(KA_ENS_WRITE, w, stream);
+                HIPCHK(hipGetLastError());
+        }
+        if (run != total) return fail("ka_ens: the table's counts changed between two passes");
+        HIPCHK(hipMemcpyAsync(ps.p + nPairs, &run, sizeof(long long), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        *t = TabRef{ ps.p, ent.p, total };
+        return KA_OK;
+}
+
+// this handle's table from launch(COUNT / WRITE, args): a is ready but for what the passes fill in.  COUNT gives every pair its
+// size, so the pairs' first entries are known before the one WRITE pass, which reads them (a.outStart) as the table's reader will.
+template <class Launch>
+int ka_ens::derive_table(const char* who, KaEnsArgs a, Launch launch)
+{
+        const int N = q.N, rb = ens_count_block(N);
+        const long long nPairs = (long long)N * (N - 1) / 2;
+        if (dPairStart.alloc((size_t)nPairs + 1)) return fail(std::string(who) + ": out of device memory (the table)");
+        std::fill_n(tab, KA_ENS_TABLE_STATS, 0.0);
+        std::vector<long long> rowTot;
+        long long run = 0;
+        for (int b0 = 0; b0 < N; b0 += rb) {
+                const int b1 = std::min(N, b0 + rb);
+                if (count_rows(a, b0, b1, [&](const KaEnsArgs& x) { launch(KA_ENS_COUNT, x); }, rowTot, nullptr, &tab[0])) return KA_FAIL;
+                if (pair_starts(b0, b1, rowTot, &run, dPairStart.p)) return KA_FAIL;
+        }
+        if (dEnt.alloc((size_t)std::max(run, 1LL))) return fail(std::string(who) + ": out of device memory (the table, " + std::to_string(run) + " entries)");
+        HIPCHK(hipMemcpyAsync(dPairStart.p + nPairs, &run, sizeof(long long), hipMemcpyHostToDevice, stream));
+        a.i0 = 0; a.i1 = N;
+        a.outStart = dPairStart.p; a.entOut = dEnt.p;
+        HIPCHK(hipEventRecord(ev0, stream));
+        launch(KA_ENS_WRITE, a);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev1, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        tab[1] = evMs();
+        tabEntries = run;
+        tab[3] = (double)run;
+        return KA_OK;
+}
+
 // a handle on ctx's device and stream for these sequences, without a source of support yet
 static int ens_new(const char* who, ka_ctx* ctx, int numseq, const int* lens, std::unique_ptr<ka_ens>& e)
 {
         e.reset(new ka_ens);
+        e->ctx = ctx;
         if (ka_ctx_device_stream(ctx, &e->device, &e->stream)) return fail(std::string(who) + ": bad context");
         HIPCHK(hipSetDevice(e->device));
         if (e->q.init(who, numseq, lens, KA_ENS_MAX_RES,
@@ -755,6 +838,85 @@ extern "C" int ka_ens_open_table(ka_ctx* ctx, int numseq, const int* lens, const
         if (bad) return fail(std::string("ka_ens_open_table: reading ") + path + " failed");
         const uint8_t none = 0;                                           // (an empty file: the reader says so)
         return ka_ens_open_table_image(ctx, numseq, lens, image.empty() ? &none : image.data(), (long long)image.size(), out);
+}
+
+// a table-backed handle of n_runs members for the sequences of `like`, its table still to come (derive_table)
+static int ens_new_result(const char* who, const ka_ens* like, int n_runs, std::unique_ptr<ka_ens>& o)
+{
+        if (ens_new(who, like->ctx, like->q.N, like->q.lens.data(), o)) return KA_FAIL;
+        o->R = n_runs;
+        o->W.assign(n_runs, 0);
+        o->fromTable = true;
+        return KA_OK;
+}
+
+extern "C" int ka_ens_merge(ka_ens* a, ka_ens* b, ka_ens** out)
+{
+        const char* who = "ka_ens_merge";
+        if (!a || !b || !out) return fail("ka_ens_merge: bad arguments (a NULL handle or a NULL out)");
+        if (a->ctx != b->ctx) return fail("ka_ens_merge: the two handles belong to different contexts");
+        if (a->q.N != b->q.N)
+                return fail("ka_ens_merge: numseq " + std::to_string(a->q.N) + " in the first handle, " + std::to_string(b->q.N) + " in the second");
+        for (int s = 0; s < a->q.N; s++)
+                if (a->q.lens[s] != b->q.lens[s])
+                        return fail("ka_ens_merge: sequence " + std::to_string(s) + " has " + std::to_string(a->q.lens[s]) + " residues in the first handle, " +
+                                    std::to_string(b->q.lens[s]) + " in the second");
+        if (a->R + b->R > KA_ENS_MAX_RUNS)
+                return fail("ka_ens_merge: " + std::to_string(a->R) + " + " + std::to_string(b->R) + " members exceed " + std::to_string(KA_ENS_MAX_RUNS) +
+                            " (one bit per member in the reference's POAR table)");
+        HIPCHK(hipSetDevice(a->device));
+        DevBuf<long long> psA, psB;
+        DevBuf<uint2> entA, entB;
+        ka_ens::TabRef ta{}, tb{};
+        std::unique_ptr<ka_ens> o;
+        int rc = a->table_on_device(psA, entA, &ta);
+        if (!rc) rc = b->table_on_device(psB, entB, &tb);
+        if (!rc) rc = ens_new_result(who, a, a->R + b->R, o);
+        if (!rc) {
+                KaEnsArgs x = o->args();
+                x.pairStart = ta.pairStart; x.ent = ta.ent;
+                x.pairStartB = tb.pairStart; x.entB = tb.ent;
+                x.shift = a->R;
+                hipStream_t s = o->stream;
+                rc = o->derive_table(who, x, [s](int mode, const KaEnsArgs& y) { ka_poar_launch_merge(mode, y, s); });
+        }
+        psA.release(); psB.release(); entA.release(); entB.release();
+        if (rc) return rc;
+        *out = o.release();
+        return KA_OK;
+}
+
+extern "C" int ka_ens_select(ka_ens* e, const int* members, int n, ka_ens** out)
+{
+        const char* who = "ka_ens_select";
+        if (!e || !members || !out) return fail("ka_ens_select: bad arguments (a NULL handle, NULL members or a NULL out)");
+        if (n < 1 || n > e->R) return fail("ka_ens_select: n = " + std::to_string(n) + " outside 1.." + std::to_string(e->R) + " (the handle's n_runs)");
+        unsigned seen = 0;
+        for (int t = 0; t < n; t++) {
+                if (members[t] < 0 || members[t] >= e->R)
+                        return fail("ka_ens_select: member index " + std::to_string(members[t]) + " out of range 0.." + std::to_string(e->R - 1));
+                if (seen >> members[t] & 1u) return fail("ka_ens_select: member " + std::to_string(members[t]) + " given twice");
+                seen |= 1u << members[t];
+        }
+        HIPCHK(hipSetDevice(e->device));
+        DevBuf<long long> ps;
+        DevBuf<uint2> ent;
+        ka_ens::TabRef te{};
+        std::unique_ptr<ka_ens> o;
+        int rc = e->table_on_device(ps, ent, &te);
+        if (!rc) rc = ens_new_result(who, e, n, o);
+        if (!rc) {
+                KaEnsArgs x = o->args();
+                x.pairStart = te.pairStart; x.ent = te.ent;
+                x.nSel = n;
+                for (int t = 0; t < n; t++) x.sel[t] = (unsigned char)members[t];
+                hipStream_t s = o->stream;
+                rc = o->derive_table(who, x, [s](int mode, const KaEnsArgs& y) { ka_poar_launch_select(mode, y, s); });
+        }
+        ps.release(); ent.release();
+        if (rc) return rc;
+        *out = o.release();
+        return KA_OK;
 }
 
 extern "C" int ka_ens_table_stats(ka_ens* e, double* out6)

@@ -38,6 +38,13 @@ struct KaEnsArgs {
         uint2* entOut;             // table WRITE: (key = ri << 20 | rj, mask: bit k = member k holds the pair)
         const long long* pairStart;// [N * (N - 1) / 2 + 1] first entry of pair (i, j), i < j, pairs in (i, j) order
         const uint2* ent;          // the entries, keys ascending inside a pair
+        // the table algebra (poar_merge, poar_select): a new table from ent (and entB), its pairs' first entries known after COUNT
+        const long long* pairStartB; // merge: the second table, whose member bits go above the first's shift bits
+        const uint2* entB;
+        int shift;                 // merge: members of the first table
+        int nSel;                  // select: members kept; new bit t = old bit sel[t]
+        unsigned char sel[KA_ENS_MAX_RUNS];
+        const long long* outStart; // merge / select WRITE: [N * (N - 1) / 2 + 1] first entry of pair (i, j) in entOut
 };
 
 __device__ __forceinline__ int ens_wave_incl_scan(int v, int lane)
@@ -62,5 +69,9 @@ void ka_poar_launch_table(int mode, const KaEnsArgs& a, hipStream_t s);       //
 void ka_poar_launch_level(int mode, const KaEnsArgs& a, hipStream_t s);       // COUNT / WRITE over a loaded table: the entries with
                                                                               // popcount == level as candidates; level 0: every entry, as it is
 void ka_poar_launch_lookup(int mode, const KaEnsArgs& a, hipStream_t s);      // SCORE / CONF with support read from a loaded table
+void ka_poar_launch_merge(int mode, const KaEnsArgs& a, hipStream_t s);       // COUNT / WRITE: the union of two tables, the second's bits shifted
+void ka_poar_launch_select(int mode, const KaEnsArgs& a, hipStream_t s);      // COUNT / WRITE: a table with the member bits sel[], emptied entries dropped
+// pairStart[pair (i, j)] = rowBase[i - i0] + pairOff[(i - i0) * N + j] for rows i0 .. i1: a counted block's offsets in the table's own layout
+void ka_poar_launch_pair_start(const long long* pairOff, const long long* rowBase, int i0, int i1, int N, long long* pairStart, hipStream_t s);
 // ka_poar.cpp: the checks of ka_poar_check_image; also fills the pairs' first entries (n_pairs + 1) when asked
 int ka_poar_parse(const uint8_t* image, long long nBytes, int numseq, const int* lens, int* nRuns, long long* entries, std::vector<long long>* pairStart);

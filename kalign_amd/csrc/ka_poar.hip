@@ -10,6 +10,9 @@
 //   poar_level   from a loaded table: the entries of pair (i, j) whose popcount is the level, compacted in table order into
 //                the candidates (element of i, element of j) the greedy takes; level 0: every entry as it is
 //   poar_lookup  SCORE / CONF of an alignment X with support = popcount of the entry (ri, rj), found by bisection
+//   poar_merge   two tables into one (ka_ens_merge): per pair the sorted union of the keys, the second table's member bits
+//                above the first's
+//   poar_select  a table with some of its member bits, in a new order (ka_ens_select); an entry that keeps none is dropped
 #include <hip/hip_runtime.h>
 #include "ka_ens.h"
 #include "ka_msa.h"
@@ -183,6 +186,121 @@ __global__ __launch_bounds__(POAR_THREADS) void poar_lookup(KaEnsArgs a)
         }
 }
 
+// first index in [lo, hi) whose key is >= key (hi when there is none)
+__device__ __forceinline__ long long poar_lower_bound(const uint2* ent, long long lo, long long hi, unsigned key)
+{
+        while (lo < hi) {
+                const long long mid = (lo + hi) >> 1;
+                if (ent[mid].x < key) lo = mid + 1;
+                else hi = mid;
+        }
+        return lo;
+}
+
+// The union of the tables A (a.pairStart / a.ent, a.shift members) and B (a.pairStartB / a.entB) of one set of sequences, B's
+// member bits above A's.  A wave takes a pair; its lanes take A's entries in tiles of 64, then B's.  An entry's slot in the
+// sorted union is its own index plus the other list's entries below its key (a bisection) minus the keys below it that both
+// lists hold -- a ballot prefix inside the tile and a carry across tiles.  A shared key is written by the A side alone, with
+// both masks; the B side skips it.  COUNT needs the A side only: |A| + |B| - |A and B|.
+template <int MODE>
+__global__ __launch_bounds__(POAR_THREADS) void poar_merge(KaEnsArgs a)
+{
+        const int nJC = (a.N + KA_ENS_JCHUNK - 1) / KA_ENS_JCHUNK;
+        const int i = a.i0 + (int)blockIdx.x / nJC;
+        const int j0 = ((int)blockIdx.x % nJC) * KA_ENS_JCHUNK;
+        const int j1 = min(a.N, j0 + KA_ENS_JCHUNK);
+        if (j1 <= i + 1) return;
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        const unsigned long long below = (1ull << lane) - 1ull;
+        for (int j = max(j0, i + 1) + wave; j < j1; j += POAR_THREADS / 64) {
+                const long long p = ka_poar_pair(i, j, a.N);
+                const long long a0 = a.pairStart[p], a1 = a.pairStart[p + 1];
+                const long long b0 = a.pairStartB[p], b1 = a.pairStartB[p + 1];
+                const long long base = MODE == KA_ENS_WRITE ? a.outStart[p] : 0;
+                long long shared = 0;                                // keys of both lists in the tiles before this one
+                for (long long t = a0; t < a1; t += 64) {
+                        const long long x = t + lane;
+                        uint2 e = make_uint2(0u, 0u);
+                        long long lb = b0;
+                        unsigned mb = 0;
+                        if (x < a1) {
+                                e = a.ent[x];
+                                lb = poar_lower_bound(a.entB, b0, b1, e.x);
+                                if (lb < b1) {
+                                        const uint2 f = a.entB[lb];
+                                        if (f.x == e.x) mb = f.y;            // (a stored mask is never 0)
+                                }
+                        }
+                        const unsigned long long bal = __ballot(mb != 0);
+                        if (MODE == KA_ENS_WRITE && x < a1)
+                                a.entOut[base + (x - a0) + (lb - b0) - shared - __popcll(bal & below)] = make_uint2(e.x, e.y | mb << a.shift);
+                        shared += __popcll(bal);
+                }
+                if (MODE == KA_ENS_COUNT) {
+                        if (lane == 0) a.cnt[(long long)(i - a.i0) * a.N + j] = (int)((a1 - a0) + (b1 - b0) - shared);
+                        continue;
+                }
+                shared = 0;
+                for (long long t = b0; t < b1; t += 64) {
+                        const long long y = t + lane;
+                        uint2 e = make_uint2(0u, 0u);
+                        long long la = a0;
+                        bool both = false;
+                        if (y < b1) {
+                                e = a.entB[y];
+                                la = poar_lower_bound(a.ent, a0, a1, e.x);
+                                both = la < a1 && a.ent[la].x == e.x;
+                        }
+                        const unsigned long long bal = __ballot(both);
+                        if (y < b1 && !both)
+                                a.entOut[base + (y - b0) + (la - a0) - shared - __popcll(bal & below)] = make_uint2(e.x, e.y << a.shift);
+                        shared += __popcll(bal);
+                }
+        }
+}
+
+// A table's entries with the member bits a.sel[0 .. nSel) as bits 0 .. nSel - 1, the entries that keep none of them dropped:
+// poar_level's ballot compaction with this predicate, table to table.
+template <int MODE>
+__global__ __launch_bounds__(POAR_THREADS) void poar_select(KaEnsArgs a)
+{
+        const int nJC = (a.N + KA_ENS_JCHUNK - 1) / KA_ENS_JCHUNK;
+        const int i = a.i0 + (int)blockIdx.x / nJC;
+        const int j0 = ((int)blockIdx.x % nJC) * KA_ENS_JCHUNK;
+        const int j1 = min(a.N, j0 + KA_ENS_JCHUNK);
+        if (j1 <= i + 1) return;
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        for (int j = max(j0, i + 1) + wave; j < j1; j += POAR_THREADS / 64) {
+                const long long p = ka_poar_pair(i, j, a.N);
+                const long long e0 = a.pairStart[p], e1 = a.pairStart[p + 1];
+                long long base = MODE == KA_ENS_WRITE ? a.outStart[p] : 0;
+                int cntj = 0;
+                for (long long b = e0; b < e1; b += 64) {
+                        const long long x = b + lane;
+                        uint2 e = make_uint2(0u, 0u);
+                        if (x < e1) e = a.ent[x];
+                        unsigned m = 0;
+                        for (int t = 0; t < a.nSel; t++) m |= (e.y >> a.sel[t] & 1u) << t;
+                        if (MODE == KA_ENS_COUNT) { cntj += m != 0; continue; }
+                        const unsigned long long bal = __ballot(m != 0);
+                        if (m) a.entOut[base + __popcll(bal & ((1ull << lane) - 1ull))] = make_uint2(e.x, m);
+                        base += __popcll(bal);
+                }
+                if (MODE == KA_ENS_COUNT) {
+                        const long long t = ka_msa_wave_sum(cntj);
+                        if (lane == 0) a.cnt[(long long)(i - a.i0) * a.N + j] = (int)t;
+                }
+        }
+}
+
+// a counted block of rows in the table's own layout: the first entry of every pair (i, j), i0 <= i < i1
+__global__ __launch_bounds__(POAR_THREADS) void poar_pair_start(const long long* pairOff, const long long* rowBase, int i0, int N, long long* pairStart)
+{
+        const int i = i0 + (int)blockIdx.x;
+        for (int j = i + 1 + (int)threadIdx.x; j < N; j += POAR_THREADS)
+                pairStart[ka_poar_pair(i, j, N)] = rowBase[i - i0] + pairOff[(long long)(i - i0) * N + j];
+}
+
 static unsigned poar_blocks(const KaEnsArgs& a)
 {
         const int nJC = (a.N + KA_ENS_JCHUNK - 1) / KA_ENS_JCHUNK;
@@ -210,6 +328,27 @@ void ka_poar_launch_level(int mode, const KaEnsArgs& a, hipStream_t s)
         if (!blocks) return;
         if (mode == KA_ENS_COUNT) poar_level<KA_ENS_COUNT><<<blocks, POAR_THREADS, 0, s>>>(a);
         else poar_level<KA_ENS_WRITE><<<blocks, POAR_THREADS, 0, s>>>(a);
+}
+
+void ka_poar_launch_merge(int mode, const KaEnsArgs& a, hipStream_t s)
+{
+        const unsigned blocks = poar_blocks(a);
+        if (!blocks) return;
+        if (mode == KA_ENS_COUNT) poar_merge<KA_ENS_COUNT><<<blocks, POAR_THREADS, 0, s>>>(a);
+        else poar_merge<KA_ENS_WRITE><<<blocks, POAR_THREADS, 0, s>>>(a);
+}
+
+void ka_poar_launch_select(int mode, const KaEnsArgs& a, hipStream_t s)
+{
+        const unsigned blocks = poar_blocks(a);
+        if (!blocks) return;
+        if (mode == KA_ENS_COUNT) poar_select<KA_ENS_COUNT><<<blocks, POAR_THREADS, 0, s>>>(a);
+        else poar_select<KA_ENS_WRITE><<<blocks, POAR_THREADS, 0, s>>>(a);
+}
+
+void ka_poar_launch_pair_start(const long long* pairOff, const long long* rowBase, int i0, int i1, int N, long long* pairStart, hipStream_t s)
+{
+        if (i1 > i0) poar_pair_start<<<i1 - i0, POAR_THREADS, 0, s>>>(pairOff, rowBase, i0, N, pairStart);
 }
 
 void ka_poar_launch_lookup(int mode, const KaEnsArgs& a, hipStream_t s)

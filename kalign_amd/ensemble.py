@@ -83,3 +83,37 @@ def consensus_from_poar(ctx, letters, poar_path, min_support):
         return dict(rows=rows, residue_confidence=res, column_confidence=col, n_runs=ens.n_runs, stats=ens.stats())
     finally:
         ens.close()
+
+
+def extend_poar(ctx, letters, poar_path, member_rows, save_poar_path=None, min_support=0):
+    """A saved POAR table grown by new members, the old members not run again: the table of poar_path merged with the
+    table of member_rows (Ensemble.merge), the new members numbered after the old ones as kalign_ensemble numbers member k.
+    letters: the sequences, in the order of the run that wrote the table; save_poar_path: the merged table goes to that
+    file.  The new members are scored against the merged table (the old members' rows are in no table, so no member is
+    selected); the consensus is taken at min_support, or at auto_min_support(n_runs) of the merged table when it is 0.
+    Returns a dict: rows (bytes), residue_confidence, column_confidence, n_runs (old and new), n_old, scores (of the new
+    members), stats."""
+    if len(member_rows) < 1:
+        raise KalignAmdError("an ensemble needs members")
+    if int(min_support) < 0:
+        raise KalignAmdError("min_support must be >= 0")
+    letters = [x.encode() if isinstance(x, str) else bytes(x) for x in letters]
+    lens = residue_lens(letters)
+    old = new = merged = None
+    try:
+        old = ctx.ensemble_from_table(lens, path=poar_path)
+        new = ctx.ensemble(lens, len(member_rows))
+        for k, rows in enumerate(member_rows):
+            new.add_member(k, rows)
+        merged = old.merge(new)
+        if save_poar_path is not None:
+            merged.write_table(save_poar_path)
+        scores = [merged.score(rows)[1] for rows in member_rows]
+        rows = merged.consensus(letters, int(min_support) if min_support > 0 else auto_min_support(merged.n_runs))
+        res, col = merged.confidence(rows)
+        return dict(rows=rows, residue_confidence=res, column_confidence=col, n_runs=merged.n_runs, n_old=old.n_runs,
+                    scores=scores, stats=merged.stats())
+    finally:
+        for e in (merged, new, old):
+            if e is not None:
+                e.close()
