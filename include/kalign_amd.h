@@ -227,6 +227,25 @@ int ka_debug_set_hooks(ka_ctx* ctx, int hooks);
 /* Tools and tests: the KA_* environment switches (experiments and measurements; none is needed in production) are read
    once, at ka_ctx_create.  This reads them again and rebuilds the launch plan of the uploaded job. */
 int ka_debug_reload_env(ka_ctx* ctx);
+/* Tests and tools, no GPU and no context: the launch plan the library would make for a job -- task preparation and planner exactly as
+ * ka_tree_upload runs them, on a device of n_cus compute units, with ka_ctx_set_shared(shared), a consistency table of cons_K anchors
+ * (0: none), the ka_debug_set_hooks bits `hooks`, and, where task_ids is not NULL, for that subset of the tasks as ka_tree_plan_tasks
+ * plans it.  The KA_* switches are read from the environment on every call.  The plan comes back flattened:
+ *   scalars[16]            0 levels, 1 entries of the block table, 2 workgroups one task may use, 3 trees, 4 first level of the chained
+ *                          launch (-1: none), 5 first level of the queued launch (-1: none), 6 / 7 the queue's list in the block table
+ *                          (first entry, entries), 8 overlapping launches, 9 CUs kept for the head of the chain, 10 / 11 the chained
+ *                          launch's table in the block table (first entry, entries; 0, 0 without one), 12 .. 15 zero
+ *   per_task[7 * n_tasks]  parent, chain_need, is_root, wait_mult, qa, qb of every task, then whether it is a spine task
+ *   blocks[2 * entries]    the block table, (task, member | cluster size << 8 | flags) per workgroup: one table per level, the queue's
+ *                          list, the chained launch's table
+ *   blocks_off[levels + 1] first entry of every level's table;  level_lean[levels]: its launch kind (0 eight waves, 1 lean, 2 half)
+ * blocks_off and level_lean must hold n_tasks + 1 and n_tasks values.  With more than blocks_cap entries the call fails after it has
+ * filled scalars: call again with room for scalars[1] entries. */
+int ka_debug_plan(int numseq, const int* lens, int n_tasks, const int* tasks_abc, int n_cus, int shared, int cons_K, int hooks,
+                  const int* task_ids, int n_ids,
+                  int* scalars, int* per_task, int* blocks, int blocks_cap, int* blocks_off, int* level_lean);
+/* ... and, flattened in the same way, the plan a context holds after ka_tree_upload, ka_tree_plan_tasks or ka_debug_reload_env. */
+int ka_debug_ctx_plan(ka_ctx* ctx, int* scalars, int* per_task, int* blocks, int blocks_cap, int* blocks_off, int* level_lean);
 /* Debug: 64 breadcrumb words written by workgroup 0 (context created with KA_TRACE=1 in the
    environment); readable while a kernel is still running. */
 int ka_debug_trace(ka_ctx* ctx, int* out64);

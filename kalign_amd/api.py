@@ -43,7 +43,7 @@ class TaskRec(C.Structure):
 DIST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
 
 EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_consistency_part",
-           "ka_tree_consistency_part_range", "ka_tree_consistency_maps_dev", "ka_debug_set_hooks", "ka_debug_reload_env", "ka_debug_tp_launches", "ka_debug_kmeans_level", "ka_debug_kmeans_host", "ka_ctx_fallback_runs", "ka_ctx_helped_tasks", "ka_ctx_create", "ka_ctx_destroy", "ka_ctx_set_stream", "ka_ctx_set_shared", "ka_last_error", "ka_abi_version",
+           "ka_tree_consistency_part_range", "ka_tree_consistency_maps_dev", "ka_debug_set_hooks", "ka_debug_reload_env", "ka_debug_plan", "ka_debug_ctx_plan", "ka_debug_tp_launches", "ka_debug_kmeans_level", "ka_debug_kmeans_host", "ka_ctx_fallback_runs", "ka_ctx_helped_tasks", "ka_ctx_create", "ka_ctx_destroy", "ka_ctx_set_stream", "ka_ctx_set_shared", "ka_last_error", "ka_abi_version",
            "ka_msa_tree", "ka_tree_upload", "ka_tree_run", "ka_tree_refine", "ka_tree_sync", "ka_tree_paths_size",
            "ka_tree_download", "ka_tree_get_profile", "ka_tree_get_timing", "ka_debug_trace", "ka_tree_cells", "ka_tree_kernel_ms", "ka_tree_launch_ms",
            "ka_pairwise_batch", "ka_pairwise_kernel_ms", "ka_tree_build_consistency", "ka_tree_get_consistency",
@@ -87,6 +87,8 @@ def load_library():
     L.ka_last_error.restype = C.c_char_p
     L.ka_debug_set_hooks.argtypes = [vp, C.c_int]
     L.ka_debug_reload_env.argtypes = [vp]
+    L.ka_debug_plan.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp]
+    L.ka_debug_ctx_plan.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp]
     L.ka_tree_profile_dev.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_int)]
     L.ka_tree_reserve_profile_dev.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
     L.ka_tree_build_consistency_part.argtypes = [vp, C.c_int, C.c_float, C.c_int, C.c_int]
@@ -278,6 +280,10 @@ class Context:
     def reload_env(self):
         """tools / tests: the KA_* environment switches are read once at context creation; read them again"""
         self._chk(self.L.ka_debug_reload_env(self.h))
+
+    def debug_plan(self, n_cus=256):
+        """ka_debug_ctx_plan: the launch plan this context holds, flattened like debug_plan()'s (n_cus only sizes the first buffer)"""
+        return _flat_plan(self.L, self._job["ntasks"], int(n_cus), lambda *out: self.L.ka_debug_ctx_plan(self.h, *out))
 
     def tp_launches(self):
         """launches of the throughput kernel (KA_TP=1) since the library was loaded (ka_debug_tp_launches)"""
@@ -1063,6 +1069,44 @@ def dist_plan_subtrees(lens, tasks, world):
     if L.ka_dist_plan_subtrees(len(lens), _ptr(lens), len(tasks), _ptr(tasks), int(world), _ptr(run_rank), _ptr(top), C.byref(n_top)):
         raise RuntimeError(L.ka_last_error().decode())
     return run_rank, top[:n_top.value].tolist()
+
+
+PLAN_SCALARS = ("levels", "n_blocks", "max_cluster", "n_trees", "chain_level", "queue_first", "queue_off", "queue_n", "overlap_plan",
+                "reserve_cus", "chain_blocks_off", "chain_blocks_n")
+PLAN_TASK_FIELDS = ("parent", "chain_need", "is_root", "wait_mult", "qa", "qb", "spine")
+
+
+def _flat_plan(L, n_tasks, n_cus, call):
+    """one flattened launch plan (ka_debug_plan / ka_debug_ctx_plan) as a dict: the PLAN_SCALARS as ints, the PLAN_TASK_FIELDS
+    as int32[n_tasks], blocks int32[n, 2], blocks_off, level_lean"""
+    scalars, per_task = np.zeros(16, np.int32), np.zeros((7, n_tasks), np.int32)
+    blocks_off, level_lean = np.zeros(n_tasks + 1, np.int32), np.zeros(n_tasks, np.int32)
+    cap = 4 * n_tasks + 8 * n_cus + 4096
+    for _ in range(2):
+        blocks = np.zeros((cap, 2), np.int32)
+        rc = call(_ptr(scalars), _ptr(per_task), _ptr(blocks), cap, _ptr(blocks_off), _ptr(level_lean))
+        if not rc or scalars[1] <= cap:
+            break
+        cap = int(scalars[1])                           # (a deep, narrow tree: every level a table of its own)
+    if rc:
+        raise KalignAmdError(L.ka_last_error().decode())
+    plan = {k: int(v) for k, v in zip(PLAN_SCALARS, scalars)}
+    plan.update({k: per_task[i].copy() for i, k in enumerate(PLAN_TASK_FIELDS)})
+    plan.update(blocks=blocks[:plan["n_blocks"]].copy(), blocks_off=blocks_off[:plan["levels"] + 1].copy(),
+                level_lean=level_lean[:plan["levels"]].copy())
+    return plan
+
+
+def debug_plan(lens, tasks, n_cus, shared=False, cons_K=0, hooks=0, task_ids=None):
+    """ka_debug_plan: the launch plan of a job on a device of n_cus compute units, under the KA_* switches the environment holds
+    now -- pure host logic, needs no GPU"""
+    L = load_library()
+    lens = np.ascontiguousarray(lens, np.int32)
+    tasks = np.ascontiguousarray(tasks, np.int32)
+    ids = None if task_ids is None else np.ascontiguousarray(task_ids, np.int32)
+    return _flat_plan(L, len(tasks), int(n_cus), lambda *out: L.ka_debug_plan(
+        len(lens), _ptr(lens), len(tasks), _ptr(tasks), int(n_cus), int(bool(shared)), int(cons_K), int(hooks),
+        _ptr(ids) if ids is not None else None, 0 if ids is None else len(ids), *out))
 
 
 def dist_unique_id():

@@ -17,7 +17,7 @@ __attribute__((visibility("hidden"))) int ka_fail_message(const char* m) { retur
 extern "C" const char* ka_last_error(void) { return g_err.c_str(); }
 struct ka_ctx;
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_guide.cpp)
-extern "C" int ka_abi_version(void) { return 14; }
+extern "C" int ka_abi_version(void) { return 15; }
 
 extern "C" int ka_ctx_create(int device, ka_ctx** out)
 {
@@ -237,27 +237,6 @@ KaTreeDev tree_dev(ka_ctx* c)
         D.cons_maps = c->d_cons_maps.p; D.cons_map_off = c->d_cons_map_off.p;
         D.colof = c->d_colof.p; D.sip = c->d_sip.p; D.sip_off = c->d_sip_off.p;
         return D;
-}
-
-// Workgroup table of one launch: near the top of the tree there are fewer tasks than CUs, so a task
-// gets a cluster of up to max_cluster workgroups (the kernel decides from the actual operand
-// lengths how many of them it uses).  Workgroups of one cluster are spaced 8 blocks apart:
-// block b runs on XCD b % 8 (observed, not contractual -- used for L2 locality only).
-void build_blocks(const ka_ctx* c, const std::vector<int>& L, std::vector<int2>& tbl, int* lean_out)
-{
-        const int nt = (int)L.size();
-        int lean = 1;                                    // launch kind: 0 = 8 waves, 1 = lean, 2 = half
-        for (int t : L) if (c->descs[t].nsip_a != 1 || c->descs[t].nsip_b != 1) lean = 0;
-        if (c->env.no_lean) lean = 0;
-        if (!lean && nt > c->n_cus && !c->env.no_half) lean = 2;   // more tasks than CUs: two 4-wave workgroups per CU
-        int G = 1;
-        while (lean == 0 && G * 2 <= c->max_cluster && nt * G * 2 <= c->n_cus) G *= 2;
-        const int groups = (nt + 7) / 8;
-        tbl.assign((size_t)groups * 8 * G, make_int2(-1, 0));
-        for (int j = 0; j < nt; j++)
-                for (int m = 0; m < G; m++)
-                        tbl[(size_t)(j % 8) + 8 * ((size_t)m + (size_t)G * (j / 8))] = make_int2(L[j], m | (G << 8));
-        *lean_out = lean;
 }
 
 // KA_LAUNCH_EV: an event behind launch number c->n_launches of the run (measurements; ka_tree_launch_ms)

@@ -2,6 +2,8 @@
 // ONE queued launch, from where the rest of the tree is ONE chained launch; the workgroup table of every launch; the spare workgroups of
 // the chained launch by a greedy pass over a simulated schedule (DESIGN.md sections 4, 4d, 4h).  Replaces the task order of
 // create_msa_tree / recursive_aln (lib/src/aln_run.c:43-124) -- the reference walks the tree with OpenMP tasks.
+// The planner proper (prepare_tasks, build_blocks, plan_launches and its steps) works on a KaPlan (ka_plan.h) and needs no GPU; the
+// context comes in with ka_tree_upload and upload_plan, and ka_debug_plan / ka_debug_ctx_plan hand a plan out for tests and tools.
 #include "ka_ctx.h"
 
 // mean seq_distance over both clusters in sip order (aln_run.c:126-203)
@@ -15,534 +17,544 @@ static float mean_distance(const float* dist, const std::vector<int>& ma, const 
         return n ? sum / (float)n : 0.0f;
 }
 
-// Launch plan of the uploaded job: parents and join counts of the chained launch, workgroup tables per level.
-// Depends on c->shared_gpu (no clusters, no chain), so ka_tree_sync can re-plan after a residency failure.
-int plan_launches(ka_ctx* c)
+// Workgroup table of one launch: near the top of the tree there are fewer tasks than CUs, so a task
+// gets a cluster of up to max_cluster workgroups (the kernel decides from the actual operand
+// lengths how many of them it uses).  Workgroups of one cluster are spaced 8 blocks apart:
+// block b runs on XCD b % 8 (observed, not contractual -- used for L2 locality only).
+void build_blocks(const KaPlan* c, const std::vector<int>& L, std::vector<int2>& tbl, int* lean_out)
 {
-        const int numseq = c->numseq, n_tasks = c->n_tasks;
-        const int* abc = c->abc.data();
-        const int max_level = (int)c->levels.size();
-        // the tasks this plan covers: all of them, or the subset of ka_tree_plan_tasks (a rank's subtrees of a sharded
-        // tree: closed under descendants).  A task outside the plan is neither a parent nor a producer in it.
-        const bool subset = !c->plan_active.empty();
-        auto act = [&](int t) { return !subset || c->plan_active[t] != 0; };
-        c->plan_levels.assign(max_level, std::vector<int>());
-        for (int L = 0; L < max_level; L++) for (int t : c->levels[L]) if (act(t)) c->plan_levels[L].push_back(t);
-        const std::vector<std::vector<int>>& levels = c->plan_levels;
-        // ---- parents, and the level from which the rest of the tree runs as ONE chained launch: the first
-        // non-leaf level with at most one task per CU (all its workgroups resident at once; levels only get
-        // narrower above it).  KA_NO_CHAIN=1 keeps one launch per level.
-        {
-                std::vector<int> task_of((2 * numseq - 1), -1);
-                for (int t = 0; t < n_tasks; t++) task_of[abc[3 * t + 2]] = t;
-                for (int t = 0; t < n_tasks; t++) { c->descs[t].parent = -1; c->descs[t].chain_need = 0; }
-                for (int t = 0; t < n_tasks; t++) c->descs[t].is_root = 1;
-                for (int t = 0; t < n_tasks; t++) {
-                        const int a = abc[3 * t], b = abc[3 * t + 1];
-                        // (is_root is a property of the tree: the root's task builds no profile.  parent is one of the plan.)
-                        if (a >= numseq) { c->descs[task_of[a]].is_root = 0; if (act(t) && act(task_of[a])) c->descs[task_of[a]].parent = t; }
-                        if (b >= numseq) { c->descs[task_of[b]].is_root = 0; if (act(t) && act(task_of[b])) c->descs[task_of[b]].parent = t; }
-                }
-                {
-                        // join watchdog of the chained launch: ~2 s per 4e9 estimated DP cells below the task (a healthy
-                        // sibling subtree of a huge job may legitimately take longer than the base bound)
-                        std::vector<double> len(2 * numseq - 1, 0.0), cells(2 * numseq - 1, 0.0);
-                        for (int i = 0; i < numseq; i++) len[i] = c->lens[i];
-                        for (int t = 0; t < n_tasks; t++) {
-                                const int a = abc[3 * t], b = abc[3 * t + 1], cc = abc[3 * t + 2];
-                                len[cc] = 1.1 * std::max(len[a], len[b]);
-                                cells[cc] = cells[a] + cells[b] + len[a] * len[b];
-                                c->descs[t].wait_mult = 1 + (int)std::min(63.0, cells[cc] / 4e9);
-                                // (descs[t].refine -- the edges a KALIGN_REFINE_CONFIDENT pass refines -- is not part of the plan: it is
-                                // set by ka_tree_refine and must survive the re-plan of a watchdog fallback, ka_tree_sync)
-                        }
-                }
-                c->n_trees = numseq - n_tasks;
-                c->chain_level = -1;
-                if (!c->env.no_chain && !c->shared_gpu) {
-                        for (int L = 0; L + 1 < max_level; L++) {
-                                bool all_ss = true;
-                                for (int t : levels[L]) if (c->descs[t].nsip_a != 1 || c->descs[t].nsip_b != 1) all_ss = false;
-                                // (one tree: the chain starts where a level has at most 200 tasks -- the ~50 workgroups that leaves free go to the
-                                // entries under the critical path, and since the chain overlaps the queue (round 5) a later start costs little:
-                                // 4096 x 400 aa 14.70 -> 14.61 ms, default mode 21.4 -> 20.6, 4096 x 2000 nt 71.8 -> 70.2, 1024 x 2000 nt 33.3 -> 31.9;
-                                // a forest keeps every CU it can get: four 4096 x 2000 nt trees 183 -> 191 with 200; profiles/r05_chain_start.log)
-                                int chain_tasks = (c->n_trees <= 1) ? std::min(c->n_cus - 8, 200) : c->n_cus - 8;
-                                if (c->env.chain_tasks > 0) chain_tasks = std::min(chain_tasks, c->env.chain_tasks);   // experiments
-                                if (!all_ss && (int)levels[L].size() <= chain_tasks) { c->chain_level = L; break; }   // one workgroup per CU, all resident
-                        }
-                }
-                // SPINES IN THE CHAIN (round 6; KA_SPINE = how many; built, bit-identical, measured, OFF: DESIGN 4j).  What the single tree waits for is not
-                // a CU or an operand but the LATENCY of the tasks on its longest dependency chains (13.3 of 14.7 ms are the run times of 17
-                // tasks, tools/levels_real.py) -- and the first four or five of those run in the queued launch: one four-wave workgroup,
-                // ka_strip with its event steps, 0.54-0.72 ms for a 430 x 420 task that takes 0.33-0.45 ms in the chained launch (helper
-                // strips, two workgroups).  So the chain reaches DOWN along the most critical entries: from each of the KA_SPINE entries of
-                // the chain's first level with the longest estimated path through them (leaves .. entry .. root), the child with the later
-                // estimated finish, and its child, ... down to the queue's first level are tasks of the chained launch too (c->spine):
-                // the lowest one is an entry of its own (both children come from the leaf levels / the queue: done flags), the others
-                // have ONE child inside the launch (chain_need 1) and one from the queue (qa / qb).  Nothing in the queue consumes a spine
-                // task (its parent is the spine task above it), so the queue's order stays topological.
-                c->spine.assign(n_tasks, 0);
-                {
-                        int L0 = 0;
-                        while (c->chain_level >= 1 && L0 < c->chain_level) {
-                                bool all_ss = true;
-                                for (int t : levels[L0]) if (c->descs[t].nsip_a != 1 || c->descs[t].nsip_b != 1) all_ss = false;
-                                if (!all_ss) break;
-                                L0++;
-                        }
-                        const bool queue_ok = c->chain_level >= 1 && !c->env.no_queue && !c->env.no_half && c->chain_level - L0 >= 2 && (int)levels[L0].size() > c->n_cus;
-                        const bool overlap_ok = c->env.overlap > 0 && !subset && !c->env.no_lean && !c->shared_gpu;
-                        const int K = env_int("KA_SPINE", 0);             // (measured: 1 % at best with KA_RESERVE -- DESIGN 4j; off)
-                        if (K > 0 && queue_ok && overlap_ok && !c->env.no_crit) {
-                                std::vector<double> lmax(2 * numseq - 1, 0.0), nmem(2 * numseq - 1, 1.0), qlen(2 * numseq - 1, 0.0), fin(2 * numseq - 1, 0.0), dur(n_tasks, 0.0), upw(n_tasks, 0.0);
-                                for (int i = 0; i < numseq; i++) { lmax[i] = c->lens[i]; qlen[i] = c->lens[i]; }
-                                for (int t = 0; t < n_tasks; t++) {
-                                        const int a = abc[3 * t], b = abc[3 * t + 1], cc = abc[3 * t + 2];
-                                        lmax[cc] = std::max(lmax[a], lmax[b]); nmem[cc] = nmem[a] + nmem[b];
-                                        qlen[cc] = lmax[cc] * (1.0 + 0.1 * std::sqrt(nmem[cc]));
-                                        dur[t] = 2.0 * std::max(qlen[a], qlen[b]) + std::min(qlen[a], qlen[b]);
-                                        fin[cc] = std::max(fin[a], fin[b]) + dur[t];
-                                }
-                                for (int t = n_tasks - 1; t >= 0; t--) upw[t] = dur[t] + ((act(t) && c->descs[t].parent >= 0) ? upw[c->descs[t].parent] : 0.0);
-                                std::vector<int> ent(levels[c->chain_level].begin(), levels[c->chain_level].end());
-                                std::stable_sort(ent.begin(), ent.end(), [&](int x, int y) { return fin[abc[3 * x + 2]] + upw[x] > fin[abc[3 * y + 2]] + upw[y]; });
-                                for (int e = 0; e < (int)ent.size() && e < K; e++) {
-                                        int cur = ent[e];
-                                        while (true) {
-                                                int best = -1;
-                                                for (int k = 0; k < 2; k++) {
-                                                        const int ch = abc[3 * cur + k];
-                                                        if (ch < numseq) continue;
-                                                        const int tc = task_of[ch];
-                                                        if (!act(tc) || c->task_level[tc] < L0 || c->task_level[tc] >= c->chain_level) continue;
-                                                        if (best < 0 || fin[ch] > fin[abc[3 * best + 2]]) best = tc;
-                                                }
-                                                if (best < 0) break;
-                                                c->spine[best] = 1;
-                                                cur = best;
-                                        }
-                                }
-                        }
-                }
-                auto inchain = [&](int t) { return t >= 0 && act(t) && (c->task_level[t] >= c->chain_level || c->spine[t]); };
-                if (c->chain_level >= 0) {
-                        for (int t = 0; t < n_tasks; t++) {
-                                if (!inchain(t)) continue;
-                                int need = 0;
-                                for (int k = 0; k < 2; k++) {
-                                        const int ch = abc[3 * t + k];
-                                        if (ch >= numseq && inchain(task_of[ch])) need++;
-                                }
-                                c->descs[t].chain_need = need;
-                        }
-                        // tests: make the last join wait for a workgroup that never comes (a residency failure as seen
-                        // from the device) -- the bounded wait must report it and ka_tree_sync must re-plan and re-run
-                        if (c->test_hooks & KA_DEBUG_STARVE_ROOT_JOIN) c->descs[n_tasks - 1].chain_need += 1;
-                }
-                // ---- the queued launch: every level between the seq-seq leaves and the chained launch (each holds more
-                // tasks than the GPU has workgroup slots) as ONE launch of the half kernel; see ka_task_queue_entry.
-                // KA_NO_QUEUE=1 keeps one launch per level.
-                for (int t = 0; t < n_tasks; t++) { c->descs[t].qa = -1; c->descs[t].qb = -1; }
-                c->queue_first = -1;
-                c->overlap_plan = 0;
-                if (c->chain_level >= 1 && !c->env.no_queue && !c->env.no_half) {
-                        int L0 = 0;
-                        while (L0 < c->chain_level) {                       // skip the leading seq-seq levels (lean kernel)
-                                bool all_ss = true;
-                                for (int t : levels[L0]) if (c->descs[t].nsip_a != 1 || c->descs[t].nsip_b != 1) all_ss = false;
-                                if (!all_ss) break;
-                                L0++;
-                        }
-                        bool ok = c->chain_level - L0 >= 2;                 // one level alone gains nothing
-                        if ((int)levels[L0].size() <= c->n_cus) ok = false;   // (the queue's first level must fill the GPU; later ones need not)
-                        if (ok) {
-                                c->queue_first = L0;
-                                // Overlapping launches (KA_OVERLAP; whole-tree plans only): the chained launch goes out beside the queued one, and
-                                // its tasks wait for the done flags of what the QUEUE makes for them (qa / qb of a chain task: its operands'
-                                // producers in the queued launch; inside the chain the join points order things as before).
-                                c->overlap_plan = (c->env.overlap > 0 && c->plan_active.empty() && !c->env.no_lean && !c->shared_gpu) ? c->env.overlap : 0;
-                                const int lo = L0;
-                                for (int t = 0; t < n_tasks; t++) {
-                                        if (c->task_level[t] < L0 || !act(t)) continue;
-                                        // (a task of the chained launch: only what OTHER launches make -- inside the chain the join points order things)
-                                        const bool in_chain = inchain(t);
-                                        if (in_chain && !c->overlap_plan) continue;
-                                        const int a = abc[3 * t], b = abc[3 * t + 1];
-                                        auto dep = [&](int node) -> int {
-                                                if (node < numseq || !act(task_of[node])) return -1;
-                                                const int lv = c->task_level[task_of[node]];
-                                                if (lv < lo || (in_chain && inchain(task_of[node]))) return -1;
-                                                return task_of[node];
-                                        };
-                                        c->descs[t].qa = dep(a);
-                                        c->descs[t].qb = dep(b);
-                                }
-                        }
-                }
-        }
+        const int nt = (int)L.size();
+        int lean = 1;                                    // launch kind: 0 = 8 waves, 1 = lean, 2 = half
+        for (int t : L) if (c->descs[t].nsip_a != 1 || c->descs[t].nsip_b != 1) lean = 0;
+        if (c->env.no_lean) lean = 0;
+        if (!lean && nt > c->n_cus && !c->env.no_half) lean = 2;   // more tasks than CUs: two 4-wave workgroups per CU
+        int G = 1;
+        while (lean == 0 && G * 2 <= c->max_cluster && nt * G * 2 <= c->n_cus) G *= 2;
+        const int groups = (nt + 7) / 8;
+        tbl.assign((size_t)groups * 8 * G, make_int2(-1, 0));
+        for (int j = 0; j < nt; j++)
+                for (int m = 0; m < G; m++)
+                        tbl[(size_t)(j % 8) + 8 * ((size_t)m + (size_t)G * (j / 8))] = make_int2(L[j], m | (G << 8));
+        *lean_out = lean;
+}
 
-        // (the spines only exist beside an overlapping queued launch: the conditions above are the queue block's own)
-        {
-                bool any = false;
-                for (int t = 0; t < n_tasks; t++) any = any || c->spine[t];
-                if (any && !(c->queue_first >= 0 && c->overlap_plan)) return fail("plan_launches: spine tasks without an overlapping queued launch");
+// ---- the launch planner: plan_launches at the end of this part is the list of its steps ----
+// The tasks a plan covers: all of them, or the subset of ka_tree_plan_tasks (a rank's subtrees of a sharded tree: closed under
+// descendants).  A task outside the plan is neither a parent nor a producer in it.
+static inline bool act(const KaPlan* p, int t) { return p->plan_active.empty() || p->plan_active[t] != 0; }
+// a task of the chained launch: at or above its first level, or on a spine that reaches down from it
+static inline bool in_chain(const KaPlan* p, int t) { return t >= 0 && act(p, t) && (p->task_level[t] >= p->chain_level || p->spine[t]); }
+static bool all_seq_seq(const KaPlan* p, const std::vector<int>& L)
+{
+        return std::all_of(L.begin(), L.end(), [&](int t) { return p->descs[t].nsip_a == 1 && p->descs[t].nsip_b == 1; });
+}
+
+// What the steps of one plan hand each other (local to a plan_launches call).
+struct PlanWork {
+        std::vector<int> task_of;                    // node -> the task that makes it (-1: a sequence)
+        // Profile lengths are only known on the device; the estimate per node, in two models.  len_sqrt: the longest member sequence
+        // times (1 + 0.1 sqrt(members)) -- the growth of the DSSim sets with their indel-rich tails (13151 columns for 4096 x 2000 nt,
+        // 2965 for 4096 x 400 aa), harmless where alignments stay shorter.  len_11: 1.1 x the longer child, compounding (round 3).
+        std::vector<double> len_sqrt, len_11;
+        // ... and per task, in either model, the way to the root: estimated wavefront steps (2 max + min of the operands' lengths) of the
+        // task and of everything above it in the plan.
+        std::vector<double> way_sqrt, way_11;
+        int L0 = 0;                                  // the first level that is not all seq-seq (at most chain_level; 0 without a chain)
+        std::vector<int> order, extra;               // the chain's entries in layout order; spare workgroups of each, beyond G0
+        int m = 0, G0 = 1, spare = 0, front_n = 0;   // entries per XCD column; workgroups every entry starts with; CUs still free; entries at the kept head
+};
+
+// parents (of the plan), roots (of the tree), trees
+static void link_tasks(KaPlan* p, PlanWork& w)
+{
+        const int numseq = p->numseq, n_tasks = p->n_tasks;
+        const int* abc = p->abc.data();
+        w.task_of.assign(2 * numseq - 1, -1);
+        for (int t = 0; t < n_tasks; t++) w.task_of[abc[3 * t + 2]] = t;
+        for (int t = 0; t < n_tasks; t++) { p->descs[t].parent = -1; p->descs[t].chain_need = 0; p->descs[t].is_root = 1; p->descs[t].qa = -1; p->descs[t].qb = -1; }
+        for (int t = 0; t < n_tasks; t++)
+                for (int k = 0; k < 2; k++) {
+                        const int ch = abc[3 * t + k];
+                        if (ch < numseq) continue;
+                        // (is_root is a property of the tree: the root's task builds no profile.  parent is one of the plan.)
+                        p->descs[w.task_of[ch]].is_root = 0;
+                        if (act(p, t) && act(p, w.task_of[ch])) p->descs[w.task_of[ch]].parent = t;
+                }
+        p->n_trees = numseq - n_tasks;
+}
+
+// The one estimator: lengths per node, ways to the root per task, both models, once per plan (the spine, queue-order, spare and
+// reserve steps read them), and with the lengths the tasks' wait_mult.  Every sum keeps its operand order -- the steps sort on these
+// doubles, and the plans are pinned bit for bit (tests/test_plan_host.py).
+static void estimate(KaPlan* p, PlanWork& w)
+{
+        const int numseq = p->numseq, n_tasks = p->n_tasks;
+        const int* abc = p->abc.data();
+        std::vector<double> lmax(2 * numseq - 1, 0.0), nmem(2 * numseq - 1, 1.0), cells(2 * numseq - 1, 0.0);
+        w.len_sqrt.assign(2 * numseq - 1, 0.0); w.len_11.assign(2 * numseq - 1, 0.0);
+        for (int i = 0; i < numseq; i++) { lmax[i] = p->lens[i]; w.len_sqrt[i] = p->lens[i]; w.len_11[i] = p->lens[i]; }
+        for (int t = 0; t < n_tasks; t++) {
+                const int a = abc[3 * t], b = abc[3 * t + 1], cc = abc[3 * t + 2];
+                lmax[cc] = std::max(lmax[a], lmax[b]); nmem[cc] = nmem[a] + nmem[b];
+                w.len_sqrt[cc] = lmax[cc] * (1.0 + 0.1 * std::sqrt(nmem[cc]));
+                w.len_11[cc] = 1.1 * std::max(w.len_11[a], w.len_11[b]);
+                // join watchdog of the chained launch: ~2 s per 4e9 estimated DP cells below the task (a healthy sibling subtree of a
+                // huge job may legitimately take longer than the base bound); always by the compounding model
+                cells[cc] = cells[a] + cells[b] + w.len_11[a] * w.len_11[b];
+                p->descs[t].wait_mult = 1 + (int)std::min(63.0, cells[cc] / 4e9);
+                // (descs[t].refine -- the edges a KALIGN_REFINE_CONFIDENT pass refines -- is not part of the plan: it is
+                // set by ka_tree_refine and must survive the re-plan of a watchdog fallback, ka_tree_sync)
         }
-        // ---- workgroup tables, one per dependency level (build_blocks) ----
-        // Workgroups one task may use: 16, or 32 for jobs whose top tasks are big enough to be work-bound at 16 (round 4: a
-        // 9000 x 9700 task of C3 takes 5.8 ms on 16 workgroups, of which ~1.6 ms are the wavefront's dependent steps) -- by the
-        // estimated root (longest sequence x (1 + 0.1 sqrt(sequences)), squared): >= 6e7 cells.  Measured, limit 16 -> 32
-        // (profiles/r04_max_cluster.log): C3 81.9 -> 74.8 ms, 1024 x 2000 nt 34.9 -> 33.0, 512 x 3000 nt 43.6 -> 41.9; 16384 x 500 aa
-        // and 2048 x 1000 aa unchanged; 4096 x 400 aa and 8192 x 300 aa 1-2 % slower (surplus members waiting at the joins).
-        {
-                double lmax = 0.0;
-                for (int i = 0; i < numseq; i++) lmax = std::max(lmax, (double)c->lens[i]);
-                const double root = lmax * (1.0 + 0.1 * std::sqrt((double)numseq));
-                // (... and for big jobs with a consistency table: the votes of their top tasks share by member ranges from 20 workgroups on)
-                const bool big_cons = c->cons_K > 0 && numseq >= 2048;
-                c->max_cluster = c->env.max_cluster > 0 ? std::min(32, c->env.max_cluster) : ((root * root >= 6e7 || big_cons) ? 32 : 16);
+        // (the steps once guarded the parent's term differently -- `active and has a parent` in three, `has a parent` in the spare pass.
+        // One guard serves both: link_tasks gives a parent to tasks of the plan only, so a task outside it has none.)
+        w.way_sqrt.assign(n_tasks, 0.0); w.way_11.assign(n_tasks, 0.0);
+        for (int t = n_tasks - 1; t >= 0; t--) {                      // parents come after their children in the task list
+                const int a = abc[3 * t], b = abc[3 * t + 1], up = p->descs[t].parent;
+                w.way_sqrt[t] = 2.0 * std::max(w.len_sqrt[a], w.len_sqrt[b]) + std::min(w.len_sqrt[a], w.len_sqrt[b]) + (up >= 0 ? w.way_sqrt[up] : 0.0);
+                w.way_11[t] = 2.0 * std::max(w.len_11[a], w.len_11[b]) + std::min(w.len_11[a], w.len_11[b]) + (up >= 0 ? w.way_11[up] : 0.0);
         }
-        if (c->shared_gpu) c->max_cluster = 1;
-        c->blocks_flat.clear(); c->blocks_off.assign(1, 0); c->level_lean.clear();
-        for (auto& L : levels) {
+}
+
+// The level from which the rest of the tree runs as ONE chained launch: the first non-leaf level with at most one task per CU (all
+// its workgroups resident at once; levels only get narrower above it).  KA_NO_CHAIN=1 keeps one launch per level.  And w.L0, the
+// first level below it that is not all seq-seq: where a queued launch would start, and how far down a spine reaches.
+static void place_chain(KaPlan* p, PlanWork& w)
+{
+        p->chain_level = -1;
+        if (p->env.no_chain || p->shared_gpu) return;
+        // (one tree: the chain starts where a level has at most 200 tasks -- the ~50 workgroups that leaves free go to the
+        // entries under the critical path, and since the chain overlaps the queue (round 5) a later start costs little:
+        // 4096 x 400 aa 14.70 -> 14.61 ms, default mode 21.4 -> 20.6, 4096 x 2000 nt 71.8 -> 70.2, 1024 x 2000 nt 33.3 -> 31.9;
+        // a forest keeps every CU it can get: four 4096 x 2000 nt trees 183 -> 191 with 200; profiles/r05_chain_start.log)
+        int chain_tasks = (p->n_trees <= 1) ? std::min(p->n_cus - 8, 200) : p->n_cus - 8;
+        if (p->env.chain_tasks > 0) chain_tasks = std::min(chain_tasks, p->env.chain_tasks);   // experiments
+        for (int L = 0; L + 1 < (int)p->plan_levels.size(); L++)
+                if (!all_seq_seq(p, p->plan_levels[L]) && (int)p->plan_levels[L].size() <= chain_tasks) { p->chain_level = L; break; }   // one workgroup per CU, all resident
+        while (w.L0 < p->chain_level && all_seq_seq(p, p->plan_levels[w.L0])) w.L0++;    // the leading seq-seq levels (lean kernel) end here
+}
+
+// The queued launch: every level between the seq-seq leaves and the chained launch (each holds more tasks than the GPU has
+// workgroup slots) as ONE launch of the half kernel; see ka_task_queue_entry.  KA_NO_QUEUE=1 keeps one launch per level.
+// Overlapping launches (KA_OVERLAP; whole-tree plans only): the chained launch goes out beside the queued one, and its tasks wait
+// for the done flags of what the QUEUE makes for them (set_queue_deps).
+static void place_queue(KaPlan* p, const PlanWork& w)
+{
+        p->queue_first = -1;
+        p->overlap_plan = 0;
+        if (p->chain_level < 1 || p->env.no_queue || p->env.no_half) return;
+        if (p->chain_level - w.L0 < 2) return;                                  // one level alone gains nothing
+        if ((int)p->plan_levels[w.L0].size() <= p->n_cus) return;               // (the queue's first level must fill the GPU; later ones need not)
+        p->queue_first = w.L0;
+        p->overlap_plan = (p->env.overlap > 0 && p->plan_active.empty() && !p->env.no_lean && !p->shared_gpu) ? p->env.overlap : 0;
+}
+
+// SPINES IN THE CHAIN (round 6; KA_SPINE = how many; built, bit-identical, measured, OFF: DESIGN 4j).  What the single tree waits for is not
+// a CU or an operand but the LATENCY of the tasks on its longest dependency chains (13.3 of 14.7 ms are the run times of 17
+// tasks, tools/levels_real.py) -- and the first four or five of those run in the queued launch: one four-wave workgroup,
+// ka_strip with its event steps, 0.54-0.72 ms for a 430 x 420 task that takes 0.33-0.45 ms in the chained launch (helper
+// strips, two workgroups).  So the chain reaches DOWN along the most critical entries: from each of the KA_SPINE entries of
+// the chain's first level with the longest estimated path through them (leaves .. entry .. root), the child with the later
+// estimated finish, and its child, ... down to the queue's first level are tasks of the chained launch too (p->spine):
+// the lowest one is an entry of its own (both children come from the leaf levels / the queue: done flags), the others
+// have ONE child inside the launch (chain_need 1) and one from the queue (qa / qb).  Nothing in the queue consumes a spine
+// task (its parent is the spine task above it), so the queue's order stays topological.
+// (the spines only exist beside an overlapping queued launch)
+static void mark_spines(KaPlan* p, const PlanWork& w)
+{
+        const int numseq = p->numseq, n_tasks = p->n_tasks;
+        const int* abc = p->abc.data();
+        p->spine.assign(n_tasks, 0);
+        const int K = p->env.spine;                       // (measured: 1 % at best with KA_RESERVE -- DESIGN 4j; off)
+        if (K <= 0 || p->queue_first < 0 || !p->overlap_plan || p->env.no_crit) return;
+        // (fin: when a node is ready if every task below it took its own wavefront steps, one after the other along the longest path --
+        // not the finish times of the greedy pass's simulated schedule, which knows about workgroups)
+        std::vector<double> fin(2 * numseq - 1, 0.0);
+        for (int t = 0; t < n_tasks; t++) {
+                const int a = abc[3 * t], b = abc[3 * t + 1], cc = abc[3 * t + 2];
+                const double dur = 2.0 * std::max(w.len_sqrt[a], w.len_sqrt[b]) + std::min(w.len_sqrt[a], w.len_sqrt[b]);
+                fin[cc] = std::max(fin[a], fin[b]) + dur;
+        }
+        std::vector<int> ent(p->plan_levels[p->chain_level].begin(), p->plan_levels[p->chain_level].end());
+        std::stable_sort(ent.begin(), ent.end(), [&](int x, int y) { return fin[abc[3 * x + 2]] + w.way_sqrt[x] > fin[abc[3 * y + 2]] + w.way_sqrt[y]; });
+        for (int e = 0; e < (int)ent.size() && e < K; e++) {
+                int cur = ent[e];
+                while (true) {
+                        int best = -1;
+                        for (int k = 0; k < 2; k++) {
+                                const int ch = abc[3 * cur + k];
+                                if (ch < numseq) continue;
+                                const int tc = w.task_of[ch];
+                                if (!act(p, tc) || p->task_level[tc] < w.L0 || p->task_level[tc] >= p->chain_level) continue;
+                                if (best < 0 || fin[ch] > fin[abc[3 * best + 2]]) best = tc;
+                        }
+                        if (best < 0) break;
+                        p->spine[best] = 1;
+                        cur = best;
+                }
+        }
+}
+
+// join counts of the chained launch: the children of a task that run inside it
+static void set_chain_need(KaPlan* p, const PlanWork& w)
+{
+        if (p->chain_level < 0) return;
+        for (int t = 0; t < p->n_tasks; t++) {
+                if (!in_chain(p, t)) continue;
+                int need = 0;
+                for (int k = 0; k < 2; k++) {
+                        const int ch = p->abc[3 * t + k];
+                        if (ch >= p->numseq && in_chain(p, w.task_of[ch])) need++;
+                }
+                p->descs[t].chain_need = need;
+        }
+        // tests: make the last join wait for a workgroup that never comes (a residency failure as seen
+        // from the device) -- the bounded wait must report it and ka_tree_sync must re-plan and re-run
+        if (p->test_hooks & KA_DEBUG_STARVE_ROOT_JOIN) p->descs[p->n_tasks - 1].chain_need += 1;
+}
+
+// qa / qb: the producers of a task's operands in the queued launch -- for the queue's own tasks, and in an overlapping plan for the
+// chain's tasks too: its operands' producers in the queued launch (inside the chain the join points order things as before).
+static void set_queue_deps(KaPlan* p, const PlanWork& w)
+{
+        if (p->queue_first < 0) return;
+        const int lo = p->queue_first;
+        for (int t = 0; t < p->n_tasks; t++) {
+                if (p->task_level[t] < lo || !act(p, t)) continue;
+                // (a task of the chained launch: only what OTHER launches make -- inside the chain the join points order things)
+                const bool chained = in_chain(p, t);
+                if (chained && !p->overlap_plan) continue;
+                auto dep = [&](int node) -> int {
+                        if (node < p->numseq || !act(p, w.task_of[node])) return -1;
+                        const int lv = p->task_level[w.task_of[node]];
+                        if (lv < lo || (chained && in_chain(p, w.task_of[node]))) return -1;
+                        return w.task_of[node];
+                };
+                p->descs[t].qa = dep(p->abc[3 * t]);
+                p->descs[t].qb = dep(p->abc[3 * t + 1]);
+        }
+}
+
+// Workgroups one task may use: 16, or 32 for jobs whose top tasks are big enough to be work-bound at 16 (round 4: a
+// 9000 x 9700 task of C3 takes 5.8 ms on 16 workgroups, of which ~1.6 ms are the wavefront's dependent steps) -- by the
+// estimated root (longest sequence x (1 + 0.1 sqrt(sequences)), squared): >= 6e7 cells.  Measured, limit 16 -> 32
+// (profiles/r04_max_cluster.log): C3 81.9 -> 74.8 ms, 1024 x 2000 nt 34.9 -> 33.0, 512 x 3000 nt 43.6 -> 41.9; 16384 x 500 aa
+// and 2048 x 1000 aa unchanged; 4096 x 400 aa and 8192 x 300 aa 1-2 % slower (surplus members waiting at the joins).
+static void set_cluster_limit(KaPlan* p)
+{
+        double lmax = 0.0;
+        for (int i = 0; i < p->numseq; i++) lmax = std::max(lmax, (double)p->lens[i]);
+        const double root = lmax * (1.0 + 0.1 * std::sqrt((double)p->numseq));
+        // (... and for big jobs with a consistency table: the votes of their top tasks share by member ranges from 20 workgroups on)
+        const bool big_cons = p->cons_K > 0 && p->numseq >= 2048;
+        p->max_cluster = p->env.max_cluster > 0 ? std::min(32, p->env.max_cluster) : ((root * root >= 6e7 || big_cons) ? 32 : 16);
+        if (p->shared_gpu) p->max_cluster = 1;
+}
+
+// workgroup tables, one per dependency level (build_blocks)
+static void build_level_tables(KaPlan* p)
+{
+        p->blocks_flat.clear(); p->blocks_off.assign(1, 0); p->level_lean.clear();
+        for (auto& L : p->plan_levels) {
                 std::vector<int2> tbl;
                 int lean = 0;
-                build_blocks(c, L, tbl, &lean);
-                c->level_lean.push_back(lean);
-                c->blocks_flat.insert(c->blocks_flat.end(), tbl.begin(), tbl.end());
-                c->blocks_off.push_back((int)c->blocks_flat.size());
+                build_blocks(p, L, tbl, &lean);
+                p->level_lean.push_back(lean);
+                p->blocks_flat.insert(p->blocks_flat.end(), tbl.begin(), tbl.end());
+                p->blocks_off.push_back((int)p->blocks_flat.size());
         }
+}
 
-        c->queue_off = (int)c->blocks_flat.size(); c->queue_n = 0;
-        if (c->queue_first >= 0) {
-                // Within a level the tasks with the longest way to the root go first (estimated wavefront steps of the task and of
-                // everything above it, as for the chain's spare workgroups below): what the chained launch waits for longest -- the
-                // spine of a caterpillar tree -- then leaves the queue early instead of wherever the task list put it.  KA_QORDER=0: list order.
-                std::vector<double> qlen(2 * numseq - 1, 0.0), qup(n_tasks, 0.0);
-                if (env_int("KA_QORDER", 1)) {
-                        std::vector<double> lmax(2 * numseq - 1, 0.0), nmem(2 * numseq - 1, 1.0);
-                        for (int i = 0; i < numseq; i++) { lmax[i] = c->lens[i]; qlen[i] = c->lens[i]; }
-                        for (int t = 0; t < n_tasks; t++) {
-                                const int a = abc[3 * t], b = abc[3 * t + 1], cc = abc[3 * t + 2];
-                                lmax[cc] = std::max(lmax[a], lmax[b]); nmem[cc] = nmem[a] + nmem[b];
-                                qlen[cc] = lmax[cc] * (1.0 + 0.1 * std::sqrt(nmem[cc]));
-                        }
-                        for (int t = n_tasks - 1; t >= 0; t--) {               // parents come after their children in the task list
-                                const double la = qlen[abc[3 * t]], lb = qlen[abc[3 * t + 1]];
-                                qup[t] = 2.0 * std::max(la, lb) + std::min(la, lb) + ((act(t) && c->descs[t].parent >= 0) ? qup[c->descs[t].parent] : 0.0);
-                        }
-                }
-                if (env_int("KA_QORDER", 1) == 2) {
-                        // experiment (round 6; measured and not kept): ONE order over all the queue's levels, by the way to the root alone.  A
-                        // child's way is longer than its parent's, so the order is still topological (a producer is pulled before its consumer: no
-                        // deadlock) -- the subtrees under the spine go first whatever their level, at the price of consumers pulled right behind
-                        // their producers, whose workgroups then hold a slot and wait: the chain gains 0.3 ms, the queue loses 1.2 (headline
-                        // 14.70 -> 15.45 ms, C3 70.0 -> 77.6, 16384 x 500 41.4 -> 45.7, sixteen trees unchanged; profiles/r06_queue_order.log).
-                        std::vector<int> all;
-                        for (int L = c->queue_first; L < c->chain_level; L++) for (int t : levels[L]) if (!c->spine[t]) all.push_back(t);
-                        std::stable_sort(all.begin(), all.end(), [&](int x, int y) { return qup[x] > qup[y]; });
-                        for (int t : all) { c->blocks_flat.push_back(make_int2(t, 1 << 8)); c->queue_n++; }
-                } else
-                for (int L = c->queue_first; L < c->chain_level; L++) {
-                        std::vector<int> lv;
-                        for (int t : levels[L]) if (!c->spine[t]) lv.push_back(t);       // (the spines' tasks run in the chained launch)
-                        std::stable_sort(lv.begin(), lv.end(), [&](int x, int y) { return qup[x] > qup[y]; });
-                        for (int t : lv) { c->blocks_flat.push_back(make_int2(t, 1 << 8)); c->queue_n++; }
-                }
+// The queue's task list.  Within a level the tasks with the longest way to the root go first (estimated wavefront steps of the task
+// and of everything above it, as for the chain's spare workgroups below): what the chained launch waits for longest -- the
+// spine of a caterpillar tree -- then leaves the queue early instead of wherever the task list put it.  KA_QORDER=0: list order.
+static void order_queue(KaPlan* p, const PlanWork& w)
+{
+        p->queue_off = (int)p->blocks_flat.size(); p->queue_n = 0;
+        if (p->queue_first < 0) return;
+        const bool by_way = p->env.qorder != 0;
+        auto longer_way = [&](int x, int y) { return by_way && w.way_sqrt[x] > w.way_sqrt[y]; };
+        // KA_QORDER=2, an experiment (round 6; measured and not kept): ONE order over all the queue's levels, by the way to the root alone.  A
+        // child's way is longer than its parent's, so the order is still topological (a producer is pulled before its consumer: no
+        // deadlock) -- the subtrees under the spine go first whatever their level, at the price of consumers pulled right behind
+        // their producers, whose workgroups then hold a slot and wait: the chain gains 0.3 ms, the queue loses 1.2 (headline
+        // 14.70 -> 15.45 ms, C3 70.0 -> 77.6, 16384 x 500 41.4 -> 45.7, sixteen trees unchanged; profiles/r06_queue_order.log).
+        const bool one_order = p->env.qorder == 2;
+        std::vector<int> run;
+        for (int L = p->queue_first; L < p->chain_level; L++) {
+                for (int t : p->plan_levels[L]) if (!p->spine[t]) run.push_back(t);       // (the spines' tasks run in the chained launch)
+                if (one_order && L + 1 < p->chain_level) continue;
+                std::stable_sort(run.begin(), run.end(), longer_way);
+                for (int t : run) { p->blocks_flat.push_back(make_int2(t, 1 << 8)); p->queue_n++; }
+                run.clear();
         }
-        if (c->chain_level >= 0) {
-                // Every task of the chain's first level starts on a single workgroup; clusters form on the way up.
-                // Entries are laid out in depth-first order of the upper tree, one contiguous run per XCD
-                // (block b runs on XCD b % 8 -- observed, not contractual): subtrees that merge early share an
-                // L2, only the top three levels cross XCDs.
-                std::vector<int> task_of((2 * numseq - 1), -1), order;
-                for (int t = 0; t < n_tasks; t++) task_of[abc[3 * t + 2]] = t;
-                std::vector<int> stack;
-                auto inchain2 = [&](int t) { return t >= 0 && act(t) && (c->task_level[t] >= c->chain_level || c->spine[t]); };
-                for (int t = n_tasks - 1; t >= 0; t--) if (act(t) && c->descs[t].parent < 0 && c->task_level[t] >= c->chain_level) stack.push_back(t);   // every root above the cut
-                while (!stack.empty()) {
-                        const int t = stack.back(); stack.pop_back();
-                        // an entry of the chain: no child of it runs inside the launch (the chain's first level -- unless a spine hangs below
-                        // it --, the lowest task of a spine; in a plan over a subset also a task whose children were all run before)
-                        if (c->descs[t].chain_need == 0) { order.push_back(t); continue; }
-                        for (int k = 1; k >= 0; k--) {
-                                const int ch = abc[3 * t + k];
-                                if (ch >= numseq && inchain2(task_of[ch])) stack.push_back(task_of[ch]);
-                        }
-                }
-                const int m = ((int)order.size() + 7) / 8;
-                // A narrow upper tree (the chain-like UPGMA trees of a realignment pass) never merges clusters: its
-                // tasks would all run on the one workgroup they started with.  Start with as many workgroups per
-                // task as a separate launch of this level would get (build_blocks); members of one cluster sit in
-                // one column = one XCD.
-                int G0 = 1;
-                while (G0 * 2 <= c->max_cluster && 8 * m * G0 * 2 <= c->n_cus) G0 *= 2;
-                if (c->env.chain_g1) G0 = 1;
-                // The CUs this leaves idle go to the entries whose way to the root is the longest (estimated wavefront steps
-                // of the tasks above them): clusters only grow where subtrees of the SAME launch meet, and the critical path
-                // of a k-means tree is a caterpillar that absorbs small subtrees finished by earlier launches -- its tasks
-                // would run on the one workgroup their entry started with while most of the GPU waits at join points.  A
-                // cluster keeps its workgroups all the way up (surplus members climb with it), so a workgroup given to an
-                // entry serves every task on that entry's path.  Extra members sit behind the regular table, in the
-                // entry's XCD column.
-                std::vector<int> extra(order.size(), 0);
-                int spare = (c->n_cus - 8 * m * G0) / 8 * 8;
-                if (!c->env.no_crit && spare > 0 && !order.empty()) {
-                        std::vector<double> len(2 * numseq - 1, 0.0), up(n_tasks, 0.0);
-                        for (int i = 0; i < numseq; i++) len[i] = c->lens[i];
-                        if (c->env.crit_greedy) {
-                                // profile lengths are only known on the device; the estimate: the longest member sequence times
-                                // (1 + 0.1 sqrt(members)) -- the growth of the DSSim sets with their indel-rich tails (13151 columns for
-                                // 4096 x 2000 nt, 2965 for 4096 x 400 aa), harmless where alignments stay shorter
-                                std::vector<double> lmax(2 * numseq - 1, 0.0), nmem(2 * numseq - 1, 1.0);
-                                for (int i = 0; i < numseq; i++) lmax[i] = c->lens[i];
-                                for (int t = 0; t < n_tasks; t++) {
-                                        const int a = abc[3 * t], b = abc[3 * t + 1], cc = abc[3 * t + 2];
-                                        lmax[cc] = std::max(lmax[a], lmax[b]); nmem[cc] = nmem[a] + nmem[b];
-                                        len[cc] = lmax[cc] * (1.0 + 0.1 * std::sqrt(nmem[cc]));
-                                }
-                        } else
-                        for (int t = 0; t < n_tasks; t++) len[abc[3 * t + 2]] = 1.1 * std::max(len[abc[3 * t]], len[abc[3 * t + 1]]);
-                        for (int t = n_tasks - 1; t >= 0; t--) {               // parents come after their children in the task list
-                                const double la = len[abc[3 * t]], lb = len[abc[3 * t + 1]];
-                                up[t] = 2.0 * std::max(la, lb) + std::min(la, lb) + (c->descs[t].parent >= 0 ? up[c->descs[t].parent] : 0.0);
-                        }
-                        // Round 4: first a GREEDY pass on a simulated schedule.  The ranking below only knows how LONG an entry's way
-                        // to the root is, not how it will be staffed: a caterpillar spine that absorbs siblings finished by earlier
-                        // launches stays on the one workgroup of its entry through level after level of 2400 x 2300 tasks (C3: six
-                        // of them at 3.8 ms, a third of the launch, next to ~200 idle CUs) while a spine fed by subtrees of THIS
-                        // launch collects their workgroups at every join.  Model: a task on G workgroups takes
-                        // a * (2 max + min) + b * la * lb / G (fitted on C3's and the headline's task times: the first term the
-                        // wavefront's dependent steps, the second the cells shared by the cluster; b / a = 0.02 from the fit, 0.01 in use), a parent has the
-                        // workgroups of its children in this launch (up to the limit) and starts when the later one ends.  One spare
-                        // workgroup at a time goes to the entry under the simulated critical path, until it stops paying; what is
-                        // left goes out by the ranking.  KA_CRIT_GREEDY=0: the ranking alone (round 3).
-                        if (c->env.crit_greedy) {
-                                std::vector<int> entry_of(n_tasks, -1);
-                                for (size_t r = 0; r < order.size(); r++) entry_of[order[r]] = (int)r;
-                                auto in_chain = [&](int t) { return inchain2(t); };
-                                std::vector<double> fin(n_tasks, 0.0);
-                                std::vector<int> Gt(n_tasks, 0), crit_child(n_tasks, -1);
-                                const double ba = 1e-3 * (double)env_int("KA_CRIT_BA", 10);   // (b / a of the model, per mille; 10 from a sweep over five job shapes, profiles/r04_crit_ba.log)
-                                auto simulate = [&]() -> int {
-                                        int last = -1;
-                                        for (int t = 0; t < n_tasks; t++) {                  // children come before their parents
-                                                if (!in_chain(t)) continue;
-                                                double start = 0.0; int cc = -1, G = 0;
-                                                if (entry_of[t] >= 0) G = G0 + extra[entry_of[t]];
-                                                else {
-                                                        for (int k = 0; k < 2; k++) {
-                                                                const int ch = abc[3 * t + k];
-                                                                const int tc = ch >= numseq ? task_of[ch] : -1;
-                                                                if (!in_chain(tc)) continue;
-                                                                G += Gt[tc];
-                                                                if (fin[tc] >= start) { start = fin[tc]; cc = tc; }
-                                                        }
-                                                        G = std::max(1, std::min(G, c->max_cluster));
-                                                }
-                                                const double la = len[abc[3 * t]], lb = len[abc[3 * t + 1]];
-                                                fin[t] = start + 2.0 * std::max(la, lb) + std::min(la, lb) + ba * la * lb / G;
-                                                Gt[t] = G; crit_child[t] = cc;
-                                                if (last < 0 || fin[t] > fin[last]) last = t;
-                                        }
-                                        return last;                                       // the task that ends last (a root)
-                                };
-                                // (several paths can be critical at once: a workgroup that shortens ONE of them leaves the end where it was.
-                                // Keep going -- the next round takes the next path -- and fall back to the best state seen when a
-                                // stretch of eight additions has not moved the end.)
-                                int given = 0, since_best = 0;
-                                std::vector<int> best_extra = extra;
-                                int best_spare = spare;
-                                double best_end = -1.0;
-                                { const int t = simulate(); if (t >= 0) best_end = fin[t]; }
-                                while (spare > 0 && best_end > 0.0 && since_best < 8) {
-                                        int t = simulate();
-                                        if (t < 0) break;
-                                        while (crit_child[t] >= 0) t = crit_child[t];        // down the critical path to its entry
-                                        const int r = entry_of[t];
-                                        if (r < 0 || G0 + extra[r] >= c->max_cluster) break;
-                                        extra[r] += 1; spare -= 1;
-                                        const int t2 = simulate();
-                                        if (fin[t2] < best_end * (1.0 - 1e-4)) { best_end = fin[t2]; best_extra = extra; best_spare = spare; since_best = 0; }
-                                        else since_best += 1;
-                                }
-                                extra = best_extra; spare = best_spare;
-                                for (size_t r = 0; r < order.size(); r++) given += extra[r];
-                                if (getenv("KA_PLAN_VERBOSE")) {
-                                        const int t = simulate();
-                                        fprintf(stderr, "chain plan: greedy pass gave %d workgroups, %d left for the ranking; simulated end %.0f\n", given, spare, t >= 0 ? fin[t] : 0.0);
-                                        for (size_t r = 0; r < order.size(); r++) if (extra[r] > 0)
-                                                fprintf(stderr, "  entry task %d (node %d) level %d: +%d\n", order[r], abc[3 * order[r] + 2], c->task_level[order[r]], extra[r]);
-                                }
-                        }
-                        std::vector<int> by_up(order.size());
-                        for (size_t r = 0; r < order.size(); r++) by_up[r] = (int)r;
-                        std::stable_sort(by_up.begin(), by_up.end(), [&](int x, int y) { return up[order[x]] > up[order[y]]; });
-                        int top_g = 4;
-                        if (c->env.crit_top > 0) top_g = std::min(c->max_cluster, c->env.crit_top);   // experiments
-                        for (size_t i = 0; i < by_up.size() && spare > 0; i++) {
-                                // (never beyond the cluster limit: surplus workgroups would only spin at a join and leave)
-                                const int want = std::min(spare, std::max(0, std::min(c->max_cluster, i == 0 ? top_g : 2 * G0) - G0 - extra[by_up[i]]));
-                                extra[by_up[i]] += want; spare -= want;
-                        }
-                        if (getenv("KA_PLAN_VERBOSE")) {
-                                fprintf(stderr, "chain plan: level %d, %zu entries, G0 %d, spare after extras %d, top_g %d\n", c->chain_level, order.size(), G0, spare, top_g);
-                                for (size_t i = 0; i < by_up.size() && i < 12; i++) {
-                                        const int t = order[by_up[i]];
-                                        fprintf(stderr, "  rank %zu: task %d (node %d) level %d lens %.0f x %.0f up %.0f extra %d\n", i, t, abc[3 * t + 2], c->task_level[t],
-                                                len[abc[3 * t]], len[abc[3 * t + 1]], up[t], extra[by_up[i]]);
-                                }
-                        }
-                }
-                // CUs KEPT FOR THE HEAD OF THE CHAIN (round 6; KA_RESERVE = 8 / 16 / 24; built, measured, OFF: the spine then starts 1 ms earlier and the run is as long -- other chains of the same length take over).  The chained launch goes out beside the
-                // queued one, but a workgroup of it wants a CU's whole LDS and the queue's 512 persistent workgroups hold two to a CU until
-                // their list is empty: the chain only ever started when the queue was over (the spine's first chained task of the headline
-                // tree waited 1.0 ms for a CU for its cluster's second workgroup; tools/levels_real.py, `prep`).  Now the queue's workgroups
-                // that find themselves on the first R CUs of XCC 0 (shader engines 0 .. R/8 - 1; ka_task_queue_entry reads HW_ID / XCC_ID)
-                // leave at once, and the chain's most critical entries -- by their estimated way to the root, all their workgroups, as
-                // many as fit R -- sit at the head of column 0 of the block table: block b goes to XCC b % 8 (tools/microbench/cu_map.hip:
-                // 0 exceptions in 512), XCC 0 dispatches its share of the chain in order onto the CUs the queue left, and those
-                // workgroups wait for their operands' done flags instead of for a CU (they do not help the queue: KA_BLK_NOHELP).
-                c->reserve_cus = 0;
-                int front_n = 0;
-                {
-                        int R = env_int("KA_RESERVE", 0);              // (measured: no gain -- DESIGN 4j; off)
-                        R = std::max(0, std::min(24, R / 8 * 8));
-                        if (R > 0 && c->overlap_plan && c->queue_first >= 0 && c->n_trees <= 1 && !subset && (int)order.size() > 8 && !c->env.no_crit) {
-                                std::vector<double> lmax(2 * numseq - 1, 0.0), nmem(2 * numseq - 1, 1.0), qlen(2 * numseq - 1, 0.0), crit(n_tasks, 0.0);
-                                for (int i = 0; i < numseq; i++) { lmax[i] = c->lens[i]; qlen[i] = c->lens[i]; }
-                                for (int t = 0; t < n_tasks; t++) {
-                                        const int a = abc[3 * t], b = abc[3 * t + 1], cc = abc[3 * t + 2];
-                                        lmax[cc] = std::max(lmax[a], lmax[b]); nmem[cc] = nmem[a] + nmem[b];
-                                        qlen[cc] = lmax[cc] * (1.0 + 0.1 * std::sqrt(nmem[cc]));
-                                }
-                                for (int t = n_tasks - 1; t >= 0; t--) {
-                                        const double la = qlen[abc[3 * t]], lb = qlen[abc[3 * t + 1]];
-                                        crit[t] = 2.0 * std::max(la, lb) + std::min(la, lb) + ((act(t) && c->descs[t].parent >= 0) ? crit[c->descs[t].parent] : 0.0);
-                                }
-                                std::vector<int> idx(order.size());
-                                for (size_t r = 0; r < order.size(); r++) idx[r] = (int)r;
-                                // (the lowest tasks of the spines first: they are what the kept CUs are for; a 430-row task uses two workgroups)
-                                for (size_t r = 0; r < order.size(); r++) if (c->task_level[order[r]] < c->chain_level) { crit[order[r]] += 1e12; extra[r] = std::min(extra[r], 1); }
-                                std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return crit[order[x]] > crit[order[y]]; });
-                                std::vector<char> is_front(order.size(), 0);
-                                std::vector<int> front;
-                                int used = 0;
-                                for (int r : idx) {
-                                        const int Gr = G0 + extra[r];
-                                        if (used + Gr > R || (int)front.size() + 1 > m) break;
-                                        front.push_back(r); is_front[r] = 1; used += Gr;
-                                }
-                                if (!front.empty()) {
-                                        std::vector<int> o2, e2;
-                                        for (int r : front) { o2.push_back(order[r]); e2.push_back(extra[r]); }
-                                        for (size_t r = 0; r < order.size(); r++) if (!is_front[r]) { o2.push_back(order[r]); e2.push_back(extra[r]); }
-                                        order.swap(o2); extra.swap(e2);
-                                        front_n = (int)front.size();
-                                        c->reserve_cus = R;
-                                }
-                        }
-                }
-                int n_extra = 0;
-                std::vector<int> col_need(8, 0);
-                for (size_t r = 0; r < order.size(); r++) { n_extra += extra[r]; col_need[r / m] += extra[r]; }
-                int extra_rows = *std::max_element(col_need.begin(), col_need.end());
-                const bool by_column = 8 * m * G0 + 8 * extra_rows <= c->n_cus;       // else: packed densely, any XCD
-                if (!by_column) extra_rows = (n_extra + 7) / 8;
-                c->chain_blocks.assign((size_t)8 * m * G0 + (size_t)8 * extra_rows, make_int2(-1, 0));
-                std::vector<int> col_fill(8, 0);
-                int dense = 0;
-                for (int r = 0; r < (int)order.size(); r++) {
-                        const int Gr = G0 + extra[r];
-                        for (int g = 0; g < G0; g++)
-                                c->chain_blocks[((size_t)(r % m) * G0 + g) * 8 + (r / m)] = make_int2(order[r], g | (Gr << 8));
-                        for (int g = G0; g < Gr; g++) {
-                                const size_t pos = (size_t)8 * m * G0 + (by_column ? (size_t)8 * col_fill[r / m]++ + (r / m) : (size_t)dense++);
-                                c->chain_blocks[pos] = make_int2(order[r], g | (Gr << 8));
-                        }
-                }
-                if (front_n > 0) {
-                        // The front entries' workgroups -- ALL of them: their extra members sit behind the regular table, in whatever column --
-                        // trade places with what the head of column 0 holds (a swap: every column keeps its number of workgroups, and with it
-                        // the guarantee that the whole launch is resident at once).
-                        std::vector<size_t> col0;
-                        for (size_t p = 0; p < c->chain_blocks.size(); p += 8) if (c->chain_blocks[p].x >= 0) col0.push_back(p);
-                        size_t i = 0;
-                        bool ok = true;
-                        for (int r = 0; r < front_n && ok; r++)
-                                for (int g = 0; g < G0 + extra[r] && ok; g++, i++) {
-                                        size_t src = c->chain_blocks.size();
-                                        for (size_t p = 0; p < c->chain_blocks.size(); p++)
-                                                if (c->chain_blocks[p].x == order[r] && (c->chain_blocks[p].y & 0xff) == g) { src = p; break; }
-                                        if (src == c->chain_blocks.size() || i >= col0.size()) { ok = false; break; }
-                                        std::swap(c->chain_blocks[col0[i]], c->chain_blocks[src]);
-                                        c->chain_blocks[col0[i]].y |= KA_BLK_NOHELP;
-                                }
-                        if (!ok) { c->reserve_cus = 0; for (auto& bb : c->chain_blocks) if (bb.x >= 0) bb.y &= ~KA_BLK_NOHELP; }
-                } else c->reserve_cus = 0;
-                if (getenv("KA_PLAN_VERBOSE")) fprintf(stderr, "chain plan: %d CUs kept for the head of the chain, %d front entries, m %d, G0 %d, by_column %d, overlap %d, queue_first %d\n",
-                                                       c->reserve_cus, front_n, m, G0, (int)by_column, c->overlap_plan, c->queue_first);
-                c->chain_blocks_off = (int)c->blocks_flat.size();
-                c->blocks_flat.insert(c->blocks_flat.end(), c->chain_blocks.begin(), c->chain_blocks.end());
-        }
+}
 
+// Every task of the chain's first level starts on a single workgroup; clusters form on the way up.
+// Entries are laid out in depth-first order of the upper tree, one contiguous run per XCD
+// (block b runs on XCD b % 8 -- observed, not contractual): subtrees that merge early share an
+// L2, only the top three levels cross XCDs.
+static void enter_chain(const KaPlan* p, PlanWork& w)
+{
+        std::vector<int> stack;
+        for (int t = p->n_tasks - 1; t >= 0; t--) if (act(p, t) && p->descs[t].parent < 0 && p->task_level[t] >= p->chain_level) stack.push_back(t);   // every root above the cut
+        while (!stack.empty()) {
+                const int t = stack.back(); stack.pop_back();
+                // an entry of the chain: no child of it runs inside the launch (the chain's first level -- unless a spine hangs below
+                // it --, the lowest task of a spine; in a plan over a subset also a task whose children were all run before)
+                if (p->descs[t].chain_need == 0) { w.order.push_back(t); continue; }
+                for (int k = 1; k >= 0; k--) {
+                        const int ch = p->abc[3 * t + k];
+                        if (ch >= p->numseq && in_chain(p, w.task_of[ch])) stack.push_back(w.task_of[ch]);
+                }
+        }
+        w.m = ((int)w.order.size() + 7) / 8;
+        w.extra.assign(w.order.size(), 0);
+        // A narrow upper tree (the chain-like UPGMA trees of a realignment pass) never merges clusters: its
+        // tasks would all run on the one workgroup they started with.  Start with as many workgroups per
+        // task as a separate launch of this level would get (build_blocks); members of one cluster sit in
+        // one column = one XCD.
+        w.G0 = 1;
+        while (w.G0 * 2 <= p->max_cluster && 8 * w.m * w.G0 * 2 <= p->n_cus) w.G0 *= 2;
+        if (p->env.chain_g1) w.G0 = 1;
+        w.spare = (p->n_cus - 8 * w.m * w.G0) / 8 * 8;
+}
+
+// Round 4: first a GREEDY pass on a simulated schedule.  The ranking below only knows how LONG an entry's way
+// to the root is, not how it will be staffed: a caterpillar spine that absorbs siblings finished by earlier
+// launches stays on the one workgroup of its entry through level after level of 2400 x 2300 tasks (C3: six
+// of them at 3.8 ms, a third of the launch, next to ~200 idle CUs) while a spine fed by subtrees of THIS
+// launch collects their workgroups at every join.  Model: a task on G workgroups takes
+// a * (2 max + min) + b * la * lb / G (fitted on C3's and the headline's task times: the first term the
+// wavefront's dependent steps, the second the cells shared by the cluster; b / a = 0.02 from the fit, 0.01 in use), a parent has the
+// workgroups of its children in this launch (up to the limit) and starts when the later one ends.  One spare
+// workgroup at a time goes to the entry under the simulated critical path, until it stops paying; what is
+// left goes out by the ranking.  KA_CRIT_GREEDY=0: the ranking alone (round 3).
+static void spare_by_simulation(const KaPlan* p, PlanWork& w, const std::vector<double>& len)
+{
+        const int numseq = p->numseq, n_tasks = p->n_tasks;
+        const int* abc = p->abc.data();
+        std::vector<int>& extra = w.extra;
+        std::vector<int> entry_of(n_tasks, -1);
+        for (size_t r = 0; r < w.order.size(); r++) entry_of[w.order[r]] = (int)r;
+        std::vector<double> fin(n_tasks, 0.0);
+        std::vector<int> Gt(n_tasks, 0), crit_child(n_tasks, -1);
+        const double ba = 1e-3 * (double)p->env.crit_ba;   // (b / a of the model, per mille; 10 from a sweep over five job shapes, profiles/r04_crit_ba.log)
+        auto simulate = [&]() -> int {
+                int last = -1;
+                for (int t = 0; t < n_tasks; t++) {                  // children come before their parents
+                        if (!in_chain(p, t)) continue;
+                        double start = 0.0; int cc = -1, G = 0;
+                        if (entry_of[t] >= 0) G = w.G0 + extra[entry_of[t]];
+                        else {
+                                for (int k = 0; k < 2; k++) {
+                                        const int ch = abc[3 * t + k];
+                                        const int tc = ch >= numseq ? w.task_of[ch] : -1;
+                                        if (!in_chain(p, tc)) continue;
+                                        G += Gt[tc];
+                                        if (fin[tc] >= start) { start = fin[tc]; cc = tc; }
+                                }
+                                G = std::max(1, std::min(G, p->max_cluster));
+                        }
+                        const double la = len[abc[3 * t]], lb = len[abc[3 * t + 1]];
+                        fin[t] = start + 2.0 * std::max(la, lb) + std::min(la, lb) + ba * la * lb / G;
+                        Gt[t] = G; crit_child[t] = cc;
+                        if (last < 0 || fin[t] > fin[last]) last = t;
+                }
+                return last;                                       // the task that ends last (a root)
+        };
+        // (several paths can be critical at once: a workgroup that shortens ONE of them leaves the end where it was.
+        // Keep going -- the next round takes the next path -- and fall back to the best state seen when a
+        // stretch of eight additions has not moved the end.)
+        int given = 0, since_best = 0;
+        std::vector<int> best_extra = extra;
+        int best_spare = w.spare;
+        double best_end = -1.0;
+        { const int t = simulate(); if (t >= 0) best_end = fin[t]; }
+        while (w.spare > 0 && best_end > 0.0 && since_best < 8) {
+                int t = simulate();
+                if (t < 0) break;
+                while (crit_child[t] >= 0) t = crit_child[t];        // down the critical path to its entry
+                const int r = entry_of[t];
+                if (r < 0 || w.G0 + extra[r] >= p->max_cluster) break;
+                extra[r] += 1; w.spare -= 1;
+                const int t2 = simulate();
+                if (fin[t2] < best_end * (1.0 - 1e-4)) { best_end = fin[t2]; best_extra = extra; best_spare = w.spare; since_best = 0; }
+                else since_best += 1;
+        }
+        extra = best_extra; w.spare = best_spare;
+        for (size_t r = 0; r < w.order.size(); r++) given += extra[r];
+        if (p->env.plan_verbose) {
+                const int t = simulate();
+                fprintf(stderr, "chain plan: greedy pass gave %d workgroups, %d left for the ranking; simulated end %.0f\n", given, w.spare, t >= 0 ? fin[t] : 0.0);
+                for (size_t r = 0; r < w.order.size(); r++) if (extra[r] > 0)
+                        fprintf(stderr, "  entry task %d (node %d) level %d: +%d\n", w.order[r], abc[3 * w.order[r] + 2], p->task_level[w.order[r]], extra[r]);
+        }
+}
+
+// ... then the ranking: what is left goes to the entries in the order of their way to the root
+static void spare_by_ranking(const KaPlan* p, PlanWork& w, const std::vector<double>& len, const std::vector<double>& up)
+{
+        const int* abc = p->abc.data();
+        std::vector<int> by_up(w.order.size());
+        for (size_t r = 0; r < w.order.size(); r++) by_up[r] = (int)r;
+        std::stable_sort(by_up.begin(), by_up.end(), [&](int x, int y) { return up[w.order[x]] > up[w.order[y]]; });
+        int top_g = 4;
+        if (p->env.crit_top > 0) top_g = std::min(p->max_cluster, p->env.crit_top);   // experiments
+        for (size_t i = 0; i < by_up.size() && w.spare > 0; i++) {
+                // (never beyond the cluster limit: surplus workgroups would only spin at a join and leave)
+                const int want = std::min(w.spare, std::max(0, std::min(p->max_cluster, i == 0 ? top_g : 2 * w.G0) - w.G0 - w.extra[by_up[i]]));
+                w.extra[by_up[i]] += want; w.spare -= want;
+        }
+        if (p->env.plan_verbose) {
+                fprintf(stderr, "chain plan: level %d, %zu entries, G0 %d, spare after extras %d, top_g %d\n", p->chain_level, w.order.size(), w.G0, w.spare, top_g);
+                for (size_t i = 0; i < by_up.size() && i < 12; i++) {
+                        const int t = w.order[by_up[i]];
+                        fprintf(stderr, "  rank %zu: task %d (node %d) level %d lens %.0f x %.0f up %.0f extra %d\n", i, t, abc[3 * t + 2], p->task_level[t],
+                                len[abc[3 * t]], len[abc[3 * t + 1]], up[t], w.extra[by_up[i]]);
+                }
+        }
+}
+
+// The CUs the entries leave idle go to the entries whose way to the root is the longest (estimated wavefront steps
+// of the tasks above them): clusters only grow where subtrees of the SAME launch meet, and the critical path
+// of a k-means tree is a caterpillar that absorbs small subtrees finished by earlier launches -- its tasks
+// would run on the one workgroup their entry started with while most of the GPU waits at join points.  A
+// cluster keeps its workgroups all the way up (surplus members climb with it), so a workgroup given to an
+// entry serves every task on that entry's path.  Extra members sit behind the regular table, in the
+// entry's XCD column.
+static void give_spare_workgroups(const KaPlan* p, PlanWork& w)
+{
+        if (p->env.no_crit || w.spare <= 0 || w.order.empty()) return;
+        // (the greedy pass and the ranking behind it read the square-root model; KA_CRIT_GREEDY=0, the ranking alone, the compounding one)
+        const std::vector<double>& len = p->env.crit_greedy ? w.len_sqrt : w.len_11;
+        const std::vector<double>& up = p->env.crit_greedy ? w.way_sqrt : w.way_11;
+        if (p->env.crit_greedy) spare_by_simulation(p, w, len);
+        spare_by_ranking(p, w, len, up);
+}
+
+// CUs KEPT FOR THE HEAD OF THE CHAIN (round 6; KA_RESERVE = 8 / 16 / 24; built, measured, OFF: the spine then starts 1 ms earlier and the run is as long -- other chains of the same length take over).  The chained launch goes out beside the
+// queued one, but a workgroup of it wants a CU's whole LDS and the queue's 512 persistent workgroups hold two to a CU until
+// their list is empty: the chain only ever started when the queue was over (the spine's first chained task of the headline
+// tree waited 1.0 ms for a CU for its cluster's second workgroup; tools/levels_real.py, `prep`).  Now the queue's workgroups
+// that find themselves on the first R CUs of XCC 0 (shader engines 0 .. R/8 - 1; ka_task_queue_entry reads HW_ID / XCC_ID)
+// leave at once, and the chain's most critical entries -- by their estimated way to the root, all their workgroups, as
+// many as fit R -- sit at the head of column 0 of the block table: block b goes to XCC b % 8 (tools/microbench/cu_map.hip:
+// 0 exceptions in 512), XCC 0 dispatches its share of the chain in order onto the CUs the queue left, and those
+// workgroups wait for their operands' done flags instead of for a CU (they do not help the queue: KA_BLK_NOHELP).
+// This step picks the front entries and moves them to the head of the order (it also trims the spare workgroups of spine entries,
+// so it runs before the layout); lay_out_chain puts their workgroups at the head of column 0.
+static void reserve_front(KaPlan* p, PlanWork& w)
+{
+        p->reserve_cus = 0;
+        w.front_n = 0;
+        const int R = p->env.reserve;                     // (measured: no gain -- DESIGN 4j; off)
+        if (R <= 0 || !p->overlap_plan || p->queue_first < 0 || p->n_trees > 1 || !p->plan_active.empty() || (int)w.order.size() <= 8 || p->env.no_crit) return;
+        std::vector<double> crit(w.way_sqrt);
+        std::vector<int> idx(w.order.size());
+        for (size_t r = 0; r < w.order.size(); r++) idx[r] = (int)r;
+        // (the lowest tasks of the spines first: they are what the kept CUs are for; a 430-row task uses two workgroups)
+        for (size_t r = 0; r < w.order.size(); r++) if (p->task_level[w.order[r]] < p->chain_level) { crit[w.order[r]] += 1e12; w.extra[r] = std::min(w.extra[r], 1); }
+        std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return crit[w.order[x]] > crit[w.order[y]]; });
+        std::vector<char> is_front(w.order.size(), 0);
+        std::vector<int> front;
+        int used = 0;
+        for (int r : idx) {
+                const int Gr = w.G0 + w.extra[r];
+                if (used + Gr > R || (int)front.size() + 1 > w.m) break;
+                front.push_back(r); is_front[r] = 1; used += Gr;
+        }
+        if (front.empty()) return;
+        std::vector<int> o2, e2;
+        for (int r : front) { o2.push_back(w.order[r]); e2.push_back(w.extra[r]); }
+        for (size_t r = 0; r < w.order.size(); r++) if (!is_front[r]) { o2.push_back(w.order[r]); e2.push_back(w.extra[r]); }
+        w.order.swap(o2); w.extra.swap(e2);
+        w.front_n = (int)front.size();
+        p->reserve_cus = R;
+}
+
+// the chained launch's block table: 8 XCD columns of m entries with G0 workgroups each, the spare workgroups behind them
+static void lay_out_chain(KaPlan* p, PlanWork& w)
+{
+        const int m = w.m, G0 = w.G0;
+        int n_extra = 0;
+        std::vector<int> col_need(8, 0);
+        for (size_t r = 0; r < w.order.size(); r++) { n_extra += w.extra[r]; col_need[r / m] += w.extra[r]; }
+        int extra_rows = *std::max_element(col_need.begin(), col_need.end());
+        const bool by_column = 8 * m * G0 + 8 * extra_rows <= p->n_cus;       // else: packed densely, any XCD
+        if (!by_column) extra_rows = (n_extra + 7) / 8;
+        p->chain_blocks.assign((size_t)8 * m * G0 + (size_t)8 * extra_rows, make_int2(-1, 0));
+        std::vector<int> col_fill(8, 0);
+        int dense = 0;
+        for (int r = 0; r < (int)w.order.size(); r++) {
+                const int Gr = G0 + w.extra[r];
+                for (int g = 0; g < G0; g++)
+                        p->chain_blocks[((size_t)(r % m) * G0 + g) * 8 + (r / m)] = make_int2(w.order[r], g | (Gr << 8));
+                for (int g = G0; g < Gr; g++) {
+                        const size_t pos = (size_t)8 * m * G0 + (by_column ? (size_t)8 * col_fill[r / m]++ + (r / m) : (size_t)dense++);
+                        p->chain_blocks[pos] = make_int2(w.order[r], g | (Gr << 8));
+                }
+        }
+        if (w.front_n > 0) {
+                // The front entries' workgroups -- ALL of them: their extra members sit behind the regular table, in whatever column --
+                // trade places with what the head of column 0 holds (a swap: every column keeps its number of workgroups, and with it
+                // the guarantee that the whole launch is resident at once).
+                std::vector<size_t> col0;
+                for (size_t q = 0; q < p->chain_blocks.size(); q += 8) if (p->chain_blocks[q].x >= 0) col0.push_back(q);
+                size_t i = 0;
+                bool ok = true;
+                for (int r = 0; r < w.front_n && ok; r++)
+                        for (int g = 0; g < G0 + w.extra[r] && ok; g++, i++) {
+                                size_t src = p->chain_blocks.size();
+                                for (size_t q = 0; q < p->chain_blocks.size(); q++)
+                                        if (p->chain_blocks[q].x == w.order[r] && (p->chain_blocks[q].y & 0xff) == g) { src = q; break; }
+                                if (src == p->chain_blocks.size() || i >= col0.size()) { ok = false; break; }
+                                std::swap(p->chain_blocks[col0[i]], p->chain_blocks[src]);
+                                p->chain_blocks[col0[i]].y |= KA_BLK_NOHELP;
+                        }
+                if (!ok) { p->reserve_cus = 0; for (auto& bb : p->chain_blocks) if (bb.x >= 0) bb.y &= ~KA_BLK_NOHELP; }
+        }
+        if (p->env.plan_verbose) fprintf(stderr, "chain plan: %d CUs kept for the head of the chain, %d front entries, m %d, G0 %d, by_column %d, overlap %d, queue_first %d\n",
+                                         p->reserve_cus, w.front_n, m, G0, (int)by_column, p->overlap_plan, p->queue_first);
+        p->chain_blocks_off = (int)p->blocks_flat.size();
+        p->blocks_flat.insert(p->blocks_flat.end(), p->chain_blocks.begin(), p->chain_blocks.end());
+}
+
+// Launch plan of the prepared job: parents and join counts of the chained launch, workgroup tables per level.
+// Depends on p->shared_gpu (no clusters, no chain), so ka_tree_sync can re-plan after a residency failure.
+int plan_launches(KaPlan* p)
+{
+        PlanWork w;
+        p->plan_levels.assign(p->levels.size(), std::vector<int>());
+        for (size_t L = 0; L < p->levels.size(); L++) for (int t : p->levels[L]) if (act(p, t)) p->plan_levels[L].push_back(t);
+        link_tasks(p, w);
+        estimate(p, w);
+        // which launches there are
+        place_chain(p, w);
+        place_queue(p, w);
+        mark_spines(p, w);
+        set_chain_need(p, w);
+        set_queue_deps(p, w);
+        // their workgroup tables: one per level, the queue's list, the chain's table
+        set_cluster_limit(p);
+        build_level_tables(p);
+        order_queue(p, w);
+        if (p->chain_level >= 0) {
+                enter_chain(p, w);
+                give_spare_workgroups(p, w);
+                reserve_front(p, w);                      // (trims the spare workgroups of spine entries: before the layout)
+                lay_out_chain(p, w);
+        }
         return KA_OK;
 }
 
-extern "C" int ka_tree_upload(ka_ctx* c, int numseq, const uint8_t* codes, const int* off, const int* lens,
-                              const float* seq_distances, int n_tasks, const int* abc,
-                              const float* subm, const float* scal, int flags)
+// Host-side task preparation of an upload: the order checks of the task list, nsip, sip order, gap_scale / subm_offset, levels.
+// Fills the job part of the KaPlan; needs no GPU (ka_tree_upload and ka_debug_plan share it).
+int prepare_tasks(KaPlan* c, int numseq, const int* lens, const float* seq_distances, int n_tasks, const int* abc, const float* scal)
 {
-        if (!c) return fail("null ctx");
-        // n_tasks == numseq-1: one guide tree.  Fewer tasks: a FOREST -- several independent alignments (a batch of
-        // families, ensemble members) scheduled together; every task with no consumer is the root of its tree.
-        if (numseq < 2 || n_tasks < 1 || n_tasks > numseq - 1) return fail("need numseq >= 2 and 1 <= n_tasks <= numseq-1");
-        HIPCHK(hipSetDevice(c->device));
         const int nprof = 2 * numseq - 1;
-        // kalign_run_realign aligns a second time on a new tree with the consistency table of the first pass
-        // (aln_wrap.c:424-431,497-502): same sequences, new task list.  Anything else starts without a table.
-        bool keep_cons = false;
-        if ((flags & KA_FLAG_KEEP_CONSISTENCY) && c->have_job && c->cons_K > 0) {
-                bool same = numseq == c->numseq;
-                for (int i = 0; same && i < numseq; i++)
-                        same = lens[i] == c->lens[i] && off[i] == c->off[i] && memcmp(codes + off[i], c->h_codes.data() + off[i], lens[i]) == 0;
-                if (!same) return fail("KA_FLAG_KEEP_CONSISTENCY: the sequences differ from those the consistency table was built on");
-                keep_cons = true;
-        }
-        c->have_job = false; c->ran = false; c->synced = false; c->state_valid = false;
-        // a join watchdog of an earlier job forced the no-cluster plan: a new job gets the fast plan again (the
-        // fallback is counted, ka_ctx_fallback_runs); a caller's own ka_ctx_set_shared stays
-        // -- unless the fallback before it was a fast-plan job's too: then fallback_hold jobs stay on the shared plan first (ka_tree_sync)
-        if (c->shared_by_fallback) {
-                if (c->fallback_hold > 0) c->fallback_hold--;
-                else { c->shared_gpu = false; c->shared_by_fallback = false; }
-        }
-        if (!keep_cons) c->cons_K = 0;           // a new job starts without a consistency table
-        c->have_colof = false;
-        c->rows_n = 0;
-        c->numseq = numseq; c->n_tasks = n_tasks; c->flags = flags;
+        c->numseq = numseq; c->n_tasks = n_tasks;
         c->lens.assign(lens, lens + numseq);
-        c->off.assign(off, off + numseq);
         c->abc.assign(abc, abc + 3 * n_tasks);
-        memcpy(c->subm, subm, sizeof(c->subm));
-        memcpy(c->scal, scal, sizeof(c->scal));
-        c->sum_len = 0; c->max_len = 0;
-        long long codes_bytes = 0;
-        int max_code = 0;
-        for (int i = 0; i < numseq; i++)
-                for (int j = 0; j < lens[i]; j++) max_code = std::max<int>(max_code, codes[off[i] + j]);
-        if (max_code > 22) return fail("sequence code out of range (alphabet is 0..22)");
-        // nucleotide alphabets use codes 0..4 (alphabet.c:206-245); proteins without B / Z / X only codes 0..19
-        c->nres = (max_code < 5) ? 5 : (max_code < 20 ? 20 : 23);
-        for (int i = 0; i < numseq; i++) {
-                if (lens[i] < 1) return fail("zero-length sequence (the reference removes them before the dispatcher, msa_check.c:66)");
-                c->sum_len += lens[i];
-                c->max_len = std::max(c->max_len, lens[i]);
-                codes_bytes = std::max<long long>(codes_bytes, (long long)off[i] + lens[i]);
-        }
-
-        c->h_codes.assign(codes, codes + codes_bytes);
-        if (seq_distances) c->seq_dist.assign(seq_distances, seq_distances + numseq); else c->seq_dist.clear();
         c->sip_flat.clear(); c->sip_off.assign(nprof, 0);
         for (int i = 0; i < numseq; i++) { c->sip_off[i] = (long long)c->sip_flat.size(); c->sip_flat.push_back(i); }
 
@@ -602,14 +614,72 @@ extern "C" int ka_tree_upload(ka_ctx* c, int numseq, const uint8_t* codes, const
         }
         c->levels.assign(max_level, std::vector<int>());
         for (int t = 0; t < n_tasks; t++) c->levels[level[abc[3 * t + 2]] - 1].push_back(t);
+
+        c->task_level.assign(n_tasks, 0);
+        for (int t = 0; t < n_tasks; t++) c->task_level[t] = level[abc[3 * t + 2]] - 1;
+        return KA_OK;
+}
+
+extern "C" int ka_tree_upload(ka_ctx* c, int numseq, const uint8_t* codes, const int* off, const int* lens,
+                              const float* seq_distances, int n_tasks, const int* abc,
+                              const float* subm, const float* scal, int flags)
+{
+        if (!c) return fail("null ctx");
+        // n_tasks == numseq-1: one guide tree.  Fewer tasks: a FOREST -- several independent alignments (a batch of
+        // families, ensemble members) scheduled together; every task with no consumer is the root of its tree.
+        if (numseq < 2 || n_tasks < 1 || n_tasks > numseq - 1) return fail("need numseq >= 2 and 1 <= n_tasks <= numseq-1");
+        HIPCHK(hipSetDevice(c->device));
+        const int nprof = 2 * numseq - 1;
+        // kalign_run_realign aligns a second time on a new tree with the consistency table of the first pass
+        // (aln_wrap.c:424-431,497-502): same sequences, new task list.  Anything else starts without a table.
+        bool keep_cons = false;
+        if ((flags & KA_FLAG_KEEP_CONSISTENCY) && c->have_job && c->cons_K > 0) {
+                bool same = numseq == c->numseq;
+                for (int i = 0; same && i < numseq; i++)
+                        same = lens[i] == c->lens[i] && off[i] == c->off[i] && memcmp(codes + off[i], c->h_codes.data() + off[i], lens[i]) == 0;
+                if (!same) return fail("KA_FLAG_KEEP_CONSISTENCY: the sequences differ from those the consistency table was built on");
+                keep_cons = true;
+        }
+        c->have_job = false; c->ran = false; c->synced = false; c->state_valid = false;
+        // a join watchdog of an earlier job forced the no-cluster plan: a new job gets the fast plan again (the
+        // fallback is counted, ka_ctx_fallback_runs); a caller's own ka_ctx_set_shared stays
+        // -- unless the fallback before it was a fast-plan job's too: then fallback_hold jobs stay on the shared plan first (ka_tree_sync)
+        if (c->shared_by_fallback) {
+                if (c->fallback_hold > 0) c->fallback_hold--;
+                else { c->shared_gpu = false; c->shared_by_fallback = false; }
+        }
+        if (!keep_cons) c->cons_K = 0;           // a new job starts without a consistency table
+        c->have_colof = false;
+        c->rows_n = 0;
+        c->flags = flags;
+        c->off.assign(off, off + numseq);
+        memcpy(c->subm, subm, sizeof(c->subm));
+        memcpy(c->scal, scal, sizeof(c->scal));
+        c->sum_len = 0; c->max_len = 0;
+        long long codes_bytes = 0;
+        int max_code = 0;
+        for (int i = 0; i < numseq; i++)
+                for (int j = 0; j < lens[i]; j++) max_code = std::max<int>(max_code, codes[off[i] + j]);
+        if (max_code > 22) return fail("sequence code out of range (alphabet is 0..22)");
+        // nucleotide alphabets use codes 0..4 (alphabet.c:206-245); proteins without B / Z / X only codes 0..19
+        c->nres = (max_code < 5) ? 5 : (max_code < 20 ? 20 : 23);
+        for (int i = 0; i < numseq; i++) {
+                if (lens[i] < 1) return fail("zero-length sequence (the reference removes them before the dispatcher, msa_check.c:66)");
+                c->sum_len += lens[i];
+                c->max_len = std::max(c->max_len, lens[i]);
+                codes_bytes = std::max<long long>(codes_bytes, (long long)off[i] + lens[i]);
+        }
+
+        c->h_codes.assign(codes, codes + codes_bytes);
+        if (seq_distances) c->seq_dist.assign(seq_distances, seq_distances + numseq); else c->seq_dist.clear();
+        if (prepare_tasks(c, numseq, lens, seq_distances, n_tasks, abc, scal)) return KA_FAIL;
+        const int max_level = (int)c->levels.size();
         c->level_ids_flat.clear(); c->level_off.assign(1, 0);
         for (auto& L : c->levels) {
                 c->level_ids_flat.insert(c->level_ids_flat.end(), L.begin(), L.end());
                 c->level_off.push_back((int)c->level_ids_flat.size());
         }
 
-        c->task_level.assign(n_tasks, 0);
-        for (int t = 0; t < n_tasks; t++) c->task_level[t] = level[abc[3 * t + 2]] - 1;
         c->plan_active.clear();
         if (plan_launches(c)) return KA_FAIL;
 
@@ -682,3 +752,54 @@ int upload_plan(ka_ctx* c)
         return KA_OK;
 }
 
+
+// ---- the plan, flattened for tests and tools (include/kalign_amd.h: ka_debug_plan) ----
+static int export_plan(const KaPlan* p, int* scalars, int* per_task, int* blocks, int blocks_cap, int* blocks_off, int* level_lean)
+{
+        if (!scalars || !per_task || !blocks_off || !level_lean || (!blocks && blocks_cap > 0)) return fail("ka_debug_plan: bad arguments");
+        const int n = p->n_tasks, levels = (int)p->plan_levels.size(), n_blocks = (int)p->blocks_flat.size();
+        const bool chain = p->chain_level >= 0;
+        const int sc[16] = { levels, n_blocks, p->max_cluster, p->n_trees, p->chain_level, p->queue_first, p->queue_off, p->queue_n, p->overlap_plan,
+                             p->reserve_cus, chain ? p->chain_blocks_off : 0, chain ? (int)p->chain_blocks.size() : 0, 0, 0, 0, 0 };
+        memcpy(scalars, sc, sizeof(sc));
+        if (n_blocks > blocks_cap) return fail("ka_debug_plan: the block table needs more room (scalars[1] entries)");
+        for (int t = 0; t < n; t++) {
+                const KaTaskDesc& d = p->descs[t];
+                const int v[7] = { d.parent, d.chain_need, d.is_root, d.wait_mult, d.qa, d.qb, (int)p->spine[t] };
+                for (int k = 0; k < 7; k++) per_task[(size_t)k * n + t] = v[k];
+        }
+        for (int i = 0; i < n_blocks; i++) { blocks[2 * i] = p->blocks_flat[i].x; blocks[2 * i + 1] = p->blocks_flat[i].y; }
+        for (int L = 0; L <= levels; L++) blocks_off[L] = p->blocks_off[L];
+        for (int L = 0; L < levels; L++) level_lean[L] = p->level_lean[L];
+        return KA_OK;
+}
+
+extern "C" int ka_debug_plan(int numseq, const int* lens, int n_tasks, const int* abc, int n_cus, int shared, int cons_K, int hooks,
+                             const int* task_ids, int n_ids,
+                             int* scalars, int* per_task, int* blocks, int blocks_cap, int* blocks_off, int* level_lean)
+{
+        if (!lens || !abc || n_cus < 1 || cons_K < 0) return fail("ka_debug_plan: bad arguments");
+        if (numseq < 2 || n_tasks < 1 || n_tasks > numseq - 1) return fail("need numseq >= 2 and 1 <= n_tasks <= numseq-1");
+        for (int i = 0; i < numseq; i++)
+                if (lens[i] < 1) return fail("zero-length sequence (the reference removes them before the dispatcher, msa_check.c:66)");
+        KaPlan p;
+        read_env(p.env);
+        p.n_cus = n_cus; p.shared_gpu = shared != 0; p.cons_K = cons_K; p.test_hooks = hooks;
+        const float scal[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };     // (gap penalties and their scaling are no part of the plan)
+        if (prepare_tasks(&p, numseq, lens, nullptr, n_tasks, abc, scal)) return KA_FAIL;
+        if (task_ids) {
+                p.plan_active.assign(n_tasks, 0);
+                for (int i = 0; i < n_ids; i++) {
+                        if (task_ids[i] < 0 || task_ids[i] >= n_tasks) return fail("task id out of range");
+                        p.plan_active[task_ids[i]] = 1;
+                }
+        }
+        if (plan_launches(&p)) return KA_FAIL;
+        return export_plan(&p, scalars, per_task, blocks, blocks_cap, blocks_off, level_lean);
+}
+
+extern "C" int ka_debug_ctx_plan(ka_ctx* c, int* scalars, int* per_task, int* blocks, int blocks_cap, int* blocks_off, int* level_lean)
+{
+        if (!c || !c->have_job) return fail("no uploaded job");
+        return export_plan(c, scalars, per_task, blocks, blocks_cap, blocks_off, level_lean);
+}
