@@ -98,6 +98,9 @@ int  ka_ctx_set_shared(ka_ctx* ctx, int shared);
 /* How often a run of this context fell back to that plan on its own because a wait between workgroups never
    completed (another process was using the GPU): the run is repeated and correct, but slower -- visible here. */
 int  ka_ctx_fallback_runs(ka_ctx* ctx);
+/* Bytes of device memory in the context's profile, path and scratch arenas.  They grow to the largest job the context has
+   seen (and on overflow) and are kept from job to job; a job of a shape the context has already run leaves them as they are. */
+long long ka_ctx_arena_bytes(ka_ctx* ctx);
 /* Of the last finished run: tasks of the queued launch that workgroups of the chained launch took over because they were resident
    before the queue was down to its last round (overlapping launches; normally 0).  -1: nothing finished. */
 long long ka_ctx_helped_tasks(ka_ctx* ctx);

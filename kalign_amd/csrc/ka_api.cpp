@@ -17,7 +17,7 @@ __attribute__((visibility("hidden"))) int ka_fail_message(const char* m) { retur
 extern "C" const char* ka_last_error(void) { return g_err.c_str(); }
 struct ka_ctx;
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_guide.cpp)
-extern "C" int ka_abi_version(void) { return 15; }
+extern "C" int ka_abi_version(void) { return 16; }
 
 extern "C" int ka_ctx_create(int device, ka_ctx** out)
 {
@@ -79,6 +79,7 @@ extern "C" int ka_debug_reload_env(ka_ctx* c)
 // How often a run of this context had to fall back to the no-cluster / no-chain plan because workgroups that wait for
 // each other were not all resident (somebody else was using the GPU).
 extern "C" int ka_ctx_fallback_runs(ka_ctx* c) { return c ? c->fallback_runs : -1; }
+extern "C" long long ka_ctx_arena_bytes(ka_ctx* c) { return c ? (long long)sizeof(float) * c->prof_cap + (long long)sizeof(int) * c->path_cap + c->scratch_cap : -1; }
 extern "C" long long ka_ctx_helped_tasks(ka_ctx* c) { return (c && c->synced) ? (long long)c->h_counters[5] : -1; }
 
 extern "C" void ka_ctx_destroy(ka_ctx* c)

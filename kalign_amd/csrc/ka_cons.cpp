@@ -205,9 +205,13 @@ extern "C" int ka_tree_build_consistency_part(ka_ctx* c, int n_anchors, float we
         if (K > KA_NB - 1) {
                 // More than five anchors: the streamed kernels carve KA_NB_BIG bonus entries per DP row and K-sized position / confidence /
                 // vote tables -- ~3.6 x the bytes per row at K = 32 -- while the plan sized the scratch arena for the K <= 5 kernels
-                // (shared contexts overflowed, doubled twice and ran their first tree three times).  Grow it here, once K is known.
+                // (shared contexts overflowed, doubled twice and ran their first tree three times).  Grow it here, once K is known:
+                // to the ratio times what THIS job's plan asked for -- not times what the context holds, which earlier jobs have grown already
+                // (a context that built one such table per job multiplied its arena every time, until hipMalloc failed).  scratch_job is the
+                // plan's estimate alone, on purpose: what ka_tree_sync doubles after an overflow stays in scratch_cap, which the next upload
+                // of that shape keeps (max), so a shape that overflowed once does not overflow again and is not multiplied again either.
                 const double ratio = (double)ka_scratch_bytes_host_big(c->sum_len, c->sum_len, c->max_len, K) / (double)std::max<long long>(ka_scratch_bytes_host(c->sum_len, c->sum_len, c->max_len), 1);
-                const long long want = (long long)((double)c->scratch_cap * std::max(ratio, 1.0)) + 4096;
+                const long long want = (long long)((double)c->scratch_job * std::max(ratio, 1.0)) + 4096;
                 if (want > c->scratch_cap) {
                         c->scratch_cap = want;
                         c->d_scratch.release();

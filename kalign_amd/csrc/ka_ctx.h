@@ -126,6 +126,7 @@ struct ka_ctx : KaPlan {
         DevBuf<KaTaskDesc> d_tasks;
         DevBuf<ka_task_rec> d_recs;
         long long prof_cap = 0, path_cap = 0, scratch_cap = 0, dbg_cap = 0;
+        long long scratch_job = 0;                   // what the uploaded job's plan asked of the scratch arena (scratch_cap: what the context holds, never shrinks)
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         std::vector<hipEvent_t> launch_ev;           // KA_LAUNCH_EV: one event behind every launch of the last run
         // two pinned bounce buffers for large downloads into the caller's (pageable) memory

@@ -714,10 +714,11 @@ extern "C" int ka_tree_upload(ka_ctx* c, int numseq, const uint8_t* codes, const
                 scr = (c->env.overlap && both <= (24LL << 30)) ? both : std::max(scr, scr_queue);
         }
         c->scratch_cap = std::max(c->scratch_cap, scr);
+        c->scratch_job = scr;
         if (c->test_hooks & KA_DEBUG_SMALL_ARENAS) {
                 // tests: start with arenas that are certainly too small, so that the overflow -> grow -> re-run
                 // path of ka_tree_sync is exercised (also across the join points of the chained launch)
-                c->prof_cap = top + 64LL * KA_REC; c->path_cap = 64; c->scratch_cap = 1 << 16;
+                c->prof_cap = top + 64LL * KA_REC; c->path_cap = 64; c->scratch_cap = c->scratch_job = 1 << 16;
                 c->d_prof_arena.release(); c->d_path_arena.release(); c->d_scratch.release();
         }
         c->dbg_cap = (flags & KA_FLAG_DEBUG_ROWS) ? std::max<long long>(c->dbg_cap, 6LL * (cols + 2LL * n_tasks + c->sum_len)) : c->dbg_cap;

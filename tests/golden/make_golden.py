@@ -85,6 +85,29 @@ def cons_cases():
     cons_case("cons_dna16x300", synth.family(16, 300, dna=True, seed=1), type_=0)
     cons_case("cons_prot48_k3", synth.family(48, 130, seed=21), n_anchors=3, weight=1.5)
     cons_case("cons_ragged", ["ACDEFGHIKL", "AC", "ACDEFGHIKLMNPQRSTVWYACDEFGHIKLMNPQRSTVWY", "MKV", "ACDKL", "WYACDEFG"])
+    stream_cons_cases()
+
+
+NOISY = dict(sub_rate=0.3, indel_rate=0.06)       # divergent families: anchors disagree, rows carry many bonus entries
+
+
+STREAM_RAGGED_LENS = (1, 2, 3, 5, 17, 33, 64, 65, 65, 66, 100, 127, 128, 128, 129, 129, 130, 131)
+
+
+def stream_ragged():
+    """lengths from 1 to 131: one-row tasks, rows without entries, tasks of 65, 128 and 129 DP rows (the seed is one at which the
+    reference's guide tree makes them; tests/test_stream_bonus_inputs.py asserts the row counts on the stored file)"""
+    fam = synth.family(len(STREAM_RAGGED_LENS), 170, seed=136, **NOISY)
+    assert all(len(s) >= L for s, L in zip(fam, STREAM_RAGGED_LENS))
+    return [s[:L] for s, L in zip(fam, STREAM_RAGGED_LENS)]
+
+
+def stream_cons_cases():
+    """more than five anchors: the second kernel set (a DP row's bonus entries are walked, not held in registers)"""
+    cons_case("cons_stream_prot16_k11", synth.family(16, 64, seed=61, **NOISY), n_anchors=11)
+    cons_case("cons_stream_dna40_k33", synth.family(40, 30, dna=True, seed=62, **NOISY), n_anchors=33, type_=0)
+    cons_case("cons_stream_ragged_k6", stream_ragged(), n_anchors=6)
+    cons_case("cons_stream_dna9_k128", synth.family(9, 70, dna=True, seed=64, **NOISY), n_anchors=128, type_=0)   # capped: K = N = 9
 
 
 def pairwise_case(name, seqs, type_):
@@ -215,6 +238,15 @@ def refine_cases():
     refine_case("refine_ragged_all", [s[:40 + 13 * i] for i, s in enumerate(synth.dssim(20, 400, seed=13))], 1)
     inline_cases()
     adaptive_cases()
+    stream_refine_cases()
+
+
+def stream_refine_cases():
+    """more than five anchors in every mode (the names sort behind the K <= 5 cases: tests that take a leading slice keep theirs)"""
+    refine_case("refine_cons_stream_k11_all", synth.dssim(16, 64, seed=71), 1, n_anchors=11)
+    refine_case("refine_cons_stream_k6_conf", synth.dssim(20, 90, seed=72), 2, n_anchors=6)
+    refine_case("refine_cons_stream_k33_inline", synth.dssim(36, 40, dna=True, seed=73), 3, n_anchors=33, type_=0)
+    refine_case("refine_cons_stream_k11_all_adaptive", synth.dssim(16, 64, seed=71), 1 + 256, n_anchors=11)
 
 
 def adaptive_cases():
@@ -265,6 +297,12 @@ def realign_cases():
     realign_case("realign_dups", fam + fam[:7] + fam[3:5])                        # identical rows: distance ties in UPGMA
     realign_case("realign_dna24_cons", synth.family(24, 150, dna=True, seed=5), n_anchors=5)
     realign_case("realign_prot150", synth.family(150, 70, seed=6))
+    stream_realign_case()
+
+
+def stream_realign_case():
+    """the second pass runs on the first pass's table of more than five anchors"""
+    realign_case("realign_dna20_cons_k11", synth.family(20, 90, dna=True, seed=8, **NOISY), n_anchors=11)
 
 
 def guide_cases():
@@ -291,6 +329,10 @@ if __name__ == "__main__":
         sys.exit("oracle/_ref/libkalign_ref.so missing: run `make -C oracle ref` (needs /root/reference)")
     if len(sys.argv) > 1 and sys.argv[1] == "cons":        # only the consistency cases
         cons_cases()
+    elif len(sys.argv) > 1 and sys.argv[1] == "stream":    # only the cases with more than five anchors
+        stream_cons_cases()
+        stream_refine_cases()
+        stream_realign_case()
     elif len(sys.argv) > 1 and sys.argv[1] == "guide":
         guide_cases()
     elif len(sys.argv) > 1 and sys.argv[1] == "realign":
