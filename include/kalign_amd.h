@@ -400,6 +400,67 @@ typedef int (*ka_dist_fn)(void* user, int npairs, const int* ia, const int* ib, 
 int ka_guide_tree_from(int numseq, const int* lens, ka_dist_fn dist, void* user, int n_threads,
                        const float* dm_scale, int* tasks_abc, float* seq_distances);
 
+/*
+ * The guide trees of a BATCH OF FAMILIES (a forest job, see ka_msa_tree): sequences fam_first[f] .. fam_first[f + 1] - 1 are
+ * family f, n_fam families, fam_first[n_fam] = numseq sequences in all.  The three phases of build_tree_kmeans -- anchors and
+ * the anchor distances; bisection and the in-cluster distances; UPGMA, tasks and seq_distances -- each run over all families
+ * before the next starts: dist() is called at most twice however many families there are, with global sequence indices, both
+ * members of a pair always of one family.  The families' host work runs on n_threads threads; nothing depends on their number.
+ *   tasks_abc[3 * (numseq - n_fam)]  one forest task list: leaves carry their global index, internal nodes are numseq + the
+ *                    task's index in this list; families in order, each family's tasks in its own TASK_ORDER_TREE order
+ *   n_tasks_out      (may be NULL) the number of tasks; a family of one sequence has none, and seq_distances 0
+ *   dm_scale         NULL, or the families' multiplier blocks one after the other, n_f * min(32, n_f) each
+ * Per family, tasks and seq_distances are bit for bit what ka_guide_tree_from gives that family alone.  Errors name their
+ * cause: "fam_first does not ascend from 0 to numseq", "empty family", "zero-length sequence".
+ * ka_guide_forest_from is host only (no context, no GPU); ka_guide_forest runs the two batches on the device (ka_bpm_batch).
+ */
+int ka_guide_forest_from(int n_fam, const int* fam_first, const int* lens, ka_dist_fn dist, void* user, int n_threads,
+                         const float* dm_scale, int* tasks_abc, int* n_tasks_out, float* seq_distances);
+int ka_guide_forest(ka_ctx* ctx, int n_fam, const int* fam_first, const uint8_t* codes, const int* off, const int* lens,
+                    int n_threads, const float* dm_scale, int* tasks_abc, int* n_tasks_out, float* seq_distances);
+
+/*
+ * ka_aln_guide_tree for a batch of families: the identity distances of all families in one launch, their row means in one,
+ * and the UPGMAs one workgroup per family (a launch per size class of the one-workgroup kernel; a family of more than 6144
+ * sequences goes through the per-merge launches on its own).  Per family, tasks, seq_distances and distances are bit for bit
+ * those of ka_aln_guide_tree on that family alone.
+ *   rows             numseq rows, row_stride apart; family f's alignment is the first alnlens[f] <= row_stride bytes of its rows
+ *                    (what lies beyond is not read); or NULL: the rows the last ka_tree_aligned_rows of a forest job (or of a
+ *                    single tree) left in HBM -- fam_first must describe that job's alignments; row_stride, alnlens and gap_char
+ *                    are ignored
+ *   tasks_abc, seq_distances (may be NULL)  as for ka_guide_forest
+ *   dm_out           (may be NULL) the families' n_f x n_f matrices one after the other
+ */
+int ka_aln_guide_forest(ka_ctx* ctx, int n_fam, const int* fam_first, const uint8_t* rows, long long row_stride,
+                        const int* alnlens, uint8_t gap_char, int* tasks_abc, float* seq_distances, float* dm_out);
+
+/*
+ * ka_run_encoded_refine for a batch of families in one call: the guide trees of all families (ka_guide_forest), one forest
+ * ka_tree_upload with KA_FLAG_DEVICE_GAPS, ka_tree_build_consistency, ka_tree_run (refine_mode 3: ka_tree_refine), per
+ * realignment iteration rows in HBM -> ka_aln_guide_forest -> upload with KA_FLAG_KEEP_CONSISTENCY -> run, refine_mode 1
+ * (| KA_REFINE_ADAPTIVE), rows.  refine_mode 2 (KALIGN_REFINE_CONFIDENT) is refused: its threshold is the median confidence of
+ * one alignment's edges, and ka_tree_refine takes it over all tasks of a job.  All families share subm / scal.  Every family comes out as ka_run_encoded_refine aligns it
+ * alone: a family of n_f >= 3 sequences gets K_f = min(n_anchors, n_f) anchors, a smaller one no table.  One forest job holds
+ * one anchor count, so families of equal K_f are one job and the jobs run one after the other on the context.
+ *   tree_codes / codes / letters, off, lens   all numseq = fam_first[n_fam] sequences, as for ka_run_encoded
+ *   dm_scale         as for ka_guide_forest
+ *   alnlen_out[numseq]  (may be NULL) the alignment length of every sequence's family (a family of one: its length)
+ * The finished rows stay in memory the context owns until the next ka_run_encoded_batch replaces them:
+ *   ka_batch_rows_size   bytes ka_batch_rows needs (-1: no finished batch)
+ *   ka_batch_rows        the rows, packed: families in order, the rows of family f alnlen_f + 1 bytes apart, each ending in a
+ *                        0 byte (a family of one sequence: its letters).  Fails, and loses nothing, when cap_bytes is too small.
+ *   ka_batch_stats       measurements of the last batch: out6 = device ms of the guide trees' distance batches, of the
+ *                        alignment runs (refinement included), of the realignment distances + UPGMA, of building rows; forest
+ *                        jobs run; wall ms of the call
+ */
+int ka_run_encoded_batch(ka_ctx* ctx, int n_fam, const int* fam_first, const uint8_t* tree_codes, const uint8_t* codes,
+                         const uint8_t* letters, const int* off, const int* lens, const float* subm, const float* scal,
+                         int n_anchors, float weight, int realign_iterations, const float* dm_scale, int n_threads,
+                         int refine_mode, uint8_t gap_char, int* alnlen_out);
+long long ka_batch_rows_size(ka_ctx* ctx);
+int ka_batch_rows(ka_ctx* ctx, uint8_t* rows_out, long long cap_bytes);
+int ka_batch_stats(ka_ctx* ctx, double* out6);
+
 /* Kernel time (HIP events on the launch stream) of the last ka_pairwise_batch / ka_bpm_batch, milliseconds. */
 float ka_pairwise_kernel_ms(ka_ctx* ctx);
 

@@ -59,7 +59,9 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_tree_adopt_alignment", "ka_ens_create", "ka_ens_destroy", "ka_ens_add_member", "ka_ens_score_rows", "ka_ens_consensus",
            "ka_ens_confidence", "ka_ens_stats", "ka_ens_table_size", "ka_ens_table_write", "ka_ens_table_image", "ka_ens_open_table",
            "ka_ens_open_table_image", "ka_ens_n_runs", "ka_ens_table_stats", "ka_poar_check_image", "ka_ens_merge", "ka_ens_select", "ka_cmp_create", "ka_cmp_destroy", "ka_cmp_set_mask", "ka_cmp_score",
-           "ka_cmp_score_batch", "ka_cmp_stats"]
+           "ka_cmp_score_batch", "ka_cmp_stats",
+           "ka_guide_forest_from", "ka_guide_forest", "ka_aln_guide_forest", "ka_run_encoded_batch", "ka_batch_rows_size", "ka_batch_rows",
+           "ka_batch_stats"]
 
 
 def lib_path():
@@ -184,6 +186,15 @@ def load_library():
     L.ka_aln_guide_tree.argtypes = [vp, C.c_int, vp, C.c_longlong, C.c_int, C.c_ubyte, vp, vp, vp]
     L.ka_guide_tree.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]
     L.ka_guide_tree_from.argtypes = [C.c_int, vp, DIST_FN, vp, C.c_int, vp, vp, vp]
+    L.ka_guide_forest_from.argtypes = [C.c_int, vp, vp, DIST_FN, vp, C.c_int, vp, vp, C.POINTER(C.c_int), vp]
+    L.ka_guide_forest.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, C.POINTER(C.c_int), vp]
+    L.ka_aln_guide_forest.argtypes = [vp, C.c_int, vp, vp, C.c_longlong, vp, C.c_ubyte, vp, vp, vp]
+    L.ka_run_encoded_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp, C.c_int,
+                                       C.c_int, C.c_ubyte, vp]
+    L.ka_batch_rows_size.argtypes = [vp]
+    L.ka_batch_rows_size.restype = C.c_longlong
+    L.ka_batch_rows.argtypes = [vp, vp, C.c_longlong]
+    L.ka_batch_stats.argtypes = [vp, vp]
     L.ka_tree_get_consistency.argtypes = [vp, vp, vp]
     L.ka_pairwise_batch.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp,
                                     C.c_float, C.c_float, C.c_float, vp, vp, vp]
@@ -716,6 +727,141 @@ def _run_encoded(self, tree_codes, codes, letters, subm, scal, n_anchors=0, weig
 Context.run_encoded = _run_encoded
 
 
+def _fam_first(sizes):
+    first = np.zeros(len(sizes) + 1, np.int32)
+    first[1:] = np.cumsum(sizes)
+    return first
+
+
+def _dm_scale_forest(noise, sizes):
+    if noise is None:
+        return None
+    noise = np.ascontiguousarray(np.concatenate([np.asarray(b, np.float32).reshape(-1) for b in noise]), np.float32)
+    if len(noise) != sum(int(n) * min(32, int(n)) for n in sizes):
+        raise KalignAmdError("dm_scale needs one block of n * min(32, n) multipliers per family")
+    return noise
+
+
+def _split_forest(tasks, sizes):
+    """the forest task list (ka_guide_forest's numbering) as one array per family, still in the forest's numbering"""
+    out, t = [], 0
+    for n in sizes:
+        out.append(tasks[t:t + int(n) - 1])
+        t += int(n) - 1
+    return out
+
+
+def _guide_forest(self, families, n_threads=1, dm_scale=None):
+    """ka_guide_forest: the guide trees of a batch of families with both distance batches on the device, two launches of
+    ka_bpm_batch for all of them.  families: one list of sequences (tree alphabet) per family; dm_scale: None or one block
+    of multipliers per family.  Returns (tasks[numseq - n_fam, 3] in the forest's numbering, seq_distances[numseq])."""
+    sizes = [len(f) for f in families]
+    flat, off, lens = _flatten([c for f in families for c in f])
+    first = _fam_first(sizes)
+    tasks = np.zeros((max(len(lens) - len(sizes), 0), 3), np.int32)
+    sd = np.zeros(len(lens), np.float32)
+    sc = _dm_scale_forest(dm_scale, sizes)
+    nt = C.c_int(0)
+    self._chk(self.L.ka_guide_forest(self.h, len(sizes), _ptr(first), _ptr(flat), _ptr(off), _ptr(lens), int(n_threads), _ptr(sc),
+                                     _ptr(tasks) if len(tasks) else None, C.byref(nt), _ptr(sd)))
+    return tasks[:nt.value], sd
+
+
+Context.guide_forest = _guide_forest
+
+
+def _aln_guide_forest(self, families=None, sizes=None, gap=b"-", want_dm=False):
+    """ka_aln_guide_forest: the realignment trees of a batch of families.  families: per family a list of equal-length rows
+    (bytes); or None with sizes = the number of sequences per family for the rows the last tree_aligned_rows left in HBM.
+    Returns (tasks in the forest's numbering, seq_distances[, one n_f x n_f distance matrix per family])."""
+    if families is None:
+        sizes = [int(n) for n in sizes]
+        flat, stride, widths = None, 0, None
+    else:
+        sizes = [len(f) for f in families]
+        widths = np.array([len(f[0]) for f in families], np.int32)
+        if any(len(r) != w for f, w in zip(families, widths) for r in f):
+            raise KalignAmdError("rows of one alignment have one length")
+        stride = int(widths.max())
+        buf = np.full((sum(sizes), stride), gap[0], np.uint8)
+        i = 0
+        for f, w in zip(families, widths):
+            for r in f:
+                buf[i, :w] = np.frombuffer(bytes(r), np.uint8)
+                i += 1
+        flat = buf.reshape(-1)
+    first = _fam_first(sizes)
+    n = int(first[-1])
+    tasks = np.zeros((max(n - len(sizes), 1), 3), np.int32)
+    sd = np.zeros(n, np.float32)
+    dm = np.zeros(sum(k * k for k in sizes), np.float32) if want_dm else None
+    self._chk(self.L.ka_aln_guide_forest(self.h, len(sizes), _ptr(first), _ptr(flat), stride, _ptr(widths), gap[0], _ptr(tasks), _ptr(sd), _ptr(dm)))
+    tasks = tasks[:n - len(sizes)]
+    if not want_dm:
+        return tasks, sd
+    out, o = [], 0
+    for k in sizes:
+        out.append(dm[o:o + k * k].reshape(k, k))
+        o += k * k
+    return tasks, sd, out
+
+
+Context.aln_guide_forest = _aln_guide_forest
+
+
+def _run_families(self, families, subm, scal, n_anchors=0, weight=2.0, realign=0, refine=0, dm_scale=None, n_threads=4, gap=b"-"):
+    """ka_run_encoded_batch: a batch of families from letters to rows in one call.  families: a list of
+    (tree_codes, codes, letters), each as run_encoded takes them; all share subm / scal.  Every family is aligned as
+    run_encoded aligns it alone.  Returns one list of rows (bytes, in the order of the family's sequences) per family."""
+    sizes = [len(f[1]) for f in families]
+    if not sizes or min(sizes) < 1:
+        raise KalignAmdError("run_families: every family needs a sequence")
+    tflat, off, lens = _flatten([c for f in families for c in f[0]])
+    cflat, _, _ = _flatten([c for f in families for c in f[1]])
+    lflat = np.ascontiguousarray(np.concatenate([np.frombuffer(x.encode() if isinstance(x, str) else bytes(x), np.uint8)
+                                                 for f in families for x in f[2]]))
+    if len(lflat) != len(cflat) or len(tflat) != len(cflat):
+        raise KalignAmdError("the three encodings of the sequences differ in length")
+    first = _fam_first(sizes)
+    sub = np.ascontiguousarray(subm, np.float32).reshape(-1)
+    sc = np.ascontiguousarray(scal, np.float32)
+    dms = _dm_scale_forest(dm_scale, sizes)
+    alen = np.zeros(len(lens), np.int32)
+    self._chk(self.L.ka_run_encoded_batch(self.h, len(sizes), _ptr(first), _ptr(tflat), _ptr(cflat), _ptr(lflat), _ptr(off), _ptr(lens),
+                                          _ptr(sub), _ptr(sc), int(n_anchors), float(weight), int(realign), _ptr(dms), int(n_threads),
+                                          int(refine), gap[0], _ptr(alen)))
+    return self.batch_rows(sizes, alen)
+
+
+def _batch_rows(self, sizes, alen):
+    """ka_batch_rows: the packed rows of the last run_families as one list of bytes per family"""
+    need = int(self.L.ka_batch_rows_size(self.h))
+    if need < 0:
+        raise KalignAmdError("no finished batch on this context")
+    buf = np.zeros(max(need, 1), np.uint8)
+    self._chk(self.L.ka_batch_rows(self.h, _ptr(buf), need))
+    out, o, i = [], 0, 0
+    for n in sizes:
+        w = int(alen[i])
+        out.append([buf[o + k * (w + 1):o + k * (w + 1) + w].tobytes() for k in range(n)])
+        o += n * (w + 1)
+        i += n
+    assert o == need
+    return out
+
+
+def _batch_stats(self):
+    """ka_batch_stats of the last run_families: dict of device ms per stage, forest jobs run and wall ms"""
+    out = np.zeros(6, np.float64)
+    self._chk(self.L.ka_batch_stats(self.h, _ptr(out)))
+    return dict(guide_dist_ms=out[0], dp_ms=out[1], realign_tree_ms=out[2], rows_ms=out[3], jobs=int(out[4]), wall_ms=out[5])
+
+
+Context.run_families = _run_families
+Context.batch_rows = _batch_rows
+Context.batch_stats = _batch_stats
+
+
 def residue_lens(rows):
     """letters per row (bytes / str, any lengths) as int32: a residue is an ASCII letter, every other byte a gap
     (ka_msa_is_residue, csrc/ka_msa.h)"""
@@ -1021,6 +1167,32 @@ def guide_tree_from(lens, dist, n_threads=1, dm_scale=None):
     if L.ka_guide_tree_from(len(lens), _ptr(lens), DIST_FN(cb), None, int(n_threads), _ptr(sc), _ptr(tasks), _ptr(sd)):
         raise KalignAmdError(L.ka_last_error().decode())
     return tasks, sd
+
+
+def guide_forest_from(fam_lens, dist, n_threads=1, dm_scale=None):
+    """ka_guide_forest_from: the guide trees of a batch of families with the caller's distance source (host only, no GPU
+    needed).  fam_lens: one array of sequence lengths per family; dist(ia, ib) gets GLOBAL sequence indices (families
+    concatenated) and is called at most twice.  Returns (tasks in the forest's numbering, seq_distances)."""
+    L = load_library()
+    sizes = [len(x) for x in fam_lens]
+    lens = np.ascontiguousarray(np.concatenate([np.asarray(x, np.int32).reshape(-1) for x in fam_lens]), np.int32)
+    first = _fam_first(sizes)
+
+    def cb(_user, n, ia, ib, out):
+        try:
+            d = dist(np.ctypeslib.as_array(ia, (n,)).copy(), np.ctypeslib.as_array(ib, (n,)).copy())
+            np.ctypeslib.as_array(out, (n,))[:] = d
+            return 0
+        except Exception:                     # reported as "the distance source failed"
+            return 1
+
+    tasks = np.zeros((max(len(lens) - len(sizes), 1), 3), np.int32)
+    sd = np.zeros(len(lens), np.float32)
+    sc = _dm_scale_forest(dm_scale, sizes)
+    nt = C.c_int(0)
+    if L.ka_guide_forest_from(len(sizes), _ptr(first), _ptr(lens), DIST_FN(cb), None, int(n_threads), _ptr(sc), _ptr(tasks), C.byref(nt), _ptr(sd)):
+        raise KalignAmdError(L.ka_last_error().decode())
+    return tasks[:nt.value], sd
 
 
 def guide_last_bisect():

@@ -17,7 +17,7 @@ __attribute__((visibility("hidden"))) int ka_fail_message(const char* m) { retur
 extern "C" const char* ka_last_error(void) { return g_err.c_str(); }
 struct ka_ctx;
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_guide.cpp)
-extern "C" int ka_abi_version(void) { return 16; }
+extern "C" int ka_abi_version(void) { return 17; }
 
 extern "C" int ka_ctx_create(int device, ka_ctx** out)
 {
@@ -98,6 +98,7 @@ extern "C" void ka_ctx_destroy(ka_ctx* c)
         c->d_adm.release(); c->d_amean.release(); c->d_uactive.release(); c->d_ucand.release(); c->d_umerges.release();
         c->d_cons_maps.release(); c->d_colof.release(); c->d_colof_init.release(); c->d_sip.release();
         c->d_cons_map_off.release(); c->d_sip_off.release();
+        c->d_adtiles.release(); c->d_adfams.release(); c->d_fam_of.release(); c->d_utable.release(); c->d_row_off.release(); c->d_batch_rows.release();
         for (int k = 0; k < 2; k++) { if (c->pin[k]) (void)hipHostFree(c->pin[k]); if (c->pin_ev[k]) (void)hipEventDestroy(c->pin_ev[k]); }
         if (c->h_trace) (void)hipHostFree(c->h_trace);
         for (hipEvent_t e : c->launch_ev) (void)hipEventDestroy(e);
@@ -680,7 +681,7 @@ extern "C" int ka_tree_adopt_alignment(ka_ctx* c, const ka_task_rec* recs, const
         c->flags |= KA_FLAG_DEVICE_GAPS;
         c->h_counters[2] = 0;                                         // (no coded paths of its own)
         c->ran = true; c->synced = true; c->partial = false; c->state_valid = false;
-        c->rows_n = 0;
+        c->rows_n = 0; c->rows_forest_n = 0;
         return KA_OK;
 }
 
@@ -714,8 +715,9 @@ static int rows_build(ka_ctx* c, const uint8_t* letters, uint8_t gap_char, const
                        c->d_rows.p, row_stride, c->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(c->stream));                      // `alen` and `letters` are the caller's
-        // (one alignment only: a forest has no common row length)
+        // (ka_aln_guide_tree: one alignment only, a forest has no common row length; ka_aln_guide_forest takes either)
         c->rows_n = (c->n_tasks == c->numseq - 1) ? c->numseq : 0;
+        c->rows_forest_n = c->numseq; c->rows_alen = alen;
         c->rows_stride = row_stride; c->rows_alnlen = widest; c->rows_gap = gap_char;
         return KA_OK;
 }
@@ -748,7 +750,7 @@ extern "C" int ka_aln_guide_tree(ka_ctx* c, int numseq, const uint8_t* rows, lon
                 const size_t bytes = (size_t)numseq * (size_t)row_stride;
                 if (c->d_rows.alloc(bytes)) return fail("hipMalloc failed");
                 HIPCHK(hipMemcpyAsync(c->d_rows.p, rows, bytes, hipMemcpyHostToDevice, c->stream));
-                c->rows_n = 0;                                        // no longer the rows of the last run
+                c->rows_n = 0; c->rows_forest_n = 0;                  // no longer the rows of the last run
         } else {
                 if (c->rows_n < 2) return fail("ka_aln_guide_tree: no rows on the device (call ka_tree_aligned_rows on a finished single-tree run first)");
                 if (numseq != c->rows_n) return fail("ka_aln_guide_tree: numseq does not match the rows on the device");
@@ -842,6 +844,333 @@ static int run_encoded(ka_ctx* c, int numseq, const uint8_t* tree_codes, const u
         if (row_stride < (long long)widest + 1) { g_err = "ka_run_encoded: row_stride is smaller than the alignment + terminator (alnlen_out says how long; ka_tree_aligned_rows fetches the rows)"; return KA_ERR_ROWS_STRIDE; }
         if (rows_build(c, letters, gap_char, alen, widest, row_stride)) return KA_FAIL;
         return copy_to_host(c, rows_out, c->d_rows.p, (size_t)numseq * (size_t)row_stride);
+}
+
+
+// ---- a batch of families: realignment trees of all of them in a handful of launches, and the one call --------------------
+static int check_fam_first(const char* who, int n_fam, const int* fam_first)
+{
+        const std::string me(who);
+        if (n_fam < 1 || !fam_first) return fail(me + ": bad arguments");
+        if (fam_first[0] != 0) return fail(me + ": fam_first does not ascend from 0 to numseq");
+        for (int f = 0; f < n_fam; f++) {
+                if (fam_first[f + 1] < fam_first[f]) return fail(me + ": fam_first does not ascend from 0 to numseq");
+                if (fam_first[f + 1] == fam_first[f]) return fail(me + ": empty family");
+        }
+        return KA_OK;
+}
+
+// compute_aln_pairwise_dist + build_tree_from_pairwise (ka_aln_guide_tree) for every family of a batch: one launch of the
+// identity distances over a table of tiles, one of the row means, and the UPGMAs one workgroup per family, a launch per size
+// class.  The task list comes back in the forest numbering of ka_guide_forest.
+extern "C" int ka_aln_guide_forest(ka_ctx* c, int n_fam, const int* fam_first, const uint8_t* rows, long long row_stride,
+                                   const int* alnlens, uint8_t gap_char, int* tasks_abc, float* seq_distances, float* dm_out)
+{
+        if (!c) return fail("null ctx");
+        if (!tasks_abc) return fail("null argument");
+        if (check_fam_first("ka_aln_guide_forest", n_fam, fam_first)) return KA_FAIL;
+        HIPCHK(hipSetDevice(c->device));
+        const int numseq = fam_first[n_fam];
+        std::vector<int> width(n_fam);
+        if (rows) {
+                if (!alnlens || row_stride < 1) return fail("ka_aln_guide_forest: bad arguments");
+                for (int f = 0; f < n_fam; f++) {
+                        if (alnlens[f] < 1 || alnlens[f] > row_stride) return fail("ka_aln_guide_forest: a family's alignment length does not fit row_stride");
+                        width[f] = alnlens[f];
+                }
+                const size_t bytes = (size_t)numseq * (size_t)row_stride;
+                if (c->d_rows.alloc(bytes)) return fail("hipMalloc failed");
+                HIPCHK(hipMemcpyAsync(c->d_rows.p, rows, bytes, hipMemcpyHostToDevice, c->stream));
+                c->rows_n = 0; c->rows_forest_n = 0;                  // no longer the rows of the last run
+        } else {
+                if (c->rows_forest_n < 1) return fail("ka_aln_guide_forest: no rows on the device (call ka_tree_aligned_rows on a finished run first)");
+                if (numseq != c->rows_forest_n) return fail("ka_aln_guide_forest: numseq does not match the rows on the device");
+                for (int f = 0; f < n_fam; f++) {
+                        width[f] = c->rows_alen[fam_first[f]];
+                        for (int i = fam_first[f]; i < fam_first[f + 1]; i++)
+                                if (c->rows_alen[i] != width[f]) return fail("ka_aln_guide_forest: fam_first does not match the alignments of the rows on the device");
+                }
+                row_stride = c->rows_stride; gap_char = c->rows_gap;
+        }
+        // ---- the tables: tiles of the distance launch, the families' matrices, the UPGMA records by size class ----
+        std::vector<long long> dm_off(n_fam + 1, 0);
+        std::vector<KaAdTile> tiles;
+        std::vector<KaAdFam> fams(n_fam);
+        std::vector<int> fam_of(numseq);
+        for (int f = 0; f < n_fam; f++) {
+                const int first = fam_first[f], n = fam_first[f + 1] - first;
+                if (n > 46340) return fail("ka_aln_guide_forest: more than 46340 sequences in a family (pair indices are 32-bit)");
+                dm_off[f + 1] = dm_off[f] + (long long)n * n;
+                fams[f] = KaAdFam{ first, n, dm_off[f] };
+                for (int i = first; i < first + n; i++) fam_of[i] = f;
+                const int t = (n + 15) / 16;
+                for (int ti = 0; ti < t; ti++)
+                        for (int tj = ti; tj < t; tj++) tiles.push_back(KaAdTile{ first, n, width[f], ti, tj, 0, dm_off[f] });
+        }
+        if (tiles.size() > (size_t)INT32_MAX) return fail("ka_aln_guide_forest: more than 2^31 distance tiles in one batch");
+        const size_t nn = (size_t)dm_off[n_fam];
+        if (c->d_adm.alloc(nn) || c->d_amean.alloc(numseq) || c->d_uactive.alloc(numseq) || c->d_ucand.alloc(2 * (size_t)numseq) ||
+            c->d_umerges.alloc(numseq) || c->d_adtiles.alloc(tiles.size()) || c->d_adfams.alloc(n_fam) || c->d_fam_of.alloc(numseq) ||
+            c->d_utable.alloc(n_fam))
+                return fail("hipMalloc failed");
+        // families by size class (one workgroup each); the others -- above the one-workgroup limit, or all of them when the
+        // per-merge launches are asked for -- go through ka_launch_upgma one by one
+        std::vector<int> by_class[KA_UPGMA_CLASSES], alone;
+        for (int f = 0; f < n_fam; f++) {
+                const int n = fams[f].n;
+                if (n < 2) continue;
+                if (n > KA_UPGMA_ONE_WG_MAX || c->env.upgma_launches) alone.push_back(f);
+                else by_class[ka_upgma_class(n)].push_back(f);
+        }
+        auto record = [&](int f) {
+                const int first = fams[f].first, n = fams[f].n;
+                unsigned long long* keys = c->d_ucand.p + 2 * (size_t)first;
+                return KaUpgma{ c->d_adm.p + dm_off[f], c->d_uactive.p + first, { keys, keys + n }, c->d_umerges.p + first, n };
+        };
+        std::vector<KaUpgma> table;
+        int cls_first[KA_UPGMA_CLASSES + 1] = { 0 }, cls_max[KA_UPGMA_CLASSES] = { 0 };
+        for (int k = 0; k < KA_UPGMA_CLASSES; k++) {
+                for (int f : by_class[k]) { table.push_back(record(f)); cls_max[k] = std::max(cls_max[k], fams[f].n); }
+                cls_first[k + 1] = (int)table.size();
+        }
+        HIPCHK(hipMemcpyAsync(c->d_adtiles.p, tiles.data(), sizeof(KaAdTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->d_adfams.p, fams.data(), sizeof(KaAdFam) * n_fam, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->d_fam_of.p, fam_of.data(), sizeof(int) * numseq, hipMemcpyHostToDevice, c->stream));
+        if (!table.empty()) HIPCHK(hipMemcpyAsync(c->d_utable.p, table.data(), sizeof(KaUpgma) * table.size(), hipMemcpyHostToDevice, c->stream));
+        ka_launch_aln_dist_forest(c->d_rows.p, row_stride, c->d_adtiles.p, (int)tiles.size(), c->d_adfams.p, c->d_fam_of.p, numseq, gap_char,
+                                  c->d_adm.p, c->d_amean.p, c->stream);
+        HIPCHK(hipGetLastError());
+        if (dm_out) HIPCHK(hipMemcpyAsync(dm_out, c->d_adm.p, sizeof(float) * nn, hipMemcpyDeviceToHost, c->stream));
+        if (seq_distances) HIPCHK(hipMemcpyAsync(seq_distances, c->d_amean.p, sizeof(float) * numseq, hipMemcpyDeviceToHost, c->stream));
+        std::vector<int> ones(numseq, 1);
+        HIPCHK(hipMemcpyAsync(c->d_uactive.p, ones.data(), sizeof(int) * numseq, hipMemcpyHostToDevice, c->stream));
+        if (!table.empty()) {
+                const int failed = ka_launch_upgma_forest(c->d_utable.p, cls_first, cls_max, c->stream);
+                HIPCHK(hipGetLastError());
+                for (int k = 0; k < KA_UPGMA_CLASSES; k++)
+                        if (failed & (1 << k)) alone.insert(alone.end(), by_class[k].begin(), by_class[k].end());
+        }
+        for (int f : alone) {
+                const KaUpgma U = record(f);
+                ka_launch_upgma(U.dm, U.active, U.key[0], U.merges, U.n, c->env.upgma_launches ? 1 : 0, c->stream);
+                HIPCHK(hipGetLastError());
+        }
+        std::vector<int> merges(2 * (size_t)numseq);
+        HIPCHK(hipMemcpyAsync(merges.data(), c->d_umerges.p, sizeof(int2) * numseq, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        // ---- upgma()'s bookkeeping per family on the host, then the forest's numbering ----
+        int t0 = 0;
+        std::vector<int> local;
+        for (int f = 0; f < n_fam; f++) {
+                const int first = fams[f].first, n = fams[f].n;
+                if (n < 2) continue;
+                local.assign(3 * (size_t)(n - 1), 0);
+                if (ka_tasks_from_merges(n, merges.data() + 2 * (size_t)first, local.data())) return KA_FAIL;
+                for (int t = 0; t < n - 1; t++)
+                        for (int k = 0; k < 3; k++) {
+                                const int x = local[3 * (size_t)t + k];
+                                tasks_abc[3 * (size_t)(t0 + t) + k] = x < n ? first + x : numseq + t0 + (x - n);
+                        }
+                t0 += n - 1;
+        }
+        return KA_OK;
+}
+
+// the finished rows of the uploaded job, every row at row_off[i] of one packed buffer, straight into host memory
+static int rows_build_packed(ka_ctx* c, const uint8_t* letters, uint8_t gap_char, const std::vector<int>& alen,
+                             const std::vector<long long>& row_off, size_t bytes, uint8_t* out)
+{
+        if (c->d_letters.alloc(c->h_codes.size()) || c->d_alnlen.alloc(c->numseq) || c->d_row_off.alloc(c->numseq) || c->d_batch_rows.alloc(bytes))
+                return fail("hipMalloc failed");
+        HIPCHK(hipMemcpyAsync(c->d_letters.p, letters, c->h_codes.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->d_alnlen.p, alen.data(), sizeof(int) * c->numseq, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->d_row_off.p, row_off.data(), sizeof(long long) * c->numseq, hipMemcpyHostToDevice, c->stream));
+        ka_launch_rows_packed(c->d_letters.p, c->d_seq_off.p, c->d_node_len.p, c->d_colof.p, c->d_alnlen.p, c->numseq, gap_char,
+                              c->d_batch_rows.p, c->d_row_off.p, c->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return copy_to_host(c, out, c->d_batch_rows.p, bytes);
+}
+
+extern "C" int ka_run_encoded_batch(ka_ctx* c, int n_fam, const int* fam_first, const uint8_t* tree_codes, const uint8_t* codes,
+                                    const uint8_t* letters, const int* off, const int* lens, const float* subm, const float* scal,
+                                    int n_anchors, float weight, int realign_iterations, const float* dm_scale, int n_threads,
+                                    int refine_mode, uint8_t gap_char, int* alnlen_out)
+{
+        if (!c) return fail("null ctx");
+        if (check_fam_first("ka_run_encoded_batch", n_fam, fam_first)) return KA_FAIL;
+        if (!tree_codes || !codes || !letters || !off || !lens || !subm || !scal) return fail("ka_run_encoded_batch: bad arguments");
+        const int base = refine_mode & 255;
+        if (refine_mode < 0 || base > 3 || (refine_mode & ~(255 | KA_REFINE_ADAPTIVE)) || ((refine_mode & KA_REFINE_ADAPTIVE) && base != 1 && base != 2))
+                return fail("ka_run_encoded_batch: refine_mode must be 0, 1 (optionally | KA_REFINE_ADAPTIVE) or 3");
+        // KALIGN_REFINE_CONFIDENT refines the edges at or below the MEDIAN confidence of an alignment's edges; ka_tree_refine takes that
+        // median over all tasks of a job, which in a forest job would mix the families
+        if (base == 2) return fail("ka_run_encoded_batch: refine_mode 2 (confident) is not available for a batch: its median would span the families");
+        if (n_anchors > KA_CONS_MAX_ANCHORS) return fail("this build takes at most 128 consistency anchors (KA_CONS_MAX_ANCHORS)");
+        HIPCHK(hipSetDevice(c->device));
+        const auto t_start = std::chrono::steady_clock::now();
+        double stats[6] = { 0, 0, 0, 0, 0, 0 };
+        hipEvent_t ev[2] = { nullptr, nullptr };
+        struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 2; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } guard{ ev };
+        HIPCHK(hipEventCreate(&ev[0]));
+        HIPCHK(hipEventCreate(&ev[1]));
+        const int numseq = fam_first[n_fam];
+        const bool inline_refine = base == 3;
+        auto align = [&]() -> int {
+                if (inline_refine ? ka_tree_refine(c, 3, nullptr) : ka_tree_run(c)) return KA_FAIL;
+                if (ka_tree_sync(c)) return KA_FAIL;
+                float ms = 0.0f;
+                if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) stats[1] += ms; else (void)hipGetLastError();
+                return KA_OK;
+        };
+        // ---- the guide trees of all families: two distance batches ----
+        std::vector<int> tasks(3 * (size_t)std::max(numseq - 1, 1)), t_first(n_fam + 1, 0);
+        std::vector<float> sd(numseq);
+        int n_tasks = 0;
+        if (ka_guide_forest(c, n_fam, fam_first, tree_codes, off, lens, n_threads, dm_scale, tasks.data(), &n_tasks, sd.data())) return KA_FAIL;
+        stats[0] = ka_guide_last_dist_ms();
+        for (int f = 0; f < n_fam; f++) t_first[f + 1] = t_first[f] + (fam_first[f + 1] - fam_first[f] - 1);
+        // ---- families of equal anchor count K_f = min(n_anchors, n_f) (none below three sequences, anchor_consistency.c:206-217)
+        //      are one forest job; the jobs run one after the other.  A family of one sequence is in none: its row is its letters ----
+        std::vector<std::vector<int>> groups;
+        {
+                std::vector<std::pair<int, int>> kf;
+                for (int f = 0; f < n_fam; f++) {
+                        const int n = fam_first[f + 1] - fam_first[f];
+                        if (n >= 2) kf.push_back({ (n_anchors > 0 && n >= 3) ? std::min(n_anchors, n) : 0, f });
+                }
+                std::stable_sort(kf.begin(), kf.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
+                for (size_t i = 0; i < kf.size(); i++) {
+                        if (i == 0 || kf[i].first != kf[i - 1].first) groups.push_back(std::vector<int>());
+                        groups.back().push_back(kf[i].second);
+                }
+        }
+        std::vector<int> width(n_fam, 0);                              // every family's alignment length
+        std::vector<std::vector<uint8_t>> group_rows(groups.size());   // a job's rows, its families packed in order
+        for (size_t g = 0; g < groups.size(); g++) {
+                const std::vector<int>& G = groups[g];
+                const int first_n = fam_first[G[0] + 1] - fam_first[G[0]];
+                const int K = (n_anchors > 0 && first_n >= 3) ? std::min(n_anchors, first_n) : 0;
+                // the job's own copy of its families: sequences and tasks renumbered from 0
+                std::vector<int> g_fam_first(1, 0), g_off, g_lens, g_tasks, g_t_first(1, 0);
+                std::vector<uint8_t> g_codes, g_letters;
+                std::vector<float> g_sd;
+                for (int f : G) {
+                        for (int i = fam_first[f]; i < fam_first[f + 1]; i++) {
+                                g_off.push_back((int)g_codes.size());
+                                g_lens.push_back(lens[i]);
+                                g_codes.insert(g_codes.end(), codes + off[i], codes + off[i] + lens[i]);
+                                g_letters.insert(g_letters.end(), letters + off[i], letters + off[i] + lens[i]);
+                                g_sd.push_back(sd[i]);
+                        }
+                        g_fam_first.push_back((int)g_lens.size());
+                        g_t_first.push_back(g_t_first.back() + (fam_first[f + 1] - fam_first[f] - 1));
+                }
+                const int gn = (int)g_lens.size(), gt = g_t_first.back();
+                g_tasks.resize(3 * (size_t)gt);
+                for (size_t x = 0; x < G.size(); x++) {
+                        const int f = G[x];
+                        for (int t = t_first[f]; t < t_first[f + 1]; t++)
+                                for (int k = 0; k < 3; k++) {
+                                        const int v = tasks[3 * (size_t)t + k];
+                                        g_tasks[3 * (size_t)(g_t_first[x] + t - t_first[f]) + k] =
+                                                v < numseq ? g_fam_first[x] + (v - fam_first[f]) : gn + g_t_first[x] + (v - numseq - t_first[f]);
+                                }
+                }
+                if (ka_tree_upload(c, gn, g_codes.data(), g_off.data(), g_lens.data(), g_sd.data(), gt, g_tasks.data(), subm, scal, KA_FLAG_DEVICE_GAPS)) return KA_FAIL;
+                if (K > 0 && ka_tree_build_consistency(c, K, weight)) return KA_FAIL;
+                if (align()) return KA_FAIL;
+                std::vector<int> alen;
+                int widest = 0;
+                for (int it = 0; it < realign_iterations; it++) {
+                        if (rows_prepare(c, g_letters.data(), alen, &widest)) return KA_FAIL;
+                        HIPCHK(hipEventRecord(ev[0], c->stream));
+                        if (rows_build(c, g_letters.data(), gap_char, alen, widest, (long long)widest + 1)) return KA_FAIL;
+                        HIPCHK(hipEventRecord(ev[1], c->stream));
+                        HIPCHK(hipEventSynchronize(ev[1]));
+                        float ms = 0.0f;
+                        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+                        stats[3] += ms;
+                        if (ka_aln_guide_forest(c, (int)G.size(), g_fam_first.data(), nullptr, 0, nullptr, 0, g_tasks.data(), g_sd.data(), nullptr)) return KA_FAIL;
+                        HIPCHK(hipEventRecord(ev[0], c->stream));
+                        HIPCHK(hipEventSynchronize(ev[0]));
+                        HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[0]));
+                        stats[2] += ms;
+                        if (ka_tree_upload(c, gn, g_codes.data(), g_off.data(), g_lens.data(), g_sd.data(), gt, g_tasks.data(), subm, scal,
+                                           KA_FLAG_DEVICE_GAPS | KA_FLAG_KEEP_CONSISTENCY)) return KA_FAIL;
+                        if (align()) return KA_FAIL;
+                }
+                if (base == 1) {
+                        if (ka_tree_refine(c, refine_mode, nullptr) || ka_tree_sync(c)) return KA_FAIL;
+                        float ms = 0.0f;
+                        if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) stats[1] += ms; else (void)hipGetLastError();
+                }
+                if (rows_prepare(c, g_letters.data(), alen, &widest)) return KA_FAIL;
+                std::vector<long long> row_off(gn);
+                long long bytes = 0;
+                for (size_t x = 0; x < G.size(); x++) {
+                        width[G[x]] = alen[g_fam_first[x]];
+                        for (int i = g_fam_first[x]; i < g_fam_first[x + 1]; i++) { row_off[i] = bytes; bytes += (long long)alen[i] + 1; }
+                }
+                group_rows[g].resize((size_t)bytes);
+                HIPCHK(hipEventRecord(ev[0], c->stream));
+                if (rows_build_packed(c, g_letters.data(), gap_char, alen, row_off, (size_t)bytes, group_rows[g].data())) return KA_FAIL;
+                HIPCHK(hipEventRecord(ev[1], c->stream));
+                HIPCHK(hipEventSynchronize(ev[1]));
+                float ms = 0.0f;
+                HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+                stats[3] += ms;
+        }
+        // ---- all families in their order, packed ----
+        std::vector<long long> fam_off(n_fam + 1, 0);
+        for (int f = 0; f < n_fam; f++) {
+                const int n = fam_first[f + 1] - fam_first[f];
+                if (n == 1) width[f] = lens[fam_first[f]];
+                fam_off[f + 1] = fam_off[f] + (long long)n * (width[f] + 1);
+        }
+        std::vector<uint8_t> packed((size_t)fam_off[n_fam]);
+        for (size_t g = 0; g < groups.size(); g++) {
+                size_t at = 0;
+                for (int f : groups[g]) {
+                        const size_t nb = (size_t)(fam_off[f + 1] - fam_off[f]);
+                        memcpy(packed.data() + fam_off[f], group_rows[g].data() + at, nb);
+                        at += nb;
+                }
+        }
+        for (int f = 0; f < n_fam; f++)
+                if (fam_first[f + 1] - fam_first[f] == 1) {
+                        const int i = fam_first[f];
+                        memcpy(packed.data() + fam_off[f], letters + off[i], lens[i]);
+                        packed[(size_t)fam_off[f] + lens[i]] = 0;
+                }
+        if (alnlen_out)
+                for (int f = 0; f < n_fam; f++)
+                        for (int i = fam_first[f]; i < fam_first[f + 1]; i++) alnlen_out[i] = width[f];
+        c->batch_rows.swap(packed);
+        c->have_batch = true;
+        stats[4] = (double)groups.size();
+        stats[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+        memcpy(c->batch_stats, stats, sizeof(stats));
+        return KA_OK;
+}
+
+extern "C" long long ka_batch_rows_size(ka_ctx* c) { return (c && c->have_batch) ? (long long)c->batch_rows.size() : -1; }
+
+extern "C" int ka_batch_rows(ka_ctx* c, uint8_t* rows_out, long long cap_bytes)
+{
+        if (!c || !c->have_batch) return fail("ka_batch_rows: no finished ka_run_encoded_batch on this context");
+        if (!rows_out) return fail("ka_batch_rows: null argument");
+        if (cap_bytes < (long long)c->batch_rows.size())
+                return fail("ka_batch_rows: cap_bytes is smaller than the rows (ka_batch_rows_size says how many bytes are needed)");
+        memcpy(rows_out, c->batch_rows.data(), c->batch_rows.size());
+        return KA_OK;
+}
+
+extern "C" int ka_batch_stats(ka_ctx* c, double* out6)
+{
+        if (!c || !c->have_batch || !out6) return fail("ka_batch_stats: no finished ka_run_encoded_batch on this context");
+        memcpy(out6, c->batch_stats, sizeof(c->batch_stats));
+        return KA_OK;
 }
 
 

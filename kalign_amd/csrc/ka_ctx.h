@@ -20,6 +20,7 @@
 
 #include "ka_device.h"
 #include "ka_plan.h"         // KaEnv, KaPlan (the host-only base of the context), fail()
+#include "ka_forest.h"       // the records of the realignment-tree kernels
 
 // the task kernels live in four translation units (ka_kernels.hip, -DKA_UNIT=0..3)
 extern "C" void ka_unit0_launch(const KaTreeDev* D, const int2* blocks_dev, int nblocks, int chain, hipStream_t stream);   // 8 waves
@@ -59,6 +60,12 @@ extern "C" void ka_launch_aln_dist(const uint8_t* rows, long long stride, int al
                                    hipStream_t stream);
 extern "C" void ka_launch_upgma(float* dm, int* active, unsigned long long* keys, int2* merges, int n, int mode, hipStream_t stream);
 int ka_tasks_from_merges(int numseq, const int* merges_ab, int* tasks_abc);      // ka_guide.cpp
+double ka_guide_last_dist_ms(void);                                              // ka_guide.cpp: device ms of the distance batches of the last ka_guide_forest
+extern "C" void ka_launch_aln_dist_forest(const uint8_t* rows, long long stride, const KaAdTile* tiles, int n_tiles, const KaAdFam* fams,
+                                          const int* fam_of, int numseq, uint8_t gap, float* dm, float* means, hipStream_t stream);
+extern "C" int ka_launch_upgma_forest(const KaUpgma* table, const int* first, const int* max_n, hipStream_t stream);
+extern "C" void ka_launch_rows_packed(const uint8_t* letters, const int* off, const int* lens, const int* colof, const int* alnlen,
+                                      int numseq, uint8_t gap, uint8_t* rows, const long long* row_off, hipStream_t stream);
 extern "C" void ka_launch_rows(const uint8_t* letters, const int* off, const int* lens, const int* colof, const int* alnlen,
                                int numseq, uint8_t gap, uint8_t* rows, long long stride, hipStream_t stream);
 extern "C" void ka_launch_bpm(const uint8_t* codes, const int* off, const int* lens, int numseq, unsigned long long* peq,
@@ -165,6 +172,14 @@ struct ka_ctx : KaPlan {
         DevBuf<uint8_t> d_letters, d_rows;
         long long rows_stride = 0; int rows_n = 0, rows_alnlen = 0; uint8_t rows_gap = 0;   // what d_rows holds (0 rows: nothing)
         DevBuf<float> d_adm, d_amean; DevBuf<int> d_uactive; DevBuf<unsigned long long> d_ucand; DevBuf<int2> d_umerges;
+        // ---- a batch of families (ka_aln_guide_forest, ka_run_encoded_batch) ----
+        int rows_forest_n = 0;                       // d_rows holds the rows of this many sequences of a forest job (a single tree included) ...
+        std::vector<int> rows_alen;                  // ... every sequence's own alignment length (d_alnlen on the host)
+        DevBuf<KaAdTile> d_adtiles; DevBuf<KaAdFam> d_adfams; DevBuf<int> d_fam_of; DevBuf<KaUpgma> d_utable;
+        DevBuf<long long> d_row_off; DevBuf<uint8_t> d_batch_rows;
+        std::vector<uint8_t> batch_rows;             // the finished rows of the last ka_run_encoded_batch, packed (ka_batch_rows)
+        bool have_batch = false;
+        double batch_stats[6] = {0, 0, 0, 0, 0, 0};  // ka_batch_stats
         DevBuf<long long> d_cons_map_off, d_sip_off;
 };
 

@@ -6,6 +6,7 @@
 // clusters of < 50 sequences, node labels, task list -- is small, branchy host work and stays on the host, in the
 // reference's fp32 evaluation order so that the tree is the same tree, bit for bit.
 #include <algorithm>
+#include <atomic>
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -13,9 +14,11 @@
 #include <cstring>
 #include <future>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <system_error>
+#include <thread>
 #include <vector>
 
 #include "kalign_amd.h"
@@ -296,14 +299,15 @@ void collect_leaves(Sub* root, std::vector<Sub*>& out)
 int ka_fail_message(const char* m);      // ka_api.cpp: sets what ka_last_error() returns
 
 // the library's own distance source (ka_bpm_batch) has already said why: keep its text
-static int dist_failed()
+static int dist_failed(const char* who)
 {
         const std::string inner = ka_last_error();
-        return ka_fail_message(("ka_guide_tree_from: the distance source failed" + (inner.empty() ? std::string() : ": " + inner)).c_str());
+        return ka_fail_message((std::string(who) + ": the distance source failed" + (inner.empty() ? std::string() : ": " + inner)).c_str());
 }
 
-static int guide_tree_from(int numseq, const int* lens, ka_dist_fn dist, void* user, int n_threads,
-                           const float* dm_scale, int* tasks_abc, float* seq_distances);
+static int guide_forest_from(const char* who, int n_fam, const int* fam_first, const int* lens, ka_dist_fn dist, void* user, int n_threads,
+                             const float* dm_scale, int* tasks_abc, int* n_tasks_out, float* seq_distances);
+
 
 // The 2-means bisection on the device (ka_kmeans.hip) for the callers that have one: ka_guide_tree sets the device and stream
 // of its context here for the duration of the call.  KA_KMEANS in the environment: "0" host, "1" device whatever the size;
@@ -325,7 +329,9 @@ extern "C" int ka_guide_tree_from(int numseq, const int* lens, ka_dist_fn dist, 
                                   const float* dm_scale, int* tasks_abc, float* seq_distances)
 {
         try {                                            // no exception may cross the C ABI
-                return guide_tree_from(numseq, lens, dist, user, n_threads, dm_scale, tasks_abc, seq_distances);
+                if (numseq < 2 || !lens || !dist || !tasks_abc) return ka_fail_message("ka_guide_tree_from: bad arguments");
+                const int fam_first[2] = { 0, numseq };
+                return guide_forest_from("ka_guide_tree_from", 1, fam_first, lens, dist, user, n_threads, dm_scale, tasks_abc, nullptr, seq_distances);
         } catch (const std::bad_alloc&) {
                 return ka_fail_message("ka_guide_tree_from: out of memory");
         } catch (const std::exception& e) {
@@ -333,42 +339,131 @@ extern "C" int ka_guide_tree_from(int numseq, const int* lens, ka_dist_fn dist, 
         }
 }
 
-static int guide_tree_from(int numseq, const int* lens, ka_dist_fn dist, void* user, int n_threads,
-                           const float* dm_scale, int* tasks_abc, float* seq_distances)
+// The guide trees of a batch of families: sequences fam_first[f] .. fam_first[f + 1] - 1 are family f.  The three phases of
+// build_tree_kmeans run over ALL families before the next one starts, so that the distance source is called at most twice
+// however many families there are; what a family does between the calls is what it does alone, on its own data.
+extern "C" int ka_guide_forest_from(int n_fam, const int* fam_first, const int* lens, ka_dist_fn dist, void* user, int n_threads,
+                                    const float* dm_scale, int* tasks_abc, int* n_tasks_out, float* seq_distances)
 {
-        if (numseq < 2 || !lens || !dist || !tasks_abc) return ka_fail_message("ka_guide_tree_from: bad arguments");
-        for (int i = 0; i < numseq; i++)
-                if (lens[i] < 1) return ka_fail_message("ka_guide_tree_from: zero-length sequence");
+        try {
+                if (n_fam < 1 || !fam_first || !lens || !dist || !tasks_abc) return ka_fail_message("ka_guide_forest_from: bad arguments");
+                return guide_forest_from("ka_guide_forest_from", n_fam, fam_first, lens, dist, user, n_threads, dm_scale, tasks_abc, n_tasks_out, seq_distances);
+        } catch (const std::bad_alloc&) {
+                return ka_fail_message("ka_guide_forest_from: out of memory");
+        } catch (const std::exception& e) {
+                return ka_fail_message((std::string("ka_guide_forest_from: ") + e.what()).c_str());
+        }
+}
 
-        // ---- anchors and the N x A distance matrix (pick_anchor, d_estimation with pair = 0) ----
+namespace {
+// One family between the phases.  Indices are the family's own (0 .. n - 1) except in the pair lists handed to the distance source.
+struct Fam {
+        int first = 0, n = 0, A = 0, padded = 0;
+        bool km_dev = false;                         // its bisection runs on the device (on the calling thread)
         std::vector<int> anchors;
-        pick_anchors(numseq, lens, anchors);
-        const int A = (int)anchors.size();
-        const int padded = ((A + 7) / 8) * 8;
-        std::vector<int> ia((size_t)numseq * A), ib((size_t)numseq * A), d((size_t)numseq * A);
-        for (int i = 0; i < numseq; i++)
-                for (int j = 0; j < A; j++) { ia[(size_t)i * A + j] = i; ib[(size_t)i * A + j] = anchors[j]; }
-        if (dist(user, numseq * A, ia.data(), ib.data(), d.data())) return dist_failed();
-        std::vector<float> dm((size_t)numseq * padded, 0.0f);
-        for (int i = 0; i < numseq; i++)
-                for (int j = 0; j < A; j++) dm[(size_t)i * padded + j] = with_length_term(d[(size_t)i * A + j], lens[i], lens[anchors[j]]);
-        // build_tree_kmeans_noisy (:103-115): the caller's multiplicative noise on the anchor distances
-        if (dm_scale)
-                for (int i = 0; i < numseq; i++)
-                        for (int j = 0; j < A; j++) dm[(size_t)i * padded + j] *= dm_scale[(size_t)i * A + j];
-
-        // ---- bisecting k-means down to clusters of < 50 sequences ----
-        Builder B;
-        B.numseq = numseq; B.num_anchors = A; B.padded = padded; B.dm = dm.data(); B.n_threads = std::max(1, n_threads);
+        std::vector<float> dm;
         std::unique_ptr<Sub> root;
-        const auto t_bisect = std::chrono::steady_clock::now();
+        std::vector<Sub*> leaves;
+        std::vector<size_t> first_pair;              // of every leaf cluster, from p2
+        size_t p1 = 0, p2 = 0;                       // the family's first pair in the anchor batch / the cluster batch
+        std::vector<int> tasks;                      // 3 * (n - 1), nodes numbered as for the family alone
+};
+
+// fn(f) for every f < n on up to n_threads threads; the first exception is thrown again here
+template <typename F>
+void for_each_family(int n, int n_threads, F fn)
+{
+        if (n_threads < 2 || n < 2) { for (int f = 0; f < n; f++) fn(f); return; }
+        std::atomic<int> next(0);
+        std::exception_ptr err;
+        std::mutex err_lock;
+        auto work = [&] {
+                for (int f; (f = next.fetch_add(1)) < n;) {
+                        try { fn(f); }
+                        catch (...) { std::lock_guard<std::mutex> g(err_lock); if (!err) err = std::current_exception(); }
+                }
+        };
+        std::vector<std::thread> pool;
+        for (int t = 1; t < std::min(n_threads, n); t++) {
+                try { pool.emplace_back(work); } catch (const std::system_error&) { break; }      // no thread to be had: fewer
+        }
+        work();
+        for (auto& t : pool) t.join();
+        if (err) std::rethrow_exception(err);
+}
+}  // namespace
+
+static int guide_forest_from(const char* who, int n_fam, const int* fam_first, const int* lens, ka_dist_fn dist, void* user, int n_threads,
+                             const float* dm_scale, int* tasks_abc, int* n_tasks_out, float* seq_distances)
+{
+        const std::string me(who);
+        if (fam_first[0] != 0) return ka_fail_message((me + ": fam_first does not ascend from 0 to numseq").c_str());
+        for (int f = 0; f < n_fam; f++) {
+                if (fam_first[f + 1] < fam_first[f]) return ka_fail_message((me + ": fam_first does not ascend from 0 to numseq").c_str());
+                if (fam_first[f + 1] == fam_first[f]) return ka_fail_message((me + ": empty family").c_str());
+        }
+        const int numseq = fam_first[n_fam];
+        for (int i = 0; i < numseq; i++)
+                if (lens[i] < 1) return ka_fail_message((me + ": zero-length sequence").c_str());
+        n_threads = std::max(1, n_threads);
+
+        // ---- anchors and the N x A distance matrix of every family (pick_anchor, d_estimation with pair = 0): ONE batch ----
+        std::vector<Fam> fams(n_fam);
+        size_t total = 0;
+        int n_trees = 0;
+        for (int f = 0; f < n_fam; f++) {
+                Fam& F = fams[f];
+                F.first = fam_first[f]; F.n = fam_first[f + 1] - fam_first[f];
+                if (F.n < 2) continue;                           // one sequence: no tree
+                n_trees++;
+                pick_anchors(F.n, lens + F.first, F.anchors);
+                F.A = (int)F.anchors.size();
+                F.padded = ((F.A + 7) / 8) * 8;
+                F.p1 = total;
+                total += (size_t)F.n * F.A;
+        }
+        if (total > (size_t)INT32_MAX) return ka_fail_message((me + ": more than 2^31 anchor distances in one batch").c_str());
+        std::vector<int> ia(total), ib(total), d(total);
+        for (const Fam& F : fams)
+                for (int i = 0; i < F.n && F.A; i++)
+                        for (int j = 0; j < F.A; j++) { ia[F.p1 + (size_t)i * F.A + j] = F.first + i; ib[F.p1 + (size_t)i * F.A + j] = F.first + F.anchors[j]; }
+        if (total && dist(user, (int)total, ia.data(), ib.data(), d.data())) return dist_failed(who);
+
+        // ---- per family: the matrix, then bisecting k-means down to clusters of < 50 sequences ----
+        // (the threads go to the families when there are several, into the one family's bisection when there is one)
+        const int inner_threads = n_trees > 1 ? 1 : n_threads;
         const char* km_env = getenv("KA_KMEANS");
-        const bool km_dev = g_km.on && A == 32 && padded == 32 && (km_env ? atoi(km_env) != 0 : numseq >= 2048);
-        g_last_bisect_device = km_dev ? 1 : 0;
-        if (km_dev) {
+        std::vector<size_t> scale_off(n_fam + 1, 0);             // dm_scale: the families' blocks, n x min(32, n) each
+        for (int f = 0; f < n_fam; f++) scale_off[f + 1] = scale_off[f] + (size_t)fams[f].n * std::min(KA_MAX_ANCHORS, fams[f].n);
+        auto matrix = [&](Fam& F, int f) {
+                const int* flen = lens + F.first;
+                F.dm.assign((size_t)F.n * F.padded, 0.0f);
+                for (int i = 0; i < F.n; i++)
+                        for (int j = 0; j < F.A; j++) F.dm[(size_t)i * F.padded + j] = with_length_term(d[F.p1 + (size_t)i * F.A + j], flen[i], flen[F.anchors[j]]);
+                // build_tree_kmeans_noisy (:103-115): the caller's multiplicative noise on the anchor distances
+                if (dm_scale)
+                        for (int i = 0; i < F.n; i++)
+                                for (int j = 0; j < F.A; j++) F.dm[(size_t)i * F.padded + j] *= dm_scale[scale_off[f] + (size_t)i * F.A + j];
+        };
+        auto clusters = [&](Fam& F) {
+                collect_leaves(F.root.get(), F.leaves);
+                F.first_pair.assign(F.leaves.size() + 1, 0);
+                for (size_t k = 0; k < F.leaves.size(); k++) {
+                        const size_t n = F.leaves[k]->cluster.size();
+                        F.first_pair[k + 1] = F.first_pair[k] + n * (n - 1) / 2;
+                }
+        };
+        const auto t_bisect = std::chrono::steady_clock::now();
+        g_last_bisect_device = 0;
+        for (int f = 0; f < n_fam; f++) {                        // the device's bisections first, from this thread
+                Fam& F = fams[f];
+                F.km_dev = F.n >= 2 && g_km.on && F.A == 32 && F.padded == 32 && (km_env ? atoi(km_env) != 0 : F.n >= 2048);
+                if (!F.km_dev) continue;
+                g_last_bisect_device = 1;
+                matrix(F, f);
                 std::vector<KaKmNode> kn;
                 std::string why;
-                if (ka_kmeans_device(g_km.device, g_km.stream, dm.data(), numseq, kn, why)) return ka_fail_message(("ka_guide_tree: " + why).c_str());
+                if (ka_kmeans_device(g_km.device, g_km.stream, F.dm.data(), F.n, kn, why)) return ka_fail_message(("ka_guide_tree: " + why).c_str());
                 // the device's node table as the builder's tree (iteratively: lopsided splits make it deep)
                 std::vector<std::unique_ptr<Sub>> made(kn.size());
                 for (size_t k = kn.size(); k--;) {                  // children have larger indices than their parent
@@ -376,77 +471,100 @@ static int guide_tree_from(int numseq, const int* lens, ka_dist_fn dist, void* u
                         if (kn[k].left < 0) made[k]->cluster = std::move(kn[k].cluster);
                         else { made[k]->l = std::move(made[kn[k].left]); made[k]->r = std::move(made[kn[k].right]); }
                 }
-                root = std::move(made[0]);
-        } else {
-                std::vector<int> all(numseq);
-                for (int i = 0; i < numseq; i++) all[i] = i;
-                root = bisect(B, std::move(all), 0);
+                F.root = std::move(made[0]);
+                clusters(F);
         }
+        for_each_family(n_fam, n_trees > 1 ? n_threads : 1, [&](int f) {
+                Fam& F = fams[f];
+                if (F.n < 2 || F.km_dev) return;
+                matrix(F, f);
+                Builder B;
+                B.numseq = F.n; B.num_anchors = F.A; B.padded = F.padded; B.dm = F.dm.data(); B.n_threads = inner_threads;
+                std::vector<int> all(F.n);
+                for (int i = 0; i < F.n; i++) all[i] = i;
+                F.root = bisect(B, std::move(all), 0);
+                clusters(F);
+        });
         g_last_bisect_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_bisect).count();
 
-        // ---- all pairs inside every leaf cluster in one batch (d_estimation with pair = 1): the value the reference
-        //      keeps for i < j is the one it computes last, calc_distance(seq[samples[j]], seq[samples[i]]) ----
-        std::vector<Sub*> leaves;
-        collect_leaves(root.get(), leaves);
-        std::vector<size_t> first(leaves.size() + 1, 0);
-        for (size_t k = 0; k < leaves.size(); k++) {
-                const size_t n = leaves[k]->cluster.size();
-                first[k + 1] = first[k] + n * (n - 1) / 2;
-        }
-        ia.assign(first.back(), 0); ib.assign(first.back(), 0); d.assign(first.back(), 0);
-        for (size_t k = 0; k < leaves.size(); k++) {
-                const std::vector<int>& s = leaves[k]->cluster;
-                size_t p = first[k];
-                for (size_t i = 0; i < s.size(); i++)
-                        for (size_t j = i + 1; j < s.size(); j++, p++) { ia[p] = s[j]; ib[p] = s[i]; }
-        }
-        if (!ia.empty() && dist(user, (int)ia.size(), ia.data(), ib.data(), d.data())) return dist_failed();
+        // ---- all pairs inside every leaf cluster of every family in ONE batch (d_estimation with pair = 1): the value the
+        //      reference keeps for i < j is the one it computes last, calc_distance(seq[samples[j]], seq[samples[i]]) ----
+        total = 0;
+        for (Fam& F : fams) { F.p2 = total; if (F.n >= 2) total += F.first_pair.back(); }
+        if (total > (size_t)INT32_MAX) return ka_fail_message((me + ": more than 2^31 in-cluster distances in one batch").c_str());
+        ia.assign(total, 0); ib.assign(total, 0); d.assign(total, 0);
+        for (const Fam& F : fams)
+                for (size_t k = 0; k < F.leaves.size(); k++) {
+                        const std::vector<int>& s = F.leaves[k]->cluster;
+                        size_t p = F.p2 + F.first_pair[k];
+                        for (size_t i = 0; i < s.size(); i++)
+                                for (size_t j = i + 1; j < s.size(); j++, p++) { ia[p] = F.first + s[j]; ib[p] = F.first + s[i]; }
+                }
+        if (total && dist(user, (int)total, ia.data(), ib.data(), d.data())) return dist_failed(who);
 
-        // ---- UPGMA inside the clusters, then labels and tasks in post-order (label_internal, create_tasks,
-        //      sort_tasks(TASK_ORDER_TREE): c ascending == post-order) ----
-        Tree T;
-        std::vector<int> leaf_root(leaves.size());
-        for (size_t k = 0; k < leaves.size(); k++) {
-                const std::vector<int>& s = leaves[k]->cluster;
-                const int n = (int)s.size();
-                std::vector<float> pd((size_t)n * n, 0.0f);
-                size_t p = first[k];
-                for (int i = 0; i < n; i++)
-                        for (int j = i + 1; j < n; j++, p++) {
-                                const float v = with_length_term(d[p], lens[s[j]], lens[s[i]]);
-                                pd[(size_t)i * n + j] = v;
-                                pd[(size_t)j * n + i] = v;
-                        }
-                leaf_root[k] = upgma(T, pd, s);
-        }
-        // stitch the k-means levels above the clusters (iteratively: the recursion can be N deep when splits are lopsided)
-        {
+        // ---- per family: UPGMA inside the clusters, then labels and tasks in post-order (label_internal, create_tasks,
+        //      sort_tasks(TASK_ORDER_TREE): c ascending == post-order), and msa->seq_distances ----
+        std::atomic<int> bad_count(0);
+        for_each_family(n_fam, n_threads, [&](int f) {
+                Fam& F = fams[f];
+                if (F.n < 2) { if (seq_distances) seq_distances[F.first] = 0.0f; return; }
+                const int* flen = lens + F.first;
+                Tree T;
+                std::vector<int> leaf_root(F.leaves.size());
+                for (size_t k = 0; k < F.leaves.size(); k++) {
+                        const std::vector<int>& s = F.leaves[k]->cluster;
+                        const int n = (int)s.size();
+                        std::vector<float> pd((size_t)n * n, 0.0f);
+                        size_t p = F.p2 + F.first_pair[k];
+                        for (int i = 0; i < n; i++)
+                                for (int j = i + 1; j < n; j++, p++) {
+                                        const float v = with_length_term(d[p], flen[s[j]], flen[s[i]]);
+                                        pd[(size_t)i * n + j] = v;
+                                        pd[(size_t)j * n + i] = v;
+                                }
+                        leaf_root[k] = upgma(T, pd, s);
+                }
+                // stitch the k-means levels above the clusters (iteratively: the recursion can be N deep when splits are lopsided)
                 size_t next_leaf = 0;
                 struct Frame { Sub* s; int state; int l; };
                 std::vector<Frame> st;
                 std::vector<int> done;           // node indices of finished subtrees
-                st.push_back(Frame{ root.get(), 0, -1 });
+                st.push_back(Frame{ F.root.get(), 0, -1 });
                 while (!st.empty()) {
-                        Frame& f = st.back();
-                        if (!f.s->l) { done.push_back(leaf_root[next_leaf++]); st.pop_back(); continue; }
-                        if (f.state == 0) { f.state = 1; st.push_back(Frame{ f.s->l.get(), 0, -1 }); continue; }
-                        if (f.state == 1) { f.state = 2; st.push_back(Frame{ f.s->r.get(), 0, -1 }); continue; }
+                        Frame& fr = st.back();
+                        if (!fr.s->l) { done.push_back(leaf_root[next_leaf++]); st.pop_back(); continue; }
+                        if (fr.state == 0) { fr.state = 1; st.push_back(Frame{ fr.s->l.get(), 0, -1 }); continue; }
+                        if (fr.state == 1) { fr.state = 2; st.push_back(Frame{ fr.s->r.get(), 0, -1 }); continue; }
                         const int r = done.back(); done.pop_back();
                         const int l = done.back(); done.pop_back();
                         done.push_back(T.add(l, r, -1));
                         st.pop_back();
                 }
-                if (emit_tasks(T, done.back(), numseq, tasks_abc) != numseq - 1) return ka_fail_message("ka_guide_tree_from: internal error (task count)");
-        }
+                F.tasks.assign(3 * (size_t)(F.n - 1), 0);
+                if (emit_tasks(T, done.back(), F.n, F.tasks.data()) != F.n - 1) bad_count++;
+                // msa->seq_distances (bisectingKmeans.c:244-255)
+                if (seq_distances)
+                        for (int i = 0; i < F.n; i++) {
+                                float sum = 0.0f;
+                                for (int j = 0; j < F.A; j++) sum += F.dm[(size_t)i * F.padded + j];
+                                const float mean_dist = sum / (float)F.A;
+                                seq_distances[F.first + i] = mean_dist / (float)flen[i];
+                        }
+        });
+        if (bad_count) return ka_fail_message((me + ": internal error (task count)").c_str());
 
-        // ---- msa->seq_distances (bisectingKmeans.c:244-255) ----
-        if (seq_distances)
-                for (int i = 0; i < numseq; i++) {
-                        float sum = 0.0f;
-                        for (int j = 0; j < A; j++) sum += dm[(size_t)i * padded + j];
-                        const float mean_dist = sum / (float)A;
-                        seq_distances[i] = mean_dist / (float)lens[i];
-                }
+        // ---- one task list: leaves carry their global index, internal nodes are numseq + the task's place in the list ----
+        int t0 = 0;
+        for (const Fam& F : fams) {
+                if (F.n < 2) continue;
+                for (int t = 0; t < F.n - 1; t++)
+                        for (int k = 0; k < 3; k++) {
+                                const int x = F.tasks[3 * (size_t)t + k];
+                                tasks_abc[3 * (size_t)(t0 + t) + k] = x < F.n ? F.first + x : numseq + t0 + (x - F.n);
+                        }
+                t0 += F.n - 1;
+        }
+        if (n_tasks_out) *n_tasks_out = t0;
         return KA_OK;
 }
 
@@ -496,22 +614,40 @@ __attribute__((visibility("hidden"))) int ka_tasks_from_merges(int numseq, const
 
 // The distance source of the product: the two batches run on the device (ka_bpm.hip).
 namespace {
-struct DeviceDist { ka_ctx* ctx; const uint8_t* codes; const int* off; const int* lens; int numseq; };
+struct DeviceDist { ka_ctx* ctx; const uint8_t* codes; const int* off; const int* lens; int numseq; double ms; };
 int device_dist(void* user, int npairs, const int* ia, const int* ib, int* out)
 {
         DeviceDist* D = (DeviceDist*)user;
-        return ka_bpm_batch(D->ctx, D->codes, D->off, D->lens, D->numseq, ia, ib, npairs, out);
+        if (ka_bpm_batch(D->ctx, D->codes, D->off, D->lens, D->numseq, ia, ib, npairs, out)) return 1;
+        D->ms += ka_pairwise_kernel_ms(D->ctx);
+        return 0;
 }
+thread_local double g_last_dist_ms = 0.0;
 }  // namespace
+// device ms of the distance batches of this thread's last ka_guide_forest (library-internal: ka_run_encoded_batch's stage times)
+__attribute__((visibility("hidden"))) double ka_guide_last_dist_ms(void) { return g_last_dist_ms; }
 
 extern "C" int ka_guide_tree(ka_ctx* ctx, int numseq, const uint8_t* codes, const int* off, const int* lens,
                              int n_threads, const float* dm_scale, int* tasks_abc, float* seq_distances)
 {
         if (!ctx || !codes || !off) return ka_fail_message("ka_guide_tree: bad arguments");
-        DeviceDist D{ ctx, codes, off, lens, numseq };
+        DeviceDist D{ ctx, codes, off, lens, numseq, 0.0 };
         g_km = KmDevice();
         g_km.on = ka_ctx_device_stream(ctx, &g_km.device, &g_km.stream) == 0;
         const int rc = ka_guide_tree_from(numseq, lens, device_dist, &D, n_threads, dm_scale, tasks_abc, seq_distances);
+        g_km = KmDevice();
+        return rc;
+}
+
+extern "C" int ka_guide_forest(ka_ctx* ctx, int n_fam, const int* fam_first, const uint8_t* codes, const int* off, const int* lens,
+                               int n_threads, const float* dm_scale, int* tasks_abc, int* n_tasks_out, float* seq_distances)
+{
+        if (!ctx || !codes || !off || !fam_first || n_fam < 1) return ka_fail_message("ka_guide_forest: bad arguments");
+        DeviceDist D{ ctx, codes, off, lens, fam_first[n_fam], 0.0 };
+        g_km = KmDevice();
+        g_km.on = ka_ctx_device_stream(ctx, &g_km.device, &g_km.stream) == 0;
+        const int rc = ka_guide_forest_from(n_fam, fam_first, lens, device_dist, &D, n_threads, dm_scale, tasks_abc, n_tasks_out, seq_distances);
+        g_last_dist_ms = D.ms;
         g_km = KmDevice();
         return rc;
 }

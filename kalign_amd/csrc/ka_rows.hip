@@ -6,21 +6,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kalign_amd.h"
+#include "ka_forest.h"
 
 // Thread p owns residue p of its sequence: the gap run in front of it (columns colof[p-1]+1 .. colof[p]-1), the
 // letter itself, and -- the last residue -- the trailing gaps and the terminator.  Every byte of the row is
 // written exactly once.
-__global__ void __launch_bounds__(256) ka_rows_kernel(const uint8_t* __restrict__ letters, const int* __restrict__ off,
-                                                      const int* __restrict__ lens, const int* __restrict__ colof,
-                                                      const int* __restrict__ alnlen, uint8_t gap,
-                                                      uint8_t* __restrict__ rows, long long stride)
+__device__ __forceinline__ void ka_row_write(const uint8_t* __restrict__ s, const int* __restrict__ col, const int len, const int n,
+                                             const uint8_t gap, uint8_t* __restrict__ row)
 {
-        const int i = blockIdx.x;
-        const int len = lens[i];
-        const int n = alnlen[i];
-        const uint8_t* s = letters + off[i];
-        const int* col = colof + off[i];
-        uint8_t* row = rows + (long long)i * stride;
         for (int p = threadIdx.x; p < len; p += blockDim.x) {
                 const int c = col[p];
                 const int first = p ? col[p - 1] + 1 : 0;
@@ -33,10 +26,36 @@ __global__ void __launch_bounds__(256) ka_rows_kernel(const uint8_t* __restrict_
         }
 }
 
+__global__ void __launch_bounds__(256) ka_rows_kernel(const uint8_t* __restrict__ letters, const int* __restrict__ off,
+                                                      const int* __restrict__ lens, const int* __restrict__ colof,
+                                                      const int* __restrict__ alnlen, uint8_t gap,
+                                                      uint8_t* __restrict__ rows, long long stride)
+{
+        const int i = blockIdx.x;
+        ka_row_write(letters + off[i], colof + off[i], lens[i], alnlen[i], gap, rows + (long long)i * stride);
+}
+
+// The same with every row at a place of its own (a batch of families, packed: the rows of a family are its own
+// alignment length + 1 apart, family after family)
+__global__ void __launch_bounds__(256) ka_rows_packed_kernel(const uint8_t* __restrict__ letters, const int* __restrict__ off,
+                                                             const int* __restrict__ lens, const int* __restrict__ colof,
+                                                             const int* __restrict__ alnlen, uint8_t gap,
+                                                             uint8_t* __restrict__ rows, const long long* __restrict__ row_off)
+{
+        const int i = blockIdx.x;
+        ka_row_write(letters + off[i], colof + off[i], lens[i], alnlen[i], gap, rows + row_off[i]);
+}
+
 extern "C" void ka_launch_rows(const uint8_t* letters, const int* off, const int* lens, const int* colof, const int* alnlen,
                                int numseq, uint8_t gap, uint8_t* rows, long long stride, hipStream_t stream)
 {
         hipLaunchKernelGGL(ka_rows_kernel, dim3(numseq), dim3(256), 0, stream, letters, off, lens, colof, alnlen, gap, rows, stride);
+}
+
+extern "C" void ka_launch_rows_packed(const uint8_t* letters, const int* off, const int* lens, const int* colof, const int* alnlen,
+                                      int numseq, uint8_t gap, uint8_t* rows, const long long* row_off, hipStream_t stream)
+{
+        hipLaunchKernelGGL(ka_rows_packed_kernel, dim3(numseq), dim3(256), 0, stream, letters, off, lens, colof, alnlen, gap, rows, row_off);
 }
 
 // Position maps of anchor consistency (reference lib/src/anchor_consistency.c:86-114): the coded path of the
@@ -96,20 +115,20 @@ extern "C" void ka_launch_posmaps(const int* paths, const long long* poff, const
 // rows padded to 33 words so that the 16 rows a wave touches at one column sit in different banks.
 #define KA_AD_TILE 16
 #define KA_AD_COLS 128
-__global__ void __launch_bounds__(256) ka_aln_dist_kernel(const uint8_t* __restrict__ rows, long long stride, int alnlen, int n,
-                                                          uint8_t gap, float* __restrict__ dm)
+// tile (bi, bj) of the n x n matrix dm, bj >= bi
+__device__ __forceinline__ void ka_aln_dist_tile(const uint8_t* __restrict__ rows, const long long stride, const int alnlen, const int n,
+                                                 const uint8_t gap, float* __restrict__ dm, const int bi, const int bj)
 {
-        if (blockIdx.x < blockIdx.y) return;                         // tile (y = i tile, x = j tile), j tile >= i tile
         __shared__ uint32_t A[KA_AD_TILE][KA_AD_COLS / 4 + 1], B[KA_AD_TILE][KA_AD_COLS / 4 + 1];
         const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
-        const int i = blockIdx.y * KA_AD_TILE + ti, j = blockIdx.x * KA_AD_TILE + tj;
+        const int i = bi * KA_AD_TILE + ti, j = bj * KA_AD_TILE + tj;
         int matches = 0, aligned = 0;
         for (int c0 = 0; c0 < alnlen; c0 += KA_AD_COLS) {
                 // 256 threads x 2 words: row r = tid / 16 of each tile, words (tid % 16) and (tid % 16) + 16
                 for (int h = 0; h < 2; ++h) {
                         const int w = tj + 16 * h;
                         uint32_t va = 0, vb = 0;
-                        const int ra = blockIdx.y * KA_AD_TILE + ti, rb = blockIdx.x * KA_AD_TILE + ti;
+                        const int ra = bi * KA_AD_TILE + ti, rb = bj * KA_AD_TILE + ti;
                         for (int b = 0; b < 4; ++b) {                // bytes past the row's end read as gaps
                                 const int c = c0 + 4 * w + b;
                                 const uint32_t ca = (ra < n && c < alnlen) ? rows[(long long)ra * stride + c] : gap;
@@ -142,6 +161,23 @@ __global__ void __launch_bounds__(256) ka_aln_dist_kernel(const uint8_t* __restr
         if (i < n && j < n && i == j) dm[(long long)i * n + i] = 0.0f;
 }
 
+__global__ void __launch_bounds__(256) ka_aln_dist_kernel(const uint8_t* __restrict__ rows, long long stride, int alnlen, int n,
+                                                          uint8_t gap, float* __restrict__ dm)
+{
+        if (blockIdx.x < blockIdx.y) return;                         // tile (y = i tile, x = j tile), j tile >= i tile
+        ka_aln_dist_tile(rows, stride, alnlen, n, gap, dm, blockIdx.y, blockIdx.x);
+}
+
+// A batch of families: the rows of all families lie `stride` apart, a family's own alignment is its first alnlen columns
+// (bytes past it read as gaps), its matrix starts at dm + dm_off.  One workgroup per entry of the tile table, which
+// lists the upper-triangle tiles of every family -- the same tile, the same integer counts, the same division.
+__global__ void __launch_bounds__(256) ka_aln_dist_forest_kernel(const uint8_t* __restrict__ rows, long long stride,
+                                                                 const KaAdTile* __restrict__ tiles, uint8_t gap, float* __restrict__ dm)
+{
+        const KaAdTile T = tiles[blockIdx.x];
+        ka_aln_dist_tile(rows + (long long)T.row0 * stride, stride, T.alnlen, T.n, gap, dm + T.dm_off, T.ti, T.tj);
+}
+
 // build_tree_from_pairwise (lib/src/bisectingKmeans.c:1150-1200): mean distance of every sequence to the others,
 // summed in column order like the reference, before UPGMA overwrites the matrix
 __global__ void ka_row_mean_kernel(const float* __restrict__ dm, int n, float* __restrict__ out)
@@ -155,6 +191,20 @@ __global__ void ka_row_mean_kernel(const float* __restrict__ dm, int n, float* _
                 if (j != i) sum += dm[(long long)j * n + i];
         out[i] = (n > 1) ? sum / (float)(n - 1) : 0.0f;
 }
+// ... of a batch of families: thread g owns sequence g of the batch, row g - first of its family's matrix
+__global__ void ka_row_mean_forest_kernel(const float* __restrict__ dm, const KaAdFam* __restrict__ fams, const int* __restrict__ fam_of,
+                                          int numseq, float* __restrict__ out)
+{
+        const int g = blockIdx.x * blockDim.x + threadIdx.x;
+        if (g >= numseq) return;
+        const KaAdFam F = fams[fam_of[g]];
+        const int i = g - F.first, n = F.n;
+        const float* m = dm + F.dm_off;
+        float sum = 0.0f;
+        for (int j = 0; j < n; ++j)
+                if (j != i) sum += m[(long long)j * n + i];
+        out[g] = (n > 1) ? sum / (float)(n - 1) : 0.0f;
+}
 
 // upgma (lib/src/bisectingKmeans.c:974-1053), one launch per merge.  The reference scans all active pairs for the
 // smallest dm[i][j], i < j, taking the first in row-major order on ties (strict '<'); here every active row keeps its
@@ -165,7 +215,7 @@ __global__ void ka_row_mean_kernel(const float* __restrict__ dm, int n, float* _
 //      dm[i][a] = (dm[i][a] + dm[i][b]) * 0.5 + 0.001 -- the value the reference writes to dm[a][i] and mirrors --,
 //      row a is rebuilt from row b (not written in this step), and a row key is rescanned only when its minimum sat in
 //      column a or b.  Keys are double-buffered: phase A of slow workgroups still reads the old ones.
-struct KaUpgma { float* dm; int* active; unsigned long long* key[2]; int2* merges; int n; };
+// (KaUpgma: ka_forest.h)
 
 __device__ __forceinline__ unsigned long long ka_upgma_key(float v, unsigned int idx)
 {
@@ -272,6 +322,13 @@ extern "C" void ka_launch_aln_dist(const uint8_t* rows, long long stride, int al
         hipLaunchKernelGGL(ka_row_mean_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, dm, n, means);
 }
 
+extern "C" void ka_launch_aln_dist_forest(const uint8_t* rows, long long stride, const KaAdTile* tiles, int n_tiles, const KaAdFam* fams,
+                                          const int* fam_of, int numseq, uint8_t gap, float* dm, float* means, hipStream_t stream)
+{
+        hipLaunchKernelGGL(ka_aln_dist_forest_kernel, dim3(n_tiles), dim3(256), 0, stream, rows, stride, tiles, gap, dm);
+        hipLaunchKernelGGL(ka_row_mean_forest_kernel, dim3((numseq + 255) / 256), dim3(256), 0, stream, dm, fams, fam_of, numseq, means);
+}
+
 // ---- all n - 1 merges in ONE launch of ONE workgroup ----
 // The merges depend on each other, so the loop is a latency chain: per launch it costs the dependent dispatch (~11 us),
 // per cluster-wide barrier in HBM a release/acquire pair across the XCDs' L2s (~21 us, measured in round 2).  One
@@ -287,8 +344,6 @@ extern "C" void ka_launch_aln_dist(const uint8_t* rows, long long stride, int al
 //      the new candidate (i < a); row a's key is the minimum over the v of the columns > a
 //   C  one wave per listed row: the key from the columns loaded in B, with v in place of column a.
 // Barriers between the phases wait for LDS only; the one in front of B also waits for the previous step's stores.
-#define KA_UPGMA_NT 512
-#define KA_UPGMA_ONE_WG_MAX 6144
 #define KA_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 template <int CTRL, int ROW_MASK>
@@ -316,7 +371,7 @@ __device__ __forceinline__ unsigned long long ka_wave_min_u64(unsigned long long
 
 // PER: rows per thread (n <= PER * KA_UPGMA_NT); SV * 64: columns of a listed row per round trip
 template <int PER, int SV>
-__global__ void __launch_bounds__(KA_UPGMA_NT) ka_upgma_one_wg_kernel(KaUpgma U)
+__device__ __forceinline__ void ka_upgma_one_wg(const KaUpgma& U)
 {
         extern __shared__ __attribute__((aligned(16))) unsigned char ka_upgma_lds[];
         __shared__ unsigned long long red[KA_UPGMA_NT / 64], red_a[KA_UPGMA_NT / 64];
@@ -444,6 +499,47 @@ __global__ void __launch_bounds__(KA_UPGMA_NT) ka_upgma_one_wg_kernel(KaUpgma U)
                 }
                 KA_LDS_BARRIER();
         }
+}
+
+template <int PER, int SV>
+__global__ void __launch_bounds__(KA_UPGMA_NT) ka_upgma_one_wg_kernel(KaUpgma U)
+{
+        ka_upgma_one_wg<PER, SV>(U);
+}
+
+// A batch of families: one workgroup per family, its record from a table.  A family's matrix, flags and merges are its
+// own slices; the LDS layout follows the family's own n (the launch reserves room for the largest family of the table).
+template <int PER, int SV>
+__global__ void __launch_bounds__(KA_UPGMA_NT) ka_upgma_forest_kernel(const KaUpgma* __restrict__ table)
+{
+        const KaUpgma U = table[blockIdx.x];
+        ka_upgma_one_wg<PER, SV>(U);
+}
+
+// table[first[k] .. first[k + 1]): the families of size class k (n <= 512, 1024, 2048, 4096, KA_UPGMA_ONE_WG_MAX: the PER of the
+// one-workgroup kernel), max_n[k] the largest of them.  One launch per class that has families: a large family then occupies
+// its workgroup for its own merges and nobody else's.  Returns a bit per class that could not be launched (more LDS than this
+// GPU grants): the caller runs those families through ka_launch_upgma.
+extern "C" int ka_launch_upgma_forest(const KaUpgma* table, const int* first, const int* max_n, hipStream_t stream)
+{
+        int failed = 0;
+        auto go = [&](auto kernel, const int k) {
+                const int count = first[k + 1] - first[k];
+                if (count <= 0) return;
+                const int lds = max_n[k] * 17 + 16;                    // keys, list, listv, act
+                if (lds > 65536 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, KA_UPGMA_ONE_WG_MAX * 17 + 16) != hipSuccess) {
+                        (void)hipGetLastError();
+                        failed |= 1 << k;
+                        return;
+                }
+                hipLaunchKernelGGL(kernel, dim3(count), dim3(KA_UPGMA_NT), lds, stream, table + first[k]);
+        };
+        go(ka_upgma_forest_kernel<1, 8>, 0);
+        go(ka_upgma_forest_kernel<2, 16>, 1);
+        go(ka_upgma_forest_kernel<4, 32>, 2);
+        go(ka_upgma_forest_kernel<8, 32>, 3);
+        go(ka_upgma_forest_kernel<KA_UPGMA_ONE_WG_MAX / KA_UPGMA_NT, 32>, 4);
+        return failed;
 }
 
 // ---- launching the n - 1 dependent merge steps, one launch per step ----
