@@ -346,6 +346,7 @@ int ka_bpm_batch(ka_ctx* ctx, const uint8_t* codes, const int* off, const int* l
  *                    alnlen, gap_char are ignored)
  *   tasks_abc[3*(numseq-1)], seq_distances[numseq] (may be NULL)  as for ka_guide_tree
  *   dm_out[numseq*numseq]  (may be NULL) the identity distances, before UPGMA consumed them
+ * One family is a batch of one: the work is ka_aln_guide_forest's (below), with n_fam = 1.
  */
 int ka_aln_guide_tree(ka_ctx* ctx, int numseq, const uint8_t* rows, long long row_stride, int alnlen, uint8_t gap_char,
                       int* tasks_abc, float* seq_distances, float* dm_out);
@@ -420,10 +421,10 @@ int ka_guide_forest(ka_ctx* ctx, int n_fam, const int* fam_first, const uint8_t*
                     int n_threads, const float* dm_scale, int* tasks_abc, int* n_tasks_out, float* seq_distances);
 
 /*
- * ka_aln_guide_tree for a batch of families: the identity distances of all families in one launch, their row means in one,
- * and the UPGMAs one workgroup per family (a launch per size class of the one-workgroup kernel; a family of more than 6144
- * sequences goes through the per-merge launches on its own).  Per family, tasks, seq_distances and distances are bit for bit
- * those of ka_aln_guide_tree on that family alone.
+ * The realignment trees of a batch of families (ka_aln_guide_tree: a batch of one): the identity distances of all families
+ * in one launch, their row means in one, and the UPGMAs one workgroup per family (a launch per size class of the
+ * one-workgroup kernel; a family of more than 6144 sequences goes through the per-merge launches on its own).  Per family,
+ * tasks, seq_distances and distances depend on that family's rows alone.
  *   rows             numseq rows, row_stride apart; family f's alignment is the first alnlens[f] <= row_stride bytes of its rows
  *                    (what lies beyond is not read); or NULL: the rows the last ka_tree_aligned_rows of a forest job (or of a
  *                    single tree) left in HBM -- fam_first must describe that job's alignments; row_stride, alnlens and gap_char
@@ -437,11 +438,13 @@ int ka_aln_guide_forest(ka_ctx* ctx, int n_fam, const int* fam_first, const uint
 /*
  * ka_run_encoded_refine for a batch of families in one call: the guide trees of all families (ka_guide_forest), one forest
  * ka_tree_upload with KA_FLAG_DEVICE_GAPS, ka_tree_build_consistency, ka_tree_run (refine_mode 3: ka_tree_refine), per
- * realignment iteration rows in HBM -> ka_aln_guide_forest -> upload with KA_FLAG_KEEP_CONSISTENCY -> run, refine_mode 1
- * (| KA_REFINE_ADAPTIVE), rows.  refine_mode 2 (KALIGN_REFINE_CONFIDENT) is refused: its threshold is the median confidence of
- * one alignment's edges, and ka_tree_refine takes it over all tasks of a job.  All families share subm / scal.  Every family comes out as ka_run_encoded_refine aligns it
- * alone: a family of n_f >= 3 sequences gets K_f = min(n_anchors, n_f) anchors, a smaller one no table.  One forest job holds
- * one anchor count, so families of equal K_f are one job and the jobs run one after the other on the context.
+ * realignment iteration rows in HBM -> ka_aln_guide_forest -> upload with KA_FLAG_KEEP_CONSISTENCY -> run, refine_mode 1 (|
+ * KA_REFINE_ADAPTIVE), rows.  refine_mode 2 (KALIGN_REFINE_CONFIDENT) is refused: its threshold is the median confidence of
+ * one alignment's edges, and ka_tree_refine takes it over all tasks of a job.  All families share subm / scal.  Every
+ * family comes out as ka_run_encoded_refine aligns it alone (both calls run the same sequence of steps on a forest job,
+ * ka_run_encoded_refine on a job of one family): a family of n_f >= 3 sequences gets K_f = min(n_anchors, n_f) anchors, a
+ * smaller one no table.  One forest job holds one anchor count, so families of equal K_f are one job and the jobs run one
+ * after the other on the context.
  *   tree_codes / codes / letters, off, lens   all numseq = fam_first[n_fam] sequences, as for ka_run_encoded
  *   dm_scale         as for ka_guide_forest
  *   alnlen_out[numseq]  (may be NULL) the alignment length of every sequence's family (a family of one: its length)

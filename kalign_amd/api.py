@@ -699,16 +699,22 @@ def _aln_guide_tree(self, rows=None, n=None, gap=b"-", want_dm=False):
 Context.aln_guide_tree = _aln_guide_tree
 
 
-def _run_encoded(self, tree_codes, codes, letters, subm, scal, n_anchors=0, weight=2.0, realign=0, dm_scale=None,
-                 n_threads=1, gap=b"-", refine=0):
-    """ka_run_encoded(_refine): guide tree, (consistency,) alignment, `realign` realignment iterations, (refinement,)
-    rows -- one call.  refine: 0, 1, 2 (| 256 adaptive budget) or 3, as kalign_run_seeded's argument.
-    Returns the aligned rows (bytes) in the order of the input sequences."""
+def _three_encodings(tree_codes, codes, letters):
+    """the sequences in the tree alphabet, in the alignment alphabet and as letters, flattened: (tflat, cflat, lflat, off, lens)"""
     tflat, off, lens = _flatten(tree_codes)
     cflat, _, _ = _flatten(codes)
     lflat = np.ascontiguousarray(np.concatenate([np.frombuffer(x.encode() if isinstance(x, str) else bytes(x), np.uint8) for x in letters]))
     if len(lflat) != len(cflat) or len(tflat) != len(cflat):
         raise KalignAmdError("the three encodings of the sequences differ in length")
+    return tflat, cflat, lflat, off, lens
+
+
+def _run_encoded(self, tree_codes, codes, letters, subm, scal, n_anchors=0, weight=2.0, realign=0, dm_scale=None,
+                 n_threads=1, gap=b"-", refine=0):
+    """ka_run_encoded(_refine): guide tree, (consistency,) alignment, `realign` realignment iterations, (refinement,)
+    rows -- one call.  refine: 0, 1, 2 (| 256 adaptive budget) or 3, as kalign_run_seeded's argument.
+    Returns the aligned rows (bytes) in the order of the input sequences."""
+    tflat, cflat, lflat, off, lens = _three_encodings(tree_codes, codes, letters)
     n = len(codes)
     sub = np.ascontiguousarray(subm, np.float32).reshape(-1)
     sc = np.ascontiguousarray(scal, np.float32)
@@ -816,12 +822,10 @@ def _run_families(self, families, subm, scal, n_anchors=0, weight=2.0, realign=0
     sizes = [len(f[1]) for f in families]
     if not sizes or min(sizes) < 1:
         raise KalignAmdError("run_families: every family needs a sequence")
-    tflat, off, lens = _flatten([c for f in families for c in f[0]])
-    cflat, _, _ = _flatten([c for f in families for c in f[1]])
-    lflat = np.ascontiguousarray(np.concatenate([np.frombuffer(x.encode() if isinstance(x, str) else bytes(x), np.uint8)
-                                                 for f in families for x in f[2]]))
-    if len(lflat) != len(cflat) or len(tflat) != len(cflat):
-        raise KalignAmdError("the three encodings of the sequences differ in length")
+    tree_codes = [x for f in families for x in f[0]]
+    codes = [x for f in families for x in f[1]]
+    letters = [x for f in families for x in f[2]]
+    tflat, cflat, lflat, off, lens = _three_encodings(tree_codes, codes, letters)
     first = _fam_first(sizes)
     sub = np.ascontiguousarray(subm, np.float32).reshape(-1)
     sc = np.ascontiguousarray(scal, np.float32)

@@ -98,7 +98,7 @@ extern "C" void ka_ctx_destroy(ka_ctx* c)
         c->d_adm.release(); c->d_amean.release(); c->d_uactive.release(); c->d_ucand.release(); c->d_umerges.release();
         c->d_cons_maps.release(); c->d_colof.release(); c->d_colof_init.release(); c->d_sip.release();
         c->d_cons_map_off.release(); c->d_sip_off.release();
-        c->d_adtiles.release(); c->d_adfams.release(); c->d_fam_of.release(); c->d_utable.release(); c->d_row_off.release(); c->d_batch_rows.release();
+        c->d_adtiles.release(); c->d_adfams.release(); c->d_fam_of.release(); c->d_utable.release(); c->d_row_off.release();
         for (int k = 0; k < 2; k++) { if (c->pin[k]) (void)hipHostFree(c->pin[k]); if (c->pin_ev[k]) (void)hipEventDestroy(c->pin_ev[k]); }
         if (c->h_trace) (void)hipHostFree(c->h_trace);
         for (hipEvent_t e : c->launch_ev) (void)hipEventDestroy(e);
@@ -681,7 +681,7 @@ extern "C" int ka_tree_adopt_alignment(ka_ctx* c, const ka_task_rec* recs, const
         c->flags |= KA_FLAG_DEVICE_GAPS;
         c->h_counters[2] = 0;                                         // (no coded paths of its own)
         c->ran = true; c->synced = true; c->partial = false; c->state_valid = false;
-        c->rows_n = 0; c->rows_forest_n = 0;
+        c->rows.forget();
         return KA_OK;
 }
 
@@ -704,21 +704,26 @@ static int rows_prepare(ka_ctx* c, const uint8_t* letters, std::vector<int>& ale
         return KA_OK;
 }
 
-// the rows in HBM (c->d_rows, row_stride apart); they stay there for ka_aln_guide_tree
-static int rows_build(ka_ctx* c, const uint8_t* letters, uint8_t gap_char, const std::vector<int>& alen, int widest, long long row_stride)
+// the rows in HBM (c->d_rows): row_stride apart, where they stay for ka_aln_guide_tree / _forest; or, with row_off, row i at
+// ascending row_off[i], one after the other (row_stride is not looked at) -- a packed hand-out, which no tree is built from
+static int rows_build(ka_ctx* c, const uint8_t* letters, uint8_t gap_char, const std::vector<int>& alen, long long row_stride,
+                      const std::vector<long long>* row_off = nullptr)
 {
-        const size_t bytes = (size_t)c->numseq * (size_t)row_stride;
-        if (c->d_letters.alloc(c->h_codes.size()) || c->d_alnlen.alloc(c->numseq) || c->d_rows.alloc(bytes)) return fail("hipMalloc failed");
+        const size_t bytes = row_off ? (size_t)(row_off->back() + alen.back() + 1) : (size_t)c->numseq * (size_t)row_stride;
+        if (c->d_letters.alloc(c->h_codes.size()) || c->d_alnlen.alloc(c->numseq) || c->d_rows.alloc(bytes) || (row_off && c->d_row_off.alloc(c->numseq)))
+                return fail("hipMalloc failed");
+        // first of all: from here on d_rows no longer holds what the record says -- a packed hand-out overwrites the strided rows
+        // of the last pass and leaves the record empty, so that no tree is built from rows that are not `stride` apart
+        c->rows.forget();
         HIPCHK(hipMemcpyAsync(c->d_letters.p, letters, c->h_codes.size(), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_alnlen.p, alen.data(), sizeof(int) * c->numseq, hipMemcpyHostToDevice, c->stream));
+        if (row_off) HIPCHK(hipMemcpyAsync(c->d_row_off.p, row_off->data(), sizeof(long long) * c->numseq, hipMemcpyHostToDevice, c->stream));
         ka_launch_rows(c->d_letters.p, c->d_seq_off.p, c->d_node_len.p, c->d_colof.p, c->d_alnlen.p, c->numseq, gap_char,
-                       c->d_rows.p, row_stride, c->stream);
+                       c->d_rows.p, row_stride, row_off ? c->d_row_off.p : nullptr, c->stream);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(c->stream));                      // `alen` and `letters` are the caller's
-        // (ka_aln_guide_tree: one alignment only, a forest has no common row length; ka_aln_guide_forest takes either)
-        c->rows_n = (c->n_tasks == c->numseq - 1) ? c->numseq : 0;
-        c->rows_forest_n = c->numseq; c->rows_alen = alen;
-        c->rows_stride = row_stride; c->rows_alnlen = widest; c->rows_gap = gap_char;
+        HIPCHK(hipStreamSynchronize(c->stream));                      // `alen`, `letters` and `row_off` are the caller's
+        // (one_tree: a forest has no common row length)
+        if (!row_off) c->rows = KaRowsHeld{ c->numseq, row_stride, gap_char, c->n_tasks == c->numseq - 1, alen };
         return KA_OK;
 }
 
@@ -731,60 +736,132 @@ extern "C" int ka_tree_aligned_rows(ka_ctx* c, const uint8_t* letters, uint8_t g
         if (rows_prepare(c, letters, alen, &widest)) return KA_FAIL;
         if (!rows_out) { memcpy(alnlen_out, alen.data(), sizeof(int) * c->numseq); return KA_OK; }       // size query
         if (row_stride < (long long)widest + 1) return fail("row_stride is smaller than the longest alignment + terminator");
-        if (rows_build(c, letters, gap_char, alen, widest, row_stride)) return KA_FAIL;
+        if (rows_build(c, letters, gap_char, alen, row_stride)) return KA_FAIL;
         if (copy_to_host(c, rows_out, c->d_rows.p, (size_t)c->numseq * (size_t)row_stride)) return KA_FAIL;
         if (alnlen_out) memcpy(alnlen_out, alen.data(), sizeof(int) * c->numseq);
         return KA_OK;
 }
 
 // ---- realignment (kalign_run_realign, aln_wrap.c:449-495): compute_aln_pairwise_dist + build_tree_from_pairwise ----
+// One family is a batch of one: aln_guide_forest does the work (its numbering of one family's tasks is the family's own)
+// and names its errors after the entry point that was called.
+static int aln_guide_forest(const char* who, ka_ctx* c, int n_fam, const int* fam_first, const uint8_t* rows, long long row_stride,
+                            const int* alnlens, uint8_t gap_char, int* tasks_abc, float* seq_distances, float* dm_out);
+// Without `rows` it takes the rows of one finished single-tree run only, as it always has.
 extern "C" int ka_aln_guide_tree(ka_ctx* c, int numseq, const uint8_t* rows, long long row_stride, int alnlen, uint8_t gap_char,
                                  int* tasks_abc, float* seq_distances, float* dm_out)
 {
         if (!c) return fail("null ctx");
         if (!tasks_abc) return fail("null argument");
-        HIPCHK(hipSetDevice(c->device));
-        const uint8_t* d_rows = nullptr;
         if (rows) {
                 if (numseq < 2 || alnlen < 1 || row_stride < alnlen) return fail("ka_aln_guide_tree: bad arguments");
-                const size_t bytes = (size_t)numseq * (size_t)row_stride;
-                if (c->d_rows.alloc(bytes)) return fail("hipMalloc failed");
-                HIPCHK(hipMemcpyAsync(c->d_rows.p, rows, bytes, hipMemcpyHostToDevice, c->stream));
-                c->rows_n = 0; c->rows_forest_n = 0;                  // no longer the rows of the last run
         } else {
-                if (c->rows_n < 2) return fail("ka_aln_guide_tree: no rows on the device (call ka_tree_aligned_rows on a finished single-tree run first)");
-                if (numseq != c->rows_n) return fail("ka_aln_guide_tree: numseq does not match the rows on the device");
-                row_stride = c->rows_stride; alnlen = c->rows_alnlen; gap_char = c->rows_gap;
+                if (!c->rows.one_tree || c->rows.n < 2) return fail("ka_aln_guide_tree: no rows on the device (call ka_tree_aligned_rows on a finished single-tree run first)");
+                if (numseq != c->rows.n) return fail("ka_aln_guide_tree: numseq does not match the rows on the device");
         }
-        d_rows = c->d_rows.p;
-        if (numseq > 46340) return fail("ka_aln_guide_tree: more than 46340 sequences (pair indices are 32-bit)");
-        const size_t nn = (size_t)numseq * (size_t)numseq;
-        if (c->d_adm.alloc(nn) || c->d_amean.alloc(numseq) || c->d_uactive.alloc(numseq) || c->d_ucand.alloc(2 * (size_t)numseq) ||
-            c->d_umerges.alloc(numseq))
-                return fail("hipMalloc failed");
-        ka_launch_aln_dist(d_rows, row_stride, alnlen, numseq, gap_char, c->d_adm.p, c->d_amean.p, c->stream);
-        HIPCHK(hipGetLastError());
-        if (dm_out) HIPCHK(hipMemcpyAsync(dm_out, c->d_adm.p, sizeof(float) * nn, hipMemcpyDeviceToHost, c->stream));
-        if (seq_distances) HIPCHK(hipMemcpyAsync(seq_distances, c->d_amean.p, sizeof(float) * numseq, hipMemcpyDeviceToHost, c->stream));
-        std::vector<int> ones(numseq, 1);
-        HIPCHK(hipMemcpyAsync(c->d_uactive.p, ones.data(), sizeof(int) * numseq, hipMemcpyHostToDevice, c->stream));
-        ka_launch_upgma(c->d_adm.p, c->d_uactive.p, c->d_ucand.p, c->d_umerges.p, numseq, c->env.upgma_launches ? 1 : 0, c->stream);
-        HIPCHK(hipGetLastError());
-        std::vector<int> merges(2 * (size_t)numseq);
-        HIPCHK(hipMemcpyAsync(merges.data(), c->d_umerges.p, sizeof(int2) * (numseq - 1), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return ka_tasks_from_merges(numseq, merges.data(), tasks_abc);
+        const int fam_first[2] = { 0, numseq };
+        return aln_guide_forest("ka_aln_guide_tree", c, 1, fam_first, rows, row_stride, &alnlen, gap_char, tasks_abc, seq_distances, dm_out);
 }
 
-// ---- kalign_run_seeded / kalign_run_realign between "sequences encoded" and "rows finalised" (aln_wrap.c:144-251,361-527)
-//      as one call: the composition of the entry points above, with the intermediate rows of realignment passes
-//      never leaving HBM ----
+// ---- kalign_run_seeded / kalign_run_realign between "trees built" and "alignment finished" (aln_wrap.c:144-251,361-527):
+//      upload, consistency, alignment, realign_iterations x (rows, trees from the rows, upload, alignment), refinement --
+//      the composition of the entry points above, with the intermediate rows of realignment passes never leaving HBM.
+//      One family (ka_run_encoded) or the families of a batch that share an anchor count (ka_run_encoded_batch) ----
 // refine_mode: 0 none; 1 / 2 (| KA_REFINE_ADAPTIVE) refine_alignment after the last alignment (aln_wrap.c:229-232, :506-509);
 // 3 KALIGN_REFINE_INLINE: every alignment is create_msa_tree_inline_refine instead of create_msa_tree (:222-226, :498-502)
+static bool refine_mode_ok(int refine_mode)
+{
+        const int base = refine_mode & 255;
+        return refine_mode >= 0 && base <= 3 && !(refine_mode & ~(255 | KA_REFINE_ADAPTIVE)) && (!(refine_mode & KA_REFINE_ADAPTIVE) || base == 1 || base == 2);
+}
+
+// the device ms per stage of ka_batch_stats (ms[1] alignment runs, [2] realignment trees, [3] rows), between two events of its own
+struct StageClock {
+        double* ms;
+        hipEvent_t ev[2] = { nullptr, nullptr };
+        ~StageClock() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+        int mark(int k, hipStream_t s) { HIPCHK(hipEventRecord(ev[k], s)); return KA_OK; }
+        // what the stream did since the other event: ev[k] goes in behind it
+        int lap(int k, int stage, hipStream_t s)
+        {
+                float t = 0.0f;
+                HIPCHK(hipEventRecord(ev[k], s));
+                HIPCHK(hipEventSynchronize(ev[k]));
+                HIPCHK(hipEventElapsedTime(&t, ev[1 - k], ev[k]));
+                ms[stage] += t;
+                return KA_OK;
+        }
+        void run_done(ka_ctx* c)                                      // a synchronised ka_tree_run / _refine
+        {
+                float t = 0.0f;
+                if (hipEventElapsedTime(&t, c->ev0, c->ev1) == hipSuccess) ms[1] += t; else (void)hipGetLastError();
+        }
+};
+
+// families [fam_first[f], fam_first[f + 1]) of sequences numbered from 0, their trees in ka_guide_forest's numbering
+struct AlignJob {
+        int numseq, n_fam; const int* fam_first;
+        const uint8_t *codes, *letters; const int *off, *lens;
+        int n_tasks; int* tasks; float* sd;                          // the first trees; every realignment pass replaces them
+        const float *subm, *scal;
+        int n_anchors; float weight; int realign_iterations, refine_mode; uint8_t gap_char;
+};
+
+// ends with rows_prepare done: alen, widest.  clk: the stage times of a batch (null: no event is recorded or waited for)
+static int align_job(ka_ctx* c, const AlignJob& J, std::vector<int>& alen, int* widest, StageClock* clk)
+{
+        const int base = J.refine_mode & 255;
+        auto align = [&]() -> int {
+                if (base == 3 ? ka_tree_refine(c, 3, nullptr) : ka_tree_run(c)) return KA_FAIL;
+                if (ka_tree_sync(c)) return KA_FAIL;
+                if (clk) clk->run_done(c);
+                return KA_OK;
+        };
+        if (ka_tree_upload(c, J.numseq, J.codes, J.off, J.lens, J.sd, J.n_tasks, J.tasks, J.subm, J.scal, KA_FLAG_DEVICE_GAPS)) return KA_FAIL;
+        if (J.n_anchors > 0 && ka_tree_build_consistency(c, J.n_anchors, J.weight)) return KA_FAIL;
+        if (align()) return KA_FAIL;
+        for (int it = 0; it < J.realign_iterations; it++) {
+                if (rows_prepare(c, J.letters, alen, widest)) return KA_FAIL;
+                if (clk && clk->mark(0, c->stream)) return KA_FAIL;
+                if (rows_build(c, J.letters, J.gap_char, alen, (long long)*widest + 1)) return KA_FAIL;
+                if (clk && clk->lap(1, 3, c->stream)) return KA_FAIL;
+                if (ka_aln_guide_forest(c, J.n_fam, J.fam_first, nullptr, 0, nullptr, 0, J.tasks, J.sd, nullptr)) return KA_FAIL;
+                if (clk && clk->lap(0, 2, c->stream)) return KA_FAIL;
+                if (ka_tree_upload(c, J.numseq, J.codes, J.off, J.lens, J.sd, J.n_tasks, J.tasks, J.subm, J.scal,
+                                   KA_FLAG_DEVICE_GAPS | KA_FLAG_KEEP_CONSISTENCY)) return KA_FAIL;
+                if (align()) return KA_FAIL;
+        }
+        if (base == 1 || base == 2) {
+                if (ka_tree_refine(c, J.refine_mode, nullptr) || ka_tree_sync(c)) return KA_FAIL;
+                if (clk) clk->run_done(c);
+        }
+        return rows_prepare(c, J.letters, alen, widest);
+}
+
+// one family on the caller's own arrays
 static int run_encoded(ka_ctx* c, int numseq, const uint8_t* tree_codes, const uint8_t* codes, const uint8_t* letters,
                        const int* off, const int* lens, const float* subm, const float* scal,
                        int n_anchors, float weight, int realign_iterations, const float* dm_scale, int n_threads, int refine_mode,
-                       uint8_t gap_char, uint8_t* rows_out, long long row_stride, int* alnlen_out);
+                       uint8_t gap_char, uint8_t* rows_out, long long row_stride, int* alnlen_out)
+{
+        if (!c) return fail("null ctx");
+        if (numseq < 2 || !tree_codes || !codes || !letters || !off || !lens || !subm || !scal || (!rows_out && !alnlen_out))
+                return fail("ka_run_encoded: bad arguments");
+        std::vector<int> tasks(3 * (size_t)(numseq - 1));
+        std::vector<float> sd(numseq);
+        if (ka_guide_tree(c, numseq, tree_codes, off, lens, n_threads, dm_scale, tasks.data(), sd.data())) return KA_FAIL;
+        const int fam_first[2] = { 0, numseq };
+        const AlignJob J{ numseq, 1, fam_first, codes, letters, off, lens, numseq - 1, tasks.data(), sd.data(), subm, scal,
+                          n_anchors, weight, realign_iterations, refine_mode, gap_char };
+        std::vector<int> alen;
+        int widest = 0;
+        if (align_job(c, J, alen, &widest, nullptr)) return KA_FAIL;
+        if (alnlen_out) memcpy(alnlen_out, alen.data(), sizeof(int) * numseq);
+        if (!rows_out) return KA_OK;                                  // the alignment stays on the device: ka_tree_aligned_rows fetches it
+        if (row_stride < (long long)widest + 1) { g_err = "ka_run_encoded: row_stride is smaller than the alignment + terminator (alnlen_out says how long; ka_tree_aligned_rows fetches the rows)"; return KA_ERR_ROWS_STRIDE; }
+        if (rows_build(c, letters, gap_char, alen, row_stride)) return KA_FAIL;
+        return copy_to_host(c, rows_out, c->d_rows.p, (size_t)numseq * (size_t)row_stride);
+}
 
 extern "C" int ka_run_encoded(ka_ctx* c, int numseq, const uint8_t* tree_codes, const uint8_t* codes, const uint8_t* letters,
                               const int* off, const int* lens, const float* subm, const float* scal,
@@ -800,54 +877,13 @@ extern "C" int ka_run_encoded_refine(ka_ctx* c, int numseq, const uint8_t* tree_
                                      int n_anchors, float weight, int realign_iterations, const float* dm_scale, int n_threads,
                                      int refine_mode, uint8_t gap_char, uint8_t* rows_out, long long row_stride, int* alnlen_out)
 {
-        const int base = refine_mode & 255;
-        if (refine_mode < 0 || base > 3 || (refine_mode & ~(255 | KA_REFINE_ADAPTIVE)) || ((refine_mode & KA_REFINE_ADAPTIVE) && base != 1 && base != 2))
-                return fail("ka_run_encoded_refine: refine_mode must be 0, 1, 2 (optionally | KA_REFINE_ADAPTIVE) or 3");
+        if (!refine_mode_ok(refine_mode)) return fail("ka_run_encoded_refine: refine_mode must be 0, 1, 2 (optionally | KA_REFINE_ADAPTIVE) or 3");
         return run_encoded(c, numseq, tree_codes, codes, letters, off, lens, subm, scal, n_anchors, weight, realign_iterations, dm_scale,
                            n_threads, refine_mode, gap_char, rows_out, row_stride, alnlen_out);
 }
 
-static int run_encoded(ka_ctx* c, int numseq, const uint8_t* tree_codes, const uint8_t* codes, const uint8_t* letters,
-                       const int* off, const int* lens, const float* subm, const float* scal,
-                       int n_anchors, float weight, int realign_iterations, const float* dm_scale, int n_threads, int refine_mode,
-                       uint8_t gap_char, uint8_t* rows_out, long long row_stride, int* alnlen_out)
-{
-        const bool inline_refine = (refine_mode & 255) == 3;
-        auto align = [&]() -> int {
-                if (inline_refine ? ka_tree_refine(c, 3, nullptr) : ka_tree_run(c)) return KA_FAIL;
-                return ka_tree_sync(c);
-        };
-        if (!c) return fail("null ctx");
-        if (numseq < 2 || !tree_codes || !codes || !letters || !off || !lens || !subm || !scal || (!rows_out && !alnlen_out))
-                return fail("ka_run_encoded: bad arguments");
-        std::vector<int> tasks(3 * (size_t)(numseq - 1));
-        std::vector<float> sd(numseq);
-        if (ka_guide_tree(c, numseq, tree_codes, off, lens, n_threads, dm_scale, tasks.data(), sd.data())) return KA_FAIL;
-        if (ka_tree_upload(c, numseq, codes, off, lens, sd.data(), numseq - 1, tasks.data(), subm, scal, KA_FLAG_DEVICE_GAPS)) return KA_FAIL;
-        if (n_anchors > 0 && ka_tree_build_consistency(c, n_anchors, weight)) return KA_FAIL;
-        if (align()) return KA_FAIL;
-        std::vector<int> alen;
-        int widest = 0;
-        for (int it = 0; it < realign_iterations; it++) {
-                if (rows_prepare(c, letters, alen, &widest) || rows_build(c, letters, gap_char, alen, widest, (long long)widest + 1)) return KA_FAIL;
-                if (ka_aln_guide_tree(c, numseq, nullptr, 0, 0, 0, tasks.data(), sd.data(), nullptr)) return KA_FAIL;
-                if (ka_tree_upload(c, numseq, codes, off, lens, sd.data(), numseq - 1, tasks.data(), subm, scal,
-                                   KA_FLAG_DEVICE_GAPS | KA_FLAG_KEEP_CONSISTENCY)) return KA_FAIL;
-                if (align()) return KA_FAIL;
-        }
-        if ((refine_mode & 255) == 1 || (refine_mode & 255) == 2) {
-                if (ka_tree_refine(c, refine_mode, nullptr) || ka_tree_sync(c)) return KA_FAIL;
-        }
-        if (rows_prepare(c, letters, alen, &widest)) return KA_FAIL;
-        if (alnlen_out) memcpy(alnlen_out, alen.data(), sizeof(int) * numseq);
-        if (!rows_out) return KA_OK;                                  // the alignment stays on the device: ka_tree_aligned_rows fetches it
-        if (row_stride < (long long)widest + 1) { g_err = "ka_run_encoded: row_stride is smaller than the alignment + terminator (alnlen_out says how long; ka_tree_aligned_rows fetches the rows)"; return KA_ERR_ROWS_STRIDE; }
-        if (rows_build(c, letters, gap_char, alen, widest, row_stride)) return KA_FAIL;
-        return copy_to_host(c, rows_out, c->d_rows.p, (size_t)numseq * (size_t)row_stride);
-}
 
-
-// ---- a batch of families: realignment trees of all of them in a handful of launches, and the one call --------------------
+// ---- a batch of families: the realignment trees of all of them in a handful of launches, and the one call --------------------
 static int check_fam_first(const char* who, int n_fam, const int* fam_first)
 {
         const std::string me(who);
@@ -860,37 +896,44 @@ static int check_fam_first(const char* who, int n_fam, const int* fam_first)
         return KA_OK;
 }
 
-// compute_aln_pairwise_dist + build_tree_from_pairwise (ka_aln_guide_tree) for every family of a batch: one launch of the
+// compute_aln_pairwise_dist + build_tree_from_pairwise for every family of a batch: one launch of the
 // identity distances over a table of tiles, one of the row means, and the UPGMAs one workgroup per family, a launch per size
 // class.  The task list comes back in the forest numbering of ka_guide_forest.
 extern "C" int ka_aln_guide_forest(ka_ctx* c, int n_fam, const int* fam_first, const uint8_t* rows, long long row_stride,
                                    const int* alnlens, uint8_t gap_char, int* tasks_abc, float* seq_distances, float* dm_out)
 {
+        return aln_guide_forest("ka_aln_guide_forest", c, n_fam, fam_first, rows, row_stride, alnlens, gap_char, tasks_abc, seq_distances, dm_out);
+}
+
+static int aln_guide_forest(const char* who, ka_ctx* c, int n_fam, const int* fam_first, const uint8_t* rows, long long row_stride,
+                            const int* alnlens, uint8_t gap_char, int* tasks_abc, float* seq_distances, float* dm_out)
+{
+        const std::string me(who);
         if (!c) return fail("null ctx");
         if (!tasks_abc) return fail("null argument");
-        if (check_fam_first("ka_aln_guide_forest", n_fam, fam_first)) return KA_FAIL;
+        if (check_fam_first(who, n_fam, fam_first)) return KA_FAIL;
         HIPCHK(hipSetDevice(c->device));
         const int numseq = fam_first[n_fam];
         std::vector<int> width(n_fam);
         if (rows) {
-                if (!alnlens || row_stride < 1) return fail("ka_aln_guide_forest: bad arguments");
+                if (!alnlens || row_stride < 1) return fail(me + ": bad arguments");
                 for (int f = 0; f < n_fam; f++) {
-                        if (alnlens[f] < 1 || alnlens[f] > row_stride) return fail("ka_aln_guide_forest: a family's alignment length does not fit row_stride");
+                        if (alnlens[f] < 1 || alnlens[f] > row_stride) return fail(me + ": a family's alignment length does not fit row_stride");
                         width[f] = alnlens[f];
                 }
                 const size_t bytes = (size_t)numseq * (size_t)row_stride;
                 if (c->d_rows.alloc(bytes)) return fail("hipMalloc failed");
                 HIPCHK(hipMemcpyAsync(c->d_rows.p, rows, bytes, hipMemcpyHostToDevice, c->stream));
-                c->rows_n = 0; c->rows_forest_n = 0;                  // no longer the rows of the last run
+                c->rows.forget();                                     // no longer the rows of the last run
         } else {
-                if (c->rows_forest_n < 1) return fail("ka_aln_guide_forest: no rows on the device (call ka_tree_aligned_rows on a finished run first)");
-                if (numseq != c->rows_forest_n) return fail("ka_aln_guide_forest: numseq does not match the rows on the device");
+                if (c->rows.n < 1) return fail(me + ": no rows on the device (call ka_tree_aligned_rows on a finished run first)");
+                if (numseq != c->rows.n) return fail(me + ": numseq does not match the rows on the device");
                 for (int f = 0; f < n_fam; f++) {
-                        width[f] = c->rows_alen[fam_first[f]];
+                        width[f] = c->rows.alen[fam_first[f]];
                         for (int i = fam_first[f]; i < fam_first[f + 1]; i++)
-                                if (c->rows_alen[i] != width[f]) return fail("ka_aln_guide_forest: fam_first does not match the alignments of the rows on the device");
+                                if (c->rows.alen[i] != width[f]) return fail(me + ": fam_first does not match the alignments of the rows on the device");
                 }
-                row_stride = c->rows_stride; gap_char = c->rows_gap;
+                row_stride = c->rows.stride; gap_char = c->rows.gap;
         }
         // ---- the tables: tiles of the distance launch, the families' matrices, the UPGMA records by size class ----
         std::vector<long long> dm_off(n_fam + 1, 0);
@@ -899,7 +942,7 @@ extern "C" int ka_aln_guide_forest(ka_ctx* c, int n_fam, const int* fam_first, c
         std::vector<int> fam_of(numseq);
         for (int f = 0; f < n_fam; f++) {
                 const int first = fam_first[f], n = fam_first[f + 1] - first;
-                if (n > 46340) return fail("ka_aln_guide_forest: more than 46340 sequences in a family (pair indices are 32-bit)");
+                if (n > 46340) return fail(me + ": more than 46340 sequences in a family (pair indices are 32-bit)");
                 dm_off[f + 1] = dm_off[f] + (long long)n * n;
                 fams[f] = KaAdFam{ first, n, dm_off[f] };
                 for (int i = first; i < first + n; i++) fam_of[i] = f;
@@ -907,14 +950,14 @@ extern "C" int ka_aln_guide_forest(ka_ctx* c, int n_fam, const int* fam_first, c
                 for (int ti = 0; ti < t; ti++)
                         for (int tj = ti; tj < t; tj++) tiles.push_back(KaAdTile{ first, n, width[f], ti, tj, 0, dm_off[f] });
         }
-        if (tiles.size() > (size_t)INT32_MAX) return fail("ka_aln_guide_forest: more than 2^31 distance tiles in one batch");
+        if (tiles.size() > (size_t)INT32_MAX) return fail(me + ": more than 2^31 distance tiles in one batch");
         const size_t nn = (size_t)dm_off[n_fam];
         if (c->d_adm.alloc(nn) || c->d_amean.alloc(numseq) || c->d_uactive.alloc(numseq) || c->d_ucand.alloc(2 * (size_t)numseq) ||
             c->d_umerges.alloc(numseq) || c->d_adtiles.alloc(tiles.size()) || c->d_adfams.alloc(n_fam) || c->d_fam_of.alloc(numseq) ||
             c->d_utable.alloc(n_fam))
                 return fail("hipMalloc failed");
         // families by size class (one workgroup each); the others -- above the one-workgroup limit, or all of them when the
-        // per-merge launches are asked for -- go through ka_launch_upgma one by one
+        // per-merge launches are asked for (KA_UPGMA_LAUNCHES) -- go through ka_launch_upgma one by one
         std::vector<int> by_class[KA_UPGMA_CLASSES], alone;
         for (int f = 0; f < n_fam; f++) {
                 const int n = fams[f].n;
@@ -937,22 +980,21 @@ extern "C" int ka_aln_guide_forest(ka_ctx* c, int n_fam, const int* fam_first, c
         HIPCHK(hipMemcpyAsync(c->d_adfams.p, fams.data(), sizeof(KaAdFam) * n_fam, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_fam_of.p, fam_of.data(), sizeof(int) * numseq, hipMemcpyHostToDevice, c->stream));
         if (!table.empty()) HIPCHK(hipMemcpyAsync(c->d_utable.p, table.data(), sizeof(KaUpgma) * table.size(), hipMemcpyHostToDevice, c->stream));
-        ka_launch_aln_dist_forest(c->d_rows.p, row_stride, c->d_adtiles.p, (int)tiles.size(), c->d_adfams.p, c->d_fam_of.p, numseq, gap_char,
-                                  c->d_adm.p, c->d_amean.p, c->stream);
+        ka_launch_aln_dist(c->d_rows.p, row_stride, c->d_adtiles.p, (int)tiles.size(), c->d_adfams.p, c->d_fam_of.p, numseq, gap_char,
+                           c->d_adm.p, c->d_amean.p, c->stream);
         HIPCHK(hipGetLastError());
         if (dm_out) HIPCHK(hipMemcpyAsync(dm_out, c->d_adm.p, sizeof(float) * nn, hipMemcpyDeviceToHost, c->stream));
         if (seq_distances) HIPCHK(hipMemcpyAsync(seq_distances, c->d_amean.p, sizeof(float) * numseq, hipMemcpyDeviceToHost, c->stream));
         std::vector<int> ones(numseq, 1);
         HIPCHK(hipMemcpyAsync(c->d_uactive.p, ones.data(), sizeof(int) * numseq, hipMemcpyHostToDevice, c->stream));
         if (!table.empty()) {
-                const int failed = ka_launch_upgma_forest(c->d_utable.p, cls_first, cls_max, c->stream);
+                const int failed = ka_launch_upgma_one_wg(c->d_utable.p, cls_first, cls_max, c->stream);
                 HIPCHK(hipGetLastError());
                 for (int k = 0; k < KA_UPGMA_CLASSES; k++)
                         if (failed & (1 << k)) alone.insert(alone.end(), by_class[k].begin(), by_class[k].end());
         }
         for (int f : alone) {
-                const KaUpgma U = record(f);
-                ka_launch_upgma(U.dm, U.active, U.key[0], U.merges, U.n, c->env.upgma_launches ? 1 : 0, c->stream);
+                ka_launch_upgma(record(f), c->stream);
                 HIPCHK(hipGetLastError());
         }
         std::vector<int> merges(2 * (size_t)numseq);
@@ -976,22 +1018,6 @@ extern "C" int ka_aln_guide_forest(ka_ctx* c, int n_fam, const int* fam_first, c
         return KA_OK;
 }
 
-// the finished rows of the uploaded job, every row at row_off[i] of one packed buffer, straight into host memory
-static int rows_build_packed(ka_ctx* c, const uint8_t* letters, uint8_t gap_char, const std::vector<int>& alen,
-                             const std::vector<long long>& row_off, size_t bytes, uint8_t* out)
-{
-        if (c->d_letters.alloc(c->h_codes.size()) || c->d_alnlen.alloc(c->numseq) || c->d_row_off.alloc(c->numseq) || c->d_batch_rows.alloc(bytes))
-                return fail("hipMalloc failed");
-        HIPCHK(hipMemcpyAsync(c->d_letters.p, letters, c->h_codes.size(), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->d_alnlen.p, alen.data(), sizeof(int) * c->numseq, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->d_row_off.p, row_off.data(), sizeof(long long) * c->numseq, hipMemcpyHostToDevice, c->stream));
-        ka_launch_rows_packed(c->d_letters.p, c->d_seq_off.p, c->d_node_len.p, c->d_colof.p, c->d_alnlen.p, c->numseq, gap_char,
-                              c->d_batch_rows.p, c->d_row_off.p, c->stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return copy_to_host(c, out, c->d_batch_rows.p, bytes);
-}
-
 extern "C" int ka_run_encoded_batch(ka_ctx* c, int n_fam, const int* fam_first, const uint8_t* tree_codes, const uint8_t* codes,
                                     const uint8_t* letters, const int* off, const int* lens, const float* subm, const float* scal,
                                     int n_anchors, float weight, int realign_iterations, const float* dm_scale, int n_threads,
@@ -1000,29 +1026,18 @@ extern "C" int ka_run_encoded_batch(ka_ctx* c, int n_fam, const int* fam_first, 
         if (!c) return fail("null ctx");
         if (check_fam_first("ka_run_encoded_batch", n_fam, fam_first)) return KA_FAIL;
         if (!tree_codes || !codes || !letters || !off || !lens || !subm || !scal) return fail("ka_run_encoded_batch: bad arguments");
-        const int base = refine_mode & 255;
-        if (refine_mode < 0 || base > 3 || (refine_mode & ~(255 | KA_REFINE_ADAPTIVE)) || ((refine_mode & KA_REFINE_ADAPTIVE) && base != 1 && base != 2))
-                return fail("ka_run_encoded_batch: refine_mode must be 0, 1 (optionally | KA_REFINE_ADAPTIVE) or 3");
+        if (!refine_mode_ok(refine_mode)) return fail("ka_run_encoded_batch: refine_mode must be 0, 1 (optionally | KA_REFINE_ADAPTIVE) or 3");
         // KALIGN_REFINE_CONFIDENT refines the edges at or below the MEDIAN confidence of an alignment's edges; ka_tree_refine takes that
         // median over all tasks of a job, which in a forest job would mix the families
-        if (base == 2) return fail("ka_run_encoded_batch: refine_mode 2 (confident) is not available for a batch: its median would span the families");
+        if ((refine_mode & 255) == 2) return fail("ka_run_encoded_batch: refine_mode 2 (confident) is not available for a batch: its median would span the families");
         if (n_anchors > KA_CONS_MAX_ANCHORS) return fail("this build takes at most 128 consistency anchors (KA_CONS_MAX_ANCHORS)");
         HIPCHK(hipSetDevice(c->device));
         const auto t_start = std::chrono::steady_clock::now();
         double stats[6] = { 0, 0, 0, 0, 0, 0 };
-        hipEvent_t ev[2] = { nullptr, nullptr };
-        struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 2; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } guard{ ev };
-        HIPCHK(hipEventCreate(&ev[0]));
-        HIPCHK(hipEventCreate(&ev[1]));
+        StageClock clk{ stats };
+        HIPCHK(hipEventCreate(&clk.ev[0]));
+        HIPCHK(hipEventCreate(&clk.ev[1]));
         const int numseq = fam_first[n_fam];
-        const bool inline_refine = base == 3;
-        auto align = [&]() -> int {
-                if (inline_refine ? ka_tree_refine(c, 3, nullptr) : ka_tree_run(c)) return KA_FAIL;
-                if (ka_tree_sync(c)) return KA_FAIL;
-                float ms = 0.0f;
-                if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) stats[1] += ms; else (void)hipGetLastError();
-                return KA_OK;
-        };
         // ---- the guide trees of all families: two distance batches ----
         std::vector<int> tasks(3 * (size_t)std::max(numseq - 1, 1)), t_first(n_fam + 1, 0);
         std::vector<float> sd(numseq);
@@ -1077,35 +1092,12 @@ extern "C" int ka_run_encoded_batch(ka_ctx* c, int n_fam, const int* fam_first, 
                                                 v < numseq ? g_fam_first[x] + (v - fam_first[f]) : gn + g_t_first[x] + (v - numseq - t_first[f]);
                                 }
                 }
-                if (ka_tree_upload(c, gn, g_codes.data(), g_off.data(), g_lens.data(), g_sd.data(), gt, g_tasks.data(), subm, scal, KA_FLAG_DEVICE_GAPS)) return KA_FAIL;
-                if (K > 0 && ka_tree_build_consistency(c, K, weight)) return KA_FAIL;
-                if (align()) return KA_FAIL;
+                const AlignJob J{ gn, (int)G.size(), g_fam_first.data(), g_codes.data(), g_letters.data(), g_off.data(), g_lens.data(), gt, g_tasks.data(),
+                                  g_sd.data(), subm, scal, K, weight, realign_iterations, refine_mode, gap_char };
                 std::vector<int> alen;
                 int widest = 0;
-                for (int it = 0; it < realign_iterations; it++) {
-                        if (rows_prepare(c, g_letters.data(), alen, &widest)) return KA_FAIL;
-                        HIPCHK(hipEventRecord(ev[0], c->stream));
-                        if (rows_build(c, g_letters.data(), gap_char, alen, widest, (long long)widest + 1)) return KA_FAIL;
-                        HIPCHK(hipEventRecord(ev[1], c->stream));
-                        HIPCHK(hipEventSynchronize(ev[1]));
-                        float ms = 0.0f;
-                        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-                        stats[3] += ms;
-                        if (ka_aln_guide_forest(c, (int)G.size(), g_fam_first.data(), nullptr, 0, nullptr, 0, g_tasks.data(), g_sd.data(), nullptr)) return KA_FAIL;
-                        HIPCHK(hipEventRecord(ev[0], c->stream));
-                        HIPCHK(hipEventSynchronize(ev[0]));
-                        HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[0]));
-                        stats[2] += ms;
-                        if (ka_tree_upload(c, gn, g_codes.data(), g_off.data(), g_lens.data(), g_sd.data(), gt, g_tasks.data(), subm, scal,
-                                           KA_FLAG_DEVICE_GAPS | KA_FLAG_KEEP_CONSISTENCY)) return KA_FAIL;
-                        if (align()) return KA_FAIL;
-                }
-                if (base == 1) {
-                        if (ka_tree_refine(c, refine_mode, nullptr) || ka_tree_sync(c)) return KA_FAIL;
-                        float ms = 0.0f;
-                        if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) stats[1] += ms; else (void)hipGetLastError();
-                }
-                if (rows_prepare(c, g_letters.data(), alen, &widest)) return KA_FAIL;
+                if (align_job(c, J, alen, &widest, &clk)) return KA_FAIL;
+                // the job's rows, packed, straight into host memory
                 std::vector<long long> row_off(gn);
                 long long bytes = 0;
                 for (size_t x = 0; x < G.size(); x++) {
@@ -1113,13 +1105,10 @@ extern "C" int ka_run_encoded_batch(ka_ctx* c, int n_fam, const int* fam_first, 
                         for (int i = g_fam_first[x]; i < g_fam_first[x + 1]; i++) { row_off[i] = bytes; bytes += (long long)alen[i] + 1; }
                 }
                 group_rows[g].resize((size_t)bytes);
-                HIPCHK(hipEventRecord(ev[0], c->stream));
-                if (rows_build_packed(c, g_letters.data(), gap_char, alen, row_off, (size_t)bytes, group_rows[g].data())) return KA_FAIL;
-                HIPCHK(hipEventRecord(ev[1], c->stream));
-                HIPCHK(hipEventSynchronize(ev[1]));
-                float ms = 0.0f;
-                HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-                stats[3] += ms;
+                if (clk.mark(0, c->stream)) return KA_FAIL;
+                if (rows_build(c, J.letters, gap_char, alen, 0, &row_off)) return KA_FAIL;   // (packed: no stride; `bytes` in all)
+                if (copy_to_host(c, group_rows[g].data(), c->d_rows.p, (size_t)bytes)) return KA_FAIL;
+                if (clk.lap(1, 3, c->stream)) return KA_FAIL;
         }
         // ---- all families in their order, packed ----
         std::vector<long long> fam_off(n_fam + 1, 0);

@@ -56,18 +56,15 @@ static inline void ka_launch_task_level(const KaTreeDev* D, const int2* blocks_d
 extern "C" int ka_max_g_host(void);
 extern "C" void ka_launch_posmaps(const int* paths, const long long* poff, const int* pair_of, const int* lens, const long long* map_off,
                                   int numseq, int K, int* maps, hipStream_t stream);
-extern "C" void ka_launch_aln_dist(const uint8_t* rows, long long stride, int alnlen, int n, uint8_t gap, float* dm, float* means,
-                                   hipStream_t stream);
-extern "C" void ka_launch_upgma(float* dm, int* active, unsigned long long* keys, int2* merges, int n, int mode, hipStream_t stream);
+// the realignment tree of a batch of families and the rows of a job (ka_rows.hip; the tables: ka_forest.h)
+extern "C" void ka_launch_aln_dist(const uint8_t* rows, long long stride, const KaAdTile* tiles, int n_tiles, const KaAdFam* fams,
+                                   const int* fam_of, int numseq, uint8_t gap, float* dm, float* means, hipStream_t stream);
+extern "C" int ka_launch_upgma_one_wg(const KaUpgma* table, const int* first, const int* max_n, hipStream_t stream);
+extern "C" void ka_launch_upgma(KaUpgma U, hipStream_t stream);                  // one launch per merge
+extern "C" void ka_launch_rows(const uint8_t* letters, const int* off, const int* lens, const int* colof, const int* alnlen,
+                               int numseq, uint8_t gap, uint8_t* rows, long long stride, const long long* row_off, hipStream_t stream);
 int ka_tasks_from_merges(int numseq, const int* merges_ab, int* tasks_abc);      // ka_guide.cpp
 double ka_guide_last_dist_ms(void);                                              // ka_guide.cpp: device ms of the distance batches of the last ka_guide_forest
-extern "C" void ka_launch_aln_dist_forest(const uint8_t* rows, long long stride, const KaAdTile* tiles, int n_tiles, const KaAdFam* fams,
-                                          const int* fam_of, int numseq, uint8_t gap, float* dm, float* means, hipStream_t stream);
-extern "C" int ka_launch_upgma_forest(const KaUpgma* table, const int* first, const int* max_n, hipStream_t stream);
-extern "C" void ka_launch_rows_packed(const uint8_t* letters, const int* off, const int* lens, const int* colof, const int* alnlen,
-                                      int numseq, uint8_t gap, uint8_t* rows, const long long* row_off, hipStream_t stream);
-extern "C" void ka_launch_rows(const uint8_t* letters, const int* off, const int* lens, const int* colof, const int* alnlen,
-                               int numseq, uint8_t gap, uint8_t* rows, long long stride, hipStream_t stream);
 extern "C" void ka_launch_bpm(const uint8_t* codes, const int* off, const int* lens, int numseq, unsigned long long* peq,
                               const int* ia, const int* ib, int npairs, int* dist, hipStream_t stream);
 extern "C" long long ka_ctl_bytes_host(void);
@@ -96,6 +93,18 @@ struct DevBuf {
                 return 0;
         }
         void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+};
+
+// The aligned rows that the last rows_build left in d_rows: n rows (0: nothing that a tree can be built from) `stride`
+// apart, row i the first alen[i] columns of its tree's alignment, the rest gap.  one_tree: all of one alignment -- what
+// ka_aln_guide_tree takes; ka_aln_guide_forest takes any.
+struct KaRowsHeld {
+        int n = 0;
+        long long stride = 0;
+        uint8_t gap = 0;
+        bool one_tree = false;
+        std::vector<int> alen;
+        void forget() { n = 0; one_tree = false; }   // a new job, other rows in d_rows
 };
 
 // (the switches, the prepared job and its launch plan are the KaPlan base: ka_plan.h)
@@ -170,13 +179,11 @@ struct ka_ctx : KaPlan {
         std::vector<long long> cons_map_off;
         DevBuf<int> d_cons_maps, d_colof, d_colof_init, d_sip, d_alnlen, d_pair_of;
         DevBuf<uint8_t> d_letters, d_rows;
-        long long rows_stride = 0; int rows_n = 0, rows_alnlen = 0; uint8_t rows_gap = 0;   // what d_rows holds (0 rows: nothing)
+        KaRowsHeld rows;                             // what d_rows holds
+        // ---- the realignment trees of a batch of families (ka_aln_guide_forest; one family: a batch of one) ----
         DevBuf<float> d_adm, d_amean; DevBuf<int> d_uactive; DevBuf<unsigned long long> d_ucand; DevBuf<int2> d_umerges;
-        // ---- a batch of families (ka_aln_guide_forest, ka_run_encoded_batch) ----
-        int rows_forest_n = 0;                       // d_rows holds the rows of this many sequences of a forest job (a single tree included) ...
-        std::vector<int> rows_alen;                  // ... every sequence's own alignment length (d_alnlen on the host)
         DevBuf<KaAdTile> d_adtiles; DevBuf<KaAdFam> d_adfams; DevBuf<int> d_fam_of; DevBuf<KaUpgma> d_utable;
-        DevBuf<long long> d_row_off; DevBuf<uint8_t> d_batch_rows;
+        DevBuf<long long> d_row_off;                 // ka_run_encoded_batch: where every row of a packed hand-out starts
         std::vector<uint8_t> batch_rows;             // the finished rows of the last ka_run_encoded_batch, packed (ka_batch_rows)
         bool have_batch = false;
         double batch_stats[6] = {0, 0, 0, 0, 0, 0};  // ka_batch_stats

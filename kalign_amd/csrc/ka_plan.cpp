@@ -650,7 +650,7 @@ extern "C" int ka_tree_upload(ka_ctx* c, int numseq, const uint8_t* codes, const
         }
         if (!keep_cons) c->cons_K = 0;           // a new job starts without a consistency table
         c->have_colof = false;
-        c->rows_n = 0; c->rows_forest_n = 0;
+        c->rows.forget();
         c->flags = flags;
         c->off.assign(off, off + numseq);
         memcpy(c->subm, subm, sizeof(c->subm));

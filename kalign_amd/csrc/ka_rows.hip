@@ -29,33 +29,18 @@ __device__ __forceinline__ void ka_row_write(const uint8_t* __restrict__ s, cons
 __global__ void __launch_bounds__(256) ka_rows_kernel(const uint8_t* __restrict__ letters, const int* __restrict__ off,
                                                       const int* __restrict__ lens, const int* __restrict__ colof,
                                                       const int* __restrict__ alnlen, uint8_t gap,
-                                                      uint8_t* __restrict__ rows, long long stride)
+                                                      uint8_t* __restrict__ rows, long long stride, const long long* __restrict__ row_off)
 {
+        // row i at row_off[i], or -- no table -- `stride` apart (a batch of families is handed out packed: the rows of a
+        // family its own alignment length + 1 apart, family after family)
         const int i = blockIdx.x;
-        ka_row_write(letters + off[i], colof + off[i], lens[i], alnlen[i], gap, rows + (long long)i * stride);
-}
-
-// The same with every row at a place of its own (a batch of families, packed: the rows of a family are its own
-// alignment length + 1 apart, family after family)
-__global__ void __launch_bounds__(256) ka_rows_packed_kernel(const uint8_t* __restrict__ letters, const int* __restrict__ off,
-                                                             const int* __restrict__ lens, const int* __restrict__ colof,
-                                                             const int* __restrict__ alnlen, uint8_t gap,
-                                                             uint8_t* __restrict__ rows, const long long* __restrict__ row_off)
-{
-        const int i = blockIdx.x;
-        ka_row_write(letters + off[i], colof + off[i], lens[i], alnlen[i], gap, rows + row_off[i]);
+        ka_row_write(letters + off[i], colof + off[i], lens[i], alnlen[i], gap, rows + (row_off ? row_off[i] : (long long)i * stride));
 }
 
 extern "C" void ka_launch_rows(const uint8_t* letters, const int* off, const int* lens, const int* colof, const int* alnlen,
-                               int numseq, uint8_t gap, uint8_t* rows, long long stride, hipStream_t stream)
+                               int numseq, uint8_t gap, uint8_t* rows, long long stride, const long long* row_off, hipStream_t stream)
 {
-        hipLaunchKernelGGL(ka_rows_kernel, dim3(numseq), dim3(256), 0, stream, letters, off, lens, colof, alnlen, gap, rows, stride);
-}
-
-extern "C" void ka_launch_rows_packed(const uint8_t* letters, const int* off, const int* lens, const int* colof, const int* alnlen,
-                                      int numseq, uint8_t gap, uint8_t* rows, const long long* row_off, hipStream_t stream)
-{
-        hipLaunchKernelGGL(ka_rows_packed_kernel, dim3(numseq), dim3(256), 0, stream, letters, off, lens, colof, alnlen, gap, rows, row_off);
+        hipLaunchKernelGGL(ka_rows_kernel, dim3(numseq), dim3(256), 0, stream, letters, off, lens, colof, alnlen, gap, rows, stride, row_off);
 }
 
 // Position maps of anchor consistency (reference lib/src/anchor_consistency.c:86-114): the coded path of the
@@ -161,45 +146,29 @@ __device__ __forceinline__ void ka_aln_dist_tile(const uint8_t* __restrict__ row
         if (i < n && j < n && i == j) dm[(long long)i * n + i] = 0.0f;
 }
 
-__global__ void __launch_bounds__(256) ka_aln_dist_kernel(const uint8_t* __restrict__ rows, long long stride, int alnlen, int n,
-                                                          uint8_t gap, float* __restrict__ dm)
-{
-        if (blockIdx.x < blockIdx.y) return;                         // tile (y = i tile, x = j tile), j tile >= i tile
-        ka_aln_dist_tile(rows, stride, alnlen, n, gap, dm, blockIdx.y, blockIdx.x);
-}
-
-// A batch of families: the rows of all families lie `stride` apart, a family's own alignment is its first alnlen columns
-// (bytes past it read as gaps), its matrix starts at dm + dm_off.  One workgroup per entry of the tile table, which
-// lists the upper-triangle tiles of every family -- the same tile, the same integer counts, the same division.
-__global__ void __launch_bounds__(256) ka_aln_dist_forest_kernel(const uint8_t* __restrict__ rows, long long stride,
-                                                                 const KaAdTile* __restrict__ tiles, uint8_t gap, float* __restrict__ dm)
+// A batch of families (one family: a batch of one): the rows of all families lie `stride` apart, a family's own alignment is
+// its first alnlen columns (bytes past it read as gaps), its matrix starts at dm + dm_off.  One workgroup per entry of the
+// tile table, which lists the upper-triangle tiles of every family.
+__global__ void __launch_bounds__(256) ka_aln_dist_kernel(const uint8_t* __restrict__ rows, long long stride,
+                                                          const KaAdTile* __restrict__ tiles, uint8_t gap, float* __restrict__ dm)
 {
         const KaAdTile T = tiles[blockIdx.x];
         ka_aln_dist_tile(rows + (long long)T.row0 * stride, stride, T.alnlen, T.n, gap, dm + T.dm_off, T.ti, T.tj);
 }
 
 // build_tree_from_pairwise (lib/src/bisectingKmeans.c:1150-1200): mean distance of every sequence to the others,
-// summed in column order like the reference, before UPGMA overwrites the matrix
-__global__ void ka_row_mean_kernel(const float* __restrict__ dm, int n, float* __restrict__ out)
-{
-        const int i = blockIdx.x * blockDim.x + threadIdx.x;
-        if (i >= n) return;
-        // the matrix is symmetric: walk column i (coalesced across the threads of a wave) instead of row i -- the same
-        // values in the same order
-        float sum = 0.0f;
-        for (int j = 0; j < n; ++j)
-                if (j != i) sum += dm[(long long)j * n + i];
-        out[i] = (n > 1) ? sum / (float)(n - 1) : 0.0f;
-}
-// ... of a batch of families: thread g owns sequence g of the batch, row g - first of its family's matrix
-__global__ void ka_row_mean_forest_kernel(const float* __restrict__ dm, const KaAdFam* __restrict__ fams, const int* __restrict__ fam_of,
-                                          int numseq, float* __restrict__ out)
+// summed in column order like the reference, before UPGMA overwrites the matrix.  Thread g owns sequence g of the batch,
+// row g - first of its family's matrix
+__global__ void ka_row_mean_kernel(const float* __restrict__ dm, const KaAdFam* __restrict__ fams, const int* __restrict__ fam_of,
+                                   int numseq, float* __restrict__ out)
 {
         const int g = blockIdx.x * blockDim.x + threadIdx.x;
         if (g >= numseq) return;
         const KaAdFam F = fams[fam_of[g]];
         const int i = g - F.first, n = F.n;
         const float* m = dm + F.dm_off;
+        // the matrix is symmetric: walk column i (coalesced across the threads of a wave) instead of row i -- the same
+        // values in the same order
         float sum = 0.0f;
         for (int j = 0; j < n; ++j)
                 if (j != i) sum += m[(long long)j * n + i];
@@ -314,19 +283,11 @@ __global__ void __launch_bounds__(256) ka_upgma_step_kernel(KaUpgma U, int step)
         ka_upgma_step(U, step, red);
 }
 
-extern "C" void ka_launch_aln_dist(const uint8_t* rows, long long stride, int alnlen, int n, uint8_t gap, float* dm, float* means,
-                                   hipStream_t stream)
+extern "C" void ka_launch_aln_dist(const uint8_t* rows, long long stride, const KaAdTile* tiles, int n_tiles, const KaAdFam* fams,
+                                   const int* fam_of, int numseq, uint8_t gap, float* dm, float* means, hipStream_t stream)
 {
-        const int t = (n + KA_AD_TILE - 1) / KA_AD_TILE;
-        hipLaunchKernelGGL(ka_aln_dist_kernel, dim3(t, t), dim3(256), 0, stream, rows, stride, alnlen, n, gap, dm);
-        hipLaunchKernelGGL(ka_row_mean_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, dm, n, means);
-}
-
-extern "C" void ka_launch_aln_dist_forest(const uint8_t* rows, long long stride, const KaAdTile* tiles, int n_tiles, const KaAdFam* fams,
-                                          const int* fam_of, int numseq, uint8_t gap, float* dm, float* means, hipStream_t stream)
-{
-        hipLaunchKernelGGL(ka_aln_dist_forest_kernel, dim3(n_tiles), dim3(256), 0, stream, rows, stride, tiles, gap, dm);
-        hipLaunchKernelGGL(ka_row_mean_forest_kernel, dim3((numseq + 255) / 256), dim3(256), 0, stream, dm, fams, fam_of, numseq, means);
+        hipLaunchKernelGGL(ka_aln_dist_kernel, dim3(n_tiles), dim3(256), 0, stream, rows, stride, tiles, gap, dm);
+        hipLaunchKernelGGL(ka_row_mean_kernel, dim3((numseq + 255) / 256), dim3(256), 0, stream, dm, fams, fam_of, numseq, means);
 }
 
 // ---- all n - 1 merges in ONE launch of ONE workgroup ----
@@ -501,16 +462,10 @@ __device__ __forceinline__ void ka_upgma_one_wg(const KaUpgma& U)
         }
 }
 
+// One workgroup per family, its record from a table.  A family's matrix, flags and merges are its own slices; the LDS
+// layout follows the family's own n (the launch reserves room for the largest family of the table).
 template <int PER, int SV>
-__global__ void __launch_bounds__(KA_UPGMA_NT) ka_upgma_one_wg_kernel(KaUpgma U)
-{
-        ka_upgma_one_wg<PER, SV>(U);
-}
-
-// A batch of families: one workgroup per family, its record from a table.  A family's matrix, flags and merges are its
-// own slices; the LDS layout follows the family's own n (the launch reserves room for the largest family of the table).
-template <int PER, int SV>
-__global__ void __launch_bounds__(KA_UPGMA_NT) ka_upgma_forest_kernel(const KaUpgma* __restrict__ table)
+__global__ void __launch_bounds__(KA_UPGMA_NT) ka_upgma_one_wg_kernel(const KaUpgma* __restrict__ table)
 {
         const KaUpgma U = table[blockIdx.x];
         ka_upgma_one_wg<PER, SV>(U);
@@ -519,8 +474,8 @@ __global__ void __launch_bounds__(KA_UPGMA_NT) ka_upgma_forest_kernel(const KaUp
 // table[first[k] .. first[k + 1]): the families of size class k (n <= 512, 1024, 2048, 4096, KA_UPGMA_ONE_WG_MAX: the PER of the
 // one-workgroup kernel), max_n[k] the largest of them.  One launch per class that has families: a large family then occupies
 // its workgroup for its own merges and nobody else's.  Returns a bit per class that could not be launched (more LDS than this
-// GPU grants): the caller runs those families through ka_launch_upgma.
-extern "C" int ka_launch_upgma_forest(const KaUpgma* table, const int* first, const int* max_n, hipStream_t stream)
+// GPU grants -- another GPU, a smaller limit): the caller runs those families through ka_launch_upgma.
+extern "C" int ka_launch_upgma_one_wg(const KaUpgma* table, const int* first, const int* max_n, hipStream_t stream)
 {
         int failed = 0;
         auto go = [&](auto kernel, const int k) {
@@ -534,11 +489,11 @@ extern "C" int ka_launch_upgma_forest(const KaUpgma* table, const int* first, co
                 }
                 hipLaunchKernelGGL(kernel, dim3(count), dim3(KA_UPGMA_NT), lds, stream, table + first[k]);
         };
-        go(ka_upgma_forest_kernel<1, 8>, 0);
-        go(ka_upgma_forest_kernel<2, 16>, 1);
-        go(ka_upgma_forest_kernel<4, 32>, 2);
-        go(ka_upgma_forest_kernel<8, 32>, 3);
-        go(ka_upgma_forest_kernel<KA_UPGMA_ONE_WG_MAX / KA_UPGMA_NT, 32>, 4);
+        go(ka_upgma_one_wg_kernel<1, 8>, 0);
+        go(ka_upgma_one_wg_kernel<2, 16>, 1);
+        go(ka_upgma_one_wg_kernel<4, 32>, 2);
+        go(ka_upgma_one_wg_kernel<8, 32>, 3);
+        go(ka_upgma_one_wg_kernel<KA_UPGMA_ONE_WG_MAX / KA_UPGMA_NT, 32>, 4);
         return failed;
 }
 
@@ -547,29 +502,10 @@ extern "C" int ka_launch_upgma_forest(const KaUpgma* table, const int* first, co
 // faster: the loop replayed as one hipGraph of n kernel nodes (12 us per node: the cost is the dependent dispatch on the
 // GPU, not the host-side launch), and one persistent kernel of 64 workgroups with a barrier in HBM between steps (21 us
 // per step).  keys: 2 * n words, active: n ones, merges: n - 1 pairs.
-// mode 0: one workgroup for all merges when n <= KA_UPGMA_ONE_WG_MAX; 1: always one launch per merge (KA_UPGMA_LAUNCHES=1)
-extern "C" void ka_launch_upgma(float* dm, int* active, unsigned long long* keys, int2* merges, int n, int mode, hipStream_t stream)
+// (the path of a family above KA_UPGMA_ONE_WG_MAX rows, and of any family with KA_UPGMA_LAUNCHES=1)
+extern "C" void ka_launch_upgma(KaUpgma U, hipStream_t stream)
 {
-        KaUpgma U{ dm, active, { keys, keys + n }, merges, n };
-        if (mode == 0 && n <= KA_UPGMA_ONE_WG_MAX) {
-                const int lds = n * 17 + 16;                          // keys, list, listv, act
-                // (the opt-in to more than 64 KB of LDS can fail -- another GPU, a smaller limit: then the per-merge launches below)
-                auto go = [&](auto kernel) -> bool {
-                        if (lds > 65536 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, KA_UPGMA_ONE_WG_MAX * 17 + 16) != hipSuccess) {
-                                (void)hipGetLastError();
-                                return false;
-                        }
-                        hipLaunchKernelGGL(kernel, dim3(1), dim3(KA_UPGMA_NT), lds, stream, U);
-                        return true;
-                };
-                bool ok;
-                if (n <= KA_UPGMA_NT) ok = go(ka_upgma_one_wg_kernel<1, 8>);
-                else if (n <= 2 * KA_UPGMA_NT) ok = go(ka_upgma_one_wg_kernel<2, 16>);
-                else if (n <= 4 * KA_UPGMA_NT) ok = go(ka_upgma_one_wg_kernel<4, 32>);
-                else if (n <= 8 * KA_UPGMA_NT) ok = go(ka_upgma_one_wg_kernel<8, 32>);
-                else ok = go(ka_upgma_one_wg_kernel<KA_UPGMA_ONE_WG_MAX / KA_UPGMA_NT, 32>);
-                if (ok) return;
-        }
+        const int n = U.n;
         const int blocks = n < 256 ? n : 256;
         hipLaunchKernelGGL(ka_upgma_init_kernel, dim3(blocks), dim3(256), 0, stream, U);
         for (int step = 0; step < n - 1; ++step)

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from util import GOLDEN, Golden
+from util import GOLDEN, Golden, random_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -161,7 +161,21 @@ def test_guide_forest_on_the_device(ctx):
     assert np.array_equal(sd.view(np.uint32), np.concatenate([g.seq_distances for g in gs]).view(np.uint32))
 
 
-def test_aln_guide_forest(ctx):
+def check_forest_against_the_oracle(oracle, rows_of, tasks, sd, dms):
+    """every family of a batch against oracle.aln_guide_tree of its own rows: distances and means as bits, the tasks in
+    the forest's numbering.  A family of one row has no pair and no merge: distance 0 to itself, mean 0, no task."""
+    from kalign_amd import guide
+    lone = (np.zeros((0, 3), np.int32), np.zeros(1, np.float32), np.zeros((1, 1), np.float32))
+    want = [oracle.aln_guide_tree(r) if len(r) > 1 else lone for r in rows_of]
+    _, wtasks, _, _ = guide.forest([(r, w[0]) for r, w in zip(rows_of, want)])
+    assert np.array_equal(tasks, wtasks.reshape(-1, 3))
+    assert np.array_equal(sd.view(np.uint32), np.concatenate([w[1] for w in want]).view(np.uint32))
+    assert len(dms) == len(want)
+    for dm, w in zip(dms, want):
+        assert np.array_equal(dm.view(np.uint32), w[2].view(np.uint32))
+
+
+def test_aln_guide_forest(ctx, oracle):
     from kalign_amd import api, guide
     names = ["realign_dups", "realign_prot150", "realign_prot40"]
     zs, fams = zip(*[realign_family(n) for n in names])
@@ -175,6 +189,7 @@ def test_aln_guide_forest(ctx):
         assert np.array_equal(sd.view(np.uint32), np.concatenate([a[1] for a in alone]).view(np.uint32))
         for dm, a in zip(dms, alone):
             assert np.array_equal(dm.view(np.uint32), a[2].view(np.uint32))
+        check_forest_against_the_oracle(oracle, rows_of, tasks, sd, dms)
         return alone
 
     # rows from the host
@@ -193,6 +208,10 @@ def test_aln_guide_forest(ctx):
         assert [x.decode() for x in r] == [str(x) for x in z["rows_sorted"]]
     got = ctx.aln_guide_forest(None, sizes=sizes, want_dm=True)   # (before anything else touches the rows)
     check(per_family, *got)
+    # distinct widths under one stride, a one-row family, the tile's and the staging step's edges inside a table
+    edges = [random_rows(n, w, seed) for n, w, seed in ((1, 30, 21), (2, 1, 16), (16, 128, 22), (17, 129, 23), (520, 30, 24))]
+    assert all(set(r) != {45} for f in edges for r in f)           # no row is all gaps
+    check_forest_against_the_oracle(oracle, edges, *ctx.aln_guide_forest(edges, want_dm=True))
 
 
 def test_family_above_the_one_workgroup_limit(ctx, scoring):

@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from util import GOLDEN
+from util import GOLDEN, random_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -119,16 +119,15 @@ def test_tiny_and_degenerate_row_sets(ctx):
     assert sorted(tasks[:, 2].tolist()) == list(range(37, 73))
 
 
-@pytest.mark.parametrize("n,alnlen,seed", [(300, 257, 11), (97, 1000, 12), (513, 130, 13)])
+# (16, 128) / (17, 129): a full 16-row tile and one full 128-column staging step against one row / one column over them;
+# (2, 1): the smallest input; (520, 30): the first size with two rows per thread of the one-workgroup UPGMA
+@pytest.mark.parametrize("n,alnlen,seed", [(300, 257, 11), (97, 1000, 12), (513, 130, 13),
+                                           (16, 128, 14), (17, 129, 15), (2, 1, 16), (520, 30, 17)])
 def test_tree_from_random_rows_matches_the_oracle(ctx, oracle, n, alnlen, seed):
-    """seeded rows with many tied distances (few letters, short rows, duplicated rows): the device's distances and
-    UPGMA task list against the oracle's restatement, bit for bit"""
-    rng = np.random.RandomState(seed)
-    base = rng.choice(list(b"ACD-"), size=(n // 3 + 1, alnlen)).astype(np.uint8)
-    rows = base[rng.randint(0, len(base), size=n)].copy()
-    flip = rng.random_sample(rows.shape) < 0.02
-    rows[flip] = rng.choice(list(b"ACD-"), size=int(flip.sum())).astype(np.uint8)
-    rows = [bytes(r) for r in rows]
+    """seeded rows with many tied distances: the device's distances and UPGMA task list against the oracle's
+    restatement, bit for bit"""
+    rows = random_rows(n, alnlen, seed)
+    assert all(set(r) != {45} for r in rows)                      # no row is all gaps
     tasks, sd, dm = ctx.aln_guide_tree(rows, want_dm=True)
     otasks, osd, odm = oracle.aln_guide_tree(rows)
     assert np.array_equal(dm.view(np.uint32), odm.view(np.uint32))

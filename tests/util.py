@@ -89,3 +89,13 @@ def compare_recs(g, recs, paths, exact_fields, tol_fields=("confidence",), rtol=
         if not np.array_equal(got, g.path(t)):
             problems.append((t, "path", None, None))
     return problems
+
+
+def random_rows(n, alnlen, seed):
+    """seeded aligned rows (bytes) with many tied identity distances: few letters, duplicated rows, 2 % of the cells redrawn"""
+    rng = np.random.RandomState(seed)
+    base = rng.choice(list(b"ACD-"), size=(n // 3 + 1, alnlen)).astype(np.uint8)
+    rows = base[rng.randint(0, len(base), size=n)].copy()
+    flip = rng.random_sample(rows.shape) < 0.02
+    rows[flip] = rng.choice(list(b"ACD-"), size=int(flip.sum())).astype(np.uint8)
+    return [bytes(r) for r in rows]
