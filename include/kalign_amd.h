@@ -662,6 +662,40 @@ int  ka_cmp_score_batch(ka_cmp* h, int n_tests, const uint8_t* const* test_rows,
                         long long* counts_out, double* scores_out, float* sp_out);
 int  ka_cmp_stats(ka_cmp* h, double* stats_out);
 
+/* ---- scoring a batch of families, each against its own reference alignment (ka_cmp_fam.hip, ka_cmp_fam.cpp) ------------------
+ * What ka_cmp_create + ka_cmp_set_mask + ka_cmp_score return for every family alone -- twelve counts, five doubles and the
+ * float SP score, bit for bit -- for all families of a batch in a number of launches that does not grow with the batch,
+ * with one copy back and one synchronisation per score call.  The references stay on the device: the loop of a benchmark
+ * (one reference per family, new test alignments per parameter set) creates once and scores many times.
+ *   Families   fam_first[n_fam + 1] and lens[numseq] as ka_run_encoded_batch takes them; two sequences per family at least.
+ *   Rows       packed as ka_batch_rows hands them out: families in order, the rows of family f alnlens[f] + 1 bytes apart
+ *              (the byte after a row is not read), so its output is test_rows as it stands.  alnlens is per family.
+ *   ka_cmp_fam_check      every check of a packed batch, on the host alone (no context, no GPU): fam_first ascends from 0
+ *                         ("fam_first does not ascend from 0 to numseq", "empty family"), and per family what ka_cmp_create /
+ *                         ka_cmp_score check.  A message names the family and ends in the cause the one-family call gives:
+ *                         "ka_cmp_fam_check: family 3: row 1 holds 7 letters, its sequence 8 (...)".
+ *   ka_cmp_fam_create     the reference alignments; runs the check, then builds their position maps once.  Limits per family
+ *                         as ka_cmp_create's; over the batch fewer than 2^31 residues and fewer than 2^31 reference columns.
+ *                         Runs on ctx's device and stream: destroy it before ctx.
+ *   ka_cmp_fam_set_masks  the column rule of every family: with mask_off[f] >= 0 the ref_alnlens[f] ints at masks + mask_off[f]
+ *                         (kalign_msa_compare_with_mask), else max_gap_frac[f] (kalign_msa_compare_detailed; below 0: every
+ *                         column).  max_gap_frac NULL: -1 for every family; masks or mask_off NULL: no masks.  Until it is
+ *                         called, every column is scored.
+ *   ka_cmp_fam_score      one test alignment per family; runs the check on them.  A refused batch launches nothing and leaves
+ *                         the handle usable.  counts_out[n_fam * 12], scores_out[n_fam * 5], sp_out[n_fam] (each optional)
+ *                         as ka_cmp_score lays them out.
+ *   ka_cmp_fam_stats      device ms: stats_out[4] as ka_cmp_stats, each over the whole batch.
+ */
+typedef struct ka_cmp_fam ka_cmp_fam;
+int  ka_cmp_fam_check(int n_fam, const int* fam_first, const int* lens, const uint8_t* rows, const int* alnlens);
+int  ka_cmp_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, const int* lens, const uint8_t* ref_rows, const int* ref_alnlens,
+                       ka_cmp_fam** out);
+void ka_cmp_fam_destroy(ka_cmp_fam* h);
+int  ka_cmp_fam_set_masks(ka_cmp_fam* h, const float* max_gap_frac, const int* masks, const long long* mask_off);
+int  ka_cmp_fam_score(ka_cmp_fam* h, const uint8_t* test_rows, const int* test_alnlens, long long* counts_out, double* scores_out,
+                      float* sp_out);
+int  ka_cmp_fam_stats(ka_cmp_fam* h, double* stats_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,7 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_ens_confidence", "ka_ens_stats", "ka_ens_table_size", "ka_ens_table_write", "ka_ens_table_image", "ka_ens_open_table",
            "ka_ens_open_table_image", "ka_ens_n_runs", "ka_ens_table_stats", "ka_poar_check_image", "ka_ens_merge", "ka_ens_select", "ka_cmp_create", "ka_cmp_destroy", "ka_cmp_set_mask", "ka_cmp_score",
            "ka_cmp_score_batch", "ka_cmp_stats",
+           "ka_cmp_fam_check", "ka_cmp_fam_create", "ka_cmp_fam_destroy", "ka_cmp_fam_set_masks", "ka_cmp_fam_score", "ka_cmp_fam_stats",
            "ka_guide_forest_from", "ka_guide_forest", "ka_aln_guide_forest", "ka_run_encoded_batch", "ka_batch_rows_size", "ka_batch_rows",
            "ka_batch_stats"]
 
@@ -223,6 +224,13 @@ def load_library():
     L.ka_cmp_score.argtypes = [vp, vp, C.c_longlong, C.c_int, vp, vp, vp]
     L.ka_cmp_score_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.ka_cmp_stats.argtypes = [vp, vp]
+    L.ka_cmp_fam_check.argtypes = [C.c_int, vp, vp, vp, vp]
+    L.ka_cmp_fam_create.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(vp)]
+    L.ka_cmp_fam_destroy.argtypes = [vp]
+    L.ka_cmp_fam_destroy.restype = None
+    L.ka_cmp_fam_set_masks.argtypes = [vp, vp, vp, vp]
+    L.ka_cmp_fam_score.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ka_cmp_fam_stats.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -1149,6 +1157,98 @@ def _cmp_create(self, ref_rows):
 
 
 Context.comparer = _cmp_create
+
+
+def pack_families(families):
+    """lists of equal-length rows (bytes / str), one list per family -> (uint8 rows packed as ka_batch_rows packs them: the
+    rows of family f alnlen_f + 1 bytes apart, a 0 byte after each; int32 alnlen per family)"""
+    fams = [[x.encode() if isinstance(x, str) else bytes(x) for x in f] for f in families]
+    widths = np.array([len(f[0]) if f else 0 for f in fams], np.int32)
+    for k, (f, w) in enumerate(zip(fams, widths)):
+        if any(len(r) != w for r in f):
+            raise KalignAmdError("family %d: rows of one alignment have one length" % k)
+    packed = np.frombuffer(b"".join(r + b"\0" for f in fams for r in f), np.uint8)
+    return packed, widths
+
+
+class FamilyComparer(_CtxChild):
+    """The reference alignments of a batch of families on the device (ka_cmp_fam): score() takes one test alignment per
+    family and returns, per family, what Comparer(ref).score(test) returns for it alone -- in a number of launches that
+    does not grow with the batch.  refs / tests: one list of rows per family (what Context.run_families returns), rows
+    paired by position: kalign_amd.compare.compare_families pairs named rows."""
+    _destroy = "ka_cmp_fam_destroy"
+
+    def __init__(self, ctx, refs):
+        self.ctx, self.L = ctx, ctx.L
+        if not ctx.h:
+            raise KalignAmdError("the context is closed")
+        refs = [list(f) for f in refs]
+        if not refs:
+            raise KalignAmdError("a family comparison needs a family")
+        self.sizes = [len(f) for f in refs]
+        self.first = _fam_first(self.sizes)
+        self.lens = residue_lens([r for f in refs for r in f])
+        rows, self.widths = pack_families(refs)
+        h = C.c_void_p()
+        ctx._chk(self.L.ka_cmp_fam_create(ctx.h, len(refs), _ptr(self.first), _ptr(self.lens), _ptr(rows if len(rows) else np.zeros(1, np.uint8)),
+                                          _ptr(self.widths), C.byref(h)))
+        self._adopt(ctx, h)
+
+    def _set_masks(self, max_gap_frac, column_masks):
+        F = len(self.sizes)
+        frac = np.ascontiguousarray(np.broadcast_to(np.asarray(max_gap_frac, np.float32), (F,)))
+        if column_masks is None:
+            self.ctx._chk(self.L.ka_cmp_fam_set_masks(self.h, _ptr(frac), None, None))
+            return
+        if len(column_masks) != F:
+            raise KalignAmdError("%d column masks for %d families" % (len(column_masks), F))
+        off, parts, o = np.full(F, -1, np.int64), [], 0
+        for f, m in enumerate(column_masks):
+            if m is None:
+                continue
+            m = np.ascontiguousarray(m, np.int32).reshape(-1)
+            if len(m) != self.widths[f]:
+                raise KalignAmdError("family %d: mask length %d != reference alignment length %d" % (f, len(m), self.widths[f]))
+            off[f] = o
+            parts.append(m)
+            o += len(m)
+        masks = np.concatenate(parts) if parts else None
+        self.ctx._chk(self.L.ka_cmp_fam_set_masks(self.h, _ptr(frac), _ptr(masks), _ptr(off)))
+
+    def score(self, tests, max_gap_frac=-1.0, column_masks=None):
+        """one test alignment per family.  max_gap_frac: one value or one per family (kalign_msa_compare_detailed; < 0:
+        every column); column_masks: None, or per family None or one int per reference column
+        (kalign_msa_compare_with_mask).  Returns one Comparer.score dict per family."""
+        if not self.h:
+            raise KalignAmdError("the comparer is closed")
+        tests = [list(f) for f in tests]
+        if [len(f) for f in tests] != self.sizes:
+            for f, (t, n) in enumerate(zip(tests, self.sizes)):
+                if len(t) != n:
+                    raise KalignAmdError("family %d: the test alignment has %d rows, the reference %d" % (f, len(t), n))
+            raise KalignAmdError("%d test alignments for %d families" % (len(tests), len(self.sizes)))
+        self._set_masks(max_gap_frac, column_masks)
+        rows, widths = pack_families(tests)
+        F = len(self.sizes)
+        counts = np.zeros((F, 12), np.int64)
+        scores = np.zeros((F, 5), np.float64)
+        sp = np.zeros(F, np.float32)
+        self.ctx._chk(self.L.ka_cmp_fam_score(self.h, _ptr(rows if len(rows) else np.zeros(1, np.uint8)), _ptr(widths), _ptr(counts), _ptr(scores), _ptr(sp)))
+        return [_cmp_result(counts[f], scores[f], sp[f]) for f in range(F)]
+
+    def stats(self):
+        """device ms (ka_cmp_fam_stats): the references' maps, then the test maps, the walk and TC of the last score call"""
+        st = np.zeros(4, np.float64)
+        self.ctx._chk(self.L.ka_cmp_fam_stats(self.h, _ptr(st)))
+        return dict(zip(["ref_maps_ms", "maps_ms", "walk_ms", "tc_ms"], st.tolist()))
+
+
+def _cmp_fam_create(self, refs):
+    """ka_cmp_fam_create: a FamilyComparer holding one reference alignment per family on this context's device"""
+    return FamilyComparer(self, refs)
+
+
+Context.family_comparer = _cmp_fam_create
 
 
 def guide_tree_from(lens, dist, n_threads=1, dm_scale=None):

@@ -2,7 +2,8 @@
 _with_mask (POAR recall, precision, F1, TC; lib/src/msa_cmp.c) on the device (Context.comparer).
 
 The reference pairs the rows of the two alignments after sorting both by name (kalign_sort_msa) and refuses a name that
-occurs twice (kalign_check_msa).  compare() does the same with named rows; rows without names are paired by position."""
+occurs twice (kalign_check_msa).  compare() does the same with named rows; rows without names are paired by position.  compare_families() does it for
+a batch of families, each with its own reference, in one device pass (Context.family_comparer)."""
 from .api import KalignAmdError
 from .synth import read_fasta
 
@@ -50,6 +51,28 @@ def compare(ctx, ref, test, max_gap_frac=-1.0, column_mask=None):
     cmp = ctx.comparer(r)
     try:
         return cmp.score(t, max_gap_frac=max_gap_frac, column_mask=column_mask)
+    finally:
+        cmp.close()
+
+
+def compare_families(ctx, refs, tests, max_gap_frac=-1.0, column_masks=None):
+    """compare() for a batch of families in one device pass (Context.family_comparer): refs[f] / tests[f] as compare()
+    takes ref / test, each family's rows paired as pair_rows pairs them; max_gap_frac one value or one per family,
+    column_masks None or per family None or a mask.  Returns one compare() dict per family; an error names the family."""
+    refs, tests = list(refs), list(tests)
+    if len(refs) != len(tests):
+        raise KalignAmdError("%d reference alignments, %d test alignments" % (len(refs), len(tests)))
+    r, t = [], []
+    for f, (a, b) in enumerate(zip(refs, tests)):
+        try:
+            ra, tb = pair_rows(a, b)
+        except KalignAmdError as e:
+            raise KalignAmdError("family %d: %s" % (f, e)) from None
+        r.append(ra)
+        t.append(tb)
+    cmp = ctx.family_comparer(r)
+    try:
+        return cmp.score(t, max_gap_frac=max_gap_frac, column_masks=column_masks)
     finally:
         cmp.close()
 

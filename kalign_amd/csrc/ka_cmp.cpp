@@ -3,7 +3,7 @@
 //
 // The reference alignment's position maps and per-column residue counts are built once (ka_cmp_create); each test
 // alignment gets its own maps, then the pair walk and the TC pass (ka_cmp.hip).  The device returns exact integer counts;
-// the final doubles are computed here with the reference's expressions, in its order.
+// the final doubles are computed on the host with the reference's expressions, in its order (ka_cmp_finish, ka_cmp.h).
 //
 // Unlike the reference, the two alignments must hold the same sequences: numseq rows each, row s with lens[s] letters
 // (the reference reads out of bounds otherwise).  Two sequences at least.
@@ -103,40 +103,9 @@ int ka_cmp::score(int K, const uint8_t* const* rows, const long long* strides, c
         HIPCHK(hipMemcpyAsync(tc.data(), dTc.p, sizeof(unsigned long long) * tc.size(), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         st[1] += ms(0, 1); st[2] += ms(1, 2); st[3] += ms(2, 3);
-        // every residue has N - 1 partners in each alignment: aligned or gap
-        const uint64_t all = (uint64_t)(N - 1) * (uint64_t)T;
-        for (int k = 0; k < K; k++) {
-                const long long* w = &sums[(size_t)k * KA_CMP_WALK];
-                // struct cmp_stats, in its field order
-                const uint64_t refAl = (uint64_t)w[KA_CMP_REF_ALIGNED], refGap = all - refAl;
-                const uint64_t identAl = (uint64_t)w[KA_CMP_IDENT_ALIGNED], identGap = (uint64_t)w[KA_CMP_IDENT_GAPS];
-                const uint64_t testAl = (uint64_t)w[KA_CMP_TEST_ALIGNED], testGap = all - testAl;
-                // struct detailed_pair_stats
-                const int64_t refScored = w[KA_CMP_REF_SCORED], testPairs = w[KA_CMP_TEST_ALIGNED];
-                const int64_t commonScored = w[KA_CMP_COMMON_SCORED], commonAll = w[KA_CMP_IDENT_ALIGNED];
-                const long long tcCorrect = (long long)tc[2 * k], tcTotal = (long long)tc[2 * k + 1];
-                if (counts) {
-                        long long* c = counts + (size_t)k * 12;
-                        c[0] = (long long)refAl; c[1] = (long long)refGap; c[2] = (long long)identAl; c[3] = (long long)identGap;
-                        c[4] = (long long)testAl; c[5] = (long long)testGap;
-                        c[6] = refScored; c[7] = testPairs; c[8] = commonScored; c[9] = commonAll;
-                        c[10] = tcCorrect; c[11] = tcTotal;
-                }
-                // kalign_msa_compare (msa_cmp.c:120-123)
-                const double sa = (double)(identAl + identGap);
-                const double sb = (double)(refAl + refGap);
-                const double spd = 100.0 * sa / sb;
-                if (sp) sp[k] = (float)spd;
-                // compare_with_mask_helper (msa_cmp.c:370-398)
-                const double recall = refScored > 0 ? (double)commonScored / (double)refScored : 0.0;
-                const double precision = testPairs > 0 ? (double)commonAll / (double)testPairs : 0.0;
-                const double f1 = recall + precision > 0.0 ? 2.0 * recall * precision / (recall + precision) : 0.0;
-                const double tcv = tcTotal > 0 ? (double)(int)tcCorrect / (double)(int)tcTotal : 0.0;
-                if (scores) {
-                        double* s = scores + (size_t)k * 5;
-                        s[0] = recall; s[1] = precision; s[2] = f1; s[3] = tcv; s[4] = spd;
-                }
-        }
+        for (int k = 0; k < K; k++)
+                ka_cmp_finish(&sums[(size_t)k * KA_CMP_WALK], (long long)tc[2 * k], (long long)tc[2 * k + 1], N, T,
+                              counts ? counts + (size_t)k * 12 : nullptr, scores ? scores + (size_t)k * 5 : nullptr, sp ? sp + k : nullptr);
         return KA_OK;
 }
 

@@ -26,7 +26,9 @@ struct KaSeqSet {
         int* dLens = nullptr;                  // [N]
 
         // checks the lengths (none negative, none above max_res -- `why` ends that message --, fewer than 2^31 residues
-        // in all) and copies them to the current device; errors read "<who>: ..."
+        // in all) and numbers the residues, on the host alone; errors read "<who>: ..."
+        int set(const char* who, int numseq, const int* lens, int max_res, const char* why);
+        // set(), then the lengths copied to the current device
         int init(const char* who, int numseq, const int* lens, int max_res, const char* why);
         void release();
 };

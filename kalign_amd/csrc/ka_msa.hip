@@ -37,7 +37,7 @@ void ka_msa_launch_maps(const uint8_t* rows, int rowStride, int W, int resStride
         msa_maps<<<(q.N + MSA_WAVES - 1) / MSA_WAVES, MSA_THREADS, 0, s>>>(rows, rowStride, W, resStride, q.N, q.dOffs, q.dLens, col, res);
 }
 
-int KaSeqSet::init(const char* who, int numseq, const int* l, int max_res, const char* why)
+int KaSeqSet::set(const char* who, int numseq, const int* l, int max_res, const char* why)
 {
         const std::string w(who);
         N = numseq;
@@ -53,6 +53,13 @@ int KaSeqSet::init(const char* who, int numseq, const int* l, int max_res, const
                 if (t > INT32_MAX) return fail(w + ": more than 2^31 - 1 residues");
         }
         offs[numseq] = T = (int)t;
+        return KA_OK;
+}
+
+int KaSeqSet::init(const char* who, int numseq, const int* l, int max_res, const char* why)
+{
+        const std::string w(who);
+        if (set(who, numseq, l, max_res, why)) return KA_FAIL;
         if (hipMalloc((void**)&dOffs, sizeof(int) * (numseq + 1)) != hipSuccess || hipMalloc((void**)&dLens, sizeof(int) * numseq) != hipSuccess)
                 return fail(w + ": out of device memory");
         HIPCHK(hipMemcpy(dOffs, offs.data(), sizeof(int) * (numseq + 1), hipMemcpyHostToDevice));
