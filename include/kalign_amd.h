@@ -696,6 +696,72 @@ int  ka_cmp_fam_score(ka_cmp_fam* h, const uint8_t* test_rows, const int* test_a
                       float* sp_out);
 int  ka_cmp_fam_stats(ka_cmp_fam* h, double* stats_out);
 
+/* ---- the ensemble consensus stage for a batch of families (ka_ens_fam.hip, ka_ens_fam.cpp) ------------------------------------
+ * What ka_ens_create + ka_ens_add_member + ka_ens_score_rows + ka_ens_consensus + ka_ens_confidence return for every family
+ * alone -- equal integer sums, doubles from the same expressions, byte-identical rows, bit-identical confidences -- for all
+ * families of a batch with the same number of members.  The number of launches and host synchronisations of a call depends
+ * on n_runs and on the number of candidate chunks, never on the number of families.  The POAR table as a file
+ * (ka_ens_table_*, ka_ens_open_table*, ka_ens_merge, ka_ens_select) stays a one-family operation: use ka_ens for it.
+ *   Families   fam_first[n_fam + 1] and lens[numseq] as ka_run_encoded_batch takes them.
+ *   Rows       packed as ka_batch_rows hands them out: families in order, the rows of family f alnlens[f] + 1 bytes apart
+ *              (the byte after a row is not read), so the output of ka_run_encoded_batch is a member as it stands.  alnlens
+ *              is per family.
+ *   Limits     per family those of ka_ens_create (n_runs 1..32, no sequence above 4096 residues, any numseq >= 1); over the
+ *              batch fewer than 2^31 residues and fewer than 2^31 row bytes.
+ *   ka_ens_fam_check          every check of a packed batch, on the host alone (no context, no GPU): fam_first ascends from 0
+ *                             ("fam_first does not ascend from 0 to numseq", "empty family"), and per family what ka_ens_create
+ *                             and ka_ens_add_member / ka_ens_score_rows check.  A message names the family and ends in the
+ *                             cause the one-family call gives: "ka_ens_fam_check: family 3: row 1 holds 7 letters, its
+ *                             sequence 8 (...)".  ka_ens_fam_add_member, _score and _confidence run it first: a refused batch
+ *                             launches nothing and leaves the handle usable.
+ *   ka_ens_fam_create         n_runs and the families are checked before ctx is touched.  Runs on ctx's device and stream:
+ *                             destroy it before ctx.
+ *   ka_ens_fam_add_member     member k (0 <= k < n_runs) of every family: one upload.  Every member must be added before the
+ *                             calls below.
+ *   ka_ens_fam_score_members  ka_ens_score_rows of every member of every family from the maps already on the device (nothing
+ *                             is uploaded again): sums_out / scores_out [n_runs * n_fam], member k of family f at k * n_fam + f.
+ *   ka_ens_fam_score          one alignment per family; alnlens[f] < 0: family f has no rows in the batch and is skipped, its
+ *                             outputs are 0.  sums_out / scores_out [n_fam] (each optional).
+ *   ka_ens_fam_consensus      ka_ens_consensus at min_support[f] >= 1 per family; letters: the letters of all sequences
+ *                             concatenated.  All support levels are counted in one pass; the candidates leave the device
+ *                             level by level, highest first, a level in chunks of whole families of at most KA_ENS_CHUNK
+ *                             candidates (a larger family is a chunk of its own), double-buffered; the families of a chunk are
+ *                             dealt to n_threads (1..16) host threads, each running the greedy union -- and after the last
+ *                             chunk the column order and the fill -- of whole families.  The result does not depend on
+ *                             n_threads.  alnlens_out[n_fam].
+ *   ka_ens_fam_rows_size / ka_ens_fam_rows   the rows of the last consensus, packed as above with a 0 byte after each row
+ *                             (-1 / an error when there is none).
+ *   ka_ens_fam_confidence     ka_ens_confidence of one alignment per family: res_conf_out per family [N_f][alnlens[f]] and
+ *                             col_conf_out [alnlens[f]], families back to back.
+ *   ka_ens_fam_stats          stats_out[21]: device ms of the position maps [0], of the last score call [1], of the last
+ *                             consensus' count pass [2] and write passes [3], of the last confidence [4]; of the last consensus
+ *                             host ms of the greedy union, column order and fill summed over the threads [5] and as wall time
+ *                             [6], host ms waiting for candidates [7], chunks [8], candidates [9], breadth-first searches that
+ *                             hit the 4096-set queue limit [10]; then kernel launches and host synchronisations of the last
+ *                             add_member [11, 12], score_members [13, 14], score [15, 16], consensus [17, 18] and confidence
+ *                             [19, 20] (the members' maps count for the call that builds them).
+ * One host-only seam for tests, needing no context and no GPU:
+ *   ka_debug_ens_fam_consensus_host   the greedy union, the column order and the fill over given candidate lists with the thread
+ *                             dealing of ka_ens_fam_consensus: cand holds two ints per candidate (residue numbers flat inside
+ *                             the family), family f's candidates from cand_first[f] to cand_first[f + 1], in the order they
+ *                             are to be replayed.  alnlens_out[n_fam] is always filled; KA_ERR_ROWS_STRIDE when rows_out is
+ *                             NULL or cap is below the packed size.
+ */
+typedef struct ka_ens_fam ka_ens_fam;
+int  ka_ens_fam_check(int n_fam, const int* fam_first, const int* lens, const uint8_t* rows, const int* alnlens);
+int  ka_ens_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, const int* lens, int n_runs, ka_ens_fam** out);
+void ka_ens_fam_destroy(ka_ens_fam* h);
+int  ka_ens_fam_add_member(ka_ens_fam* h, int k, const uint8_t* rows, const int* alnlens);
+int  ka_ens_fam_score_members(ka_ens_fam* h, long long* sums_out, double* scores_out);
+int  ka_ens_fam_score(ka_ens_fam* h, const uint8_t* rows, const int* alnlens, long long* sums_out, double* scores_out);
+int  ka_ens_fam_consensus(ka_ens_fam* h, const int* min_support, const uint8_t* letters, int n_threads, int* alnlens_out);
+long long ka_ens_fam_rows_size(ka_ens_fam* h);
+int  ka_ens_fam_rows(ka_ens_fam* h, uint8_t* out, long long cap);
+int  ka_ens_fam_confidence(ka_ens_fam* h, const uint8_t* rows, const int* alnlens, float* res_conf_out, float* col_conf_out);
+int  ka_ens_fam_stats(ka_ens_fam* h, double* stats_out);
+int  ka_debug_ens_fam_consensus_host(int n_fam, const int* fam_first, const int* lens, const long long* cand_first, const int* cand,
+                                     const uint8_t* letters, int n_threads, int* alnlens_out, uint8_t* rows_out, long long cap);
+
 #ifdef __cplusplus
 }
 #endif

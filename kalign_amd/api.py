@@ -61,6 +61,9 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_ens_open_table_image", "ka_ens_n_runs", "ka_ens_table_stats", "ka_poar_check_image", "ka_ens_merge", "ka_ens_select", "ka_cmp_create", "ka_cmp_destroy", "ka_cmp_set_mask", "ka_cmp_score",
            "ka_cmp_score_batch", "ka_cmp_stats",
            "ka_cmp_fam_check", "ka_cmp_fam_create", "ka_cmp_fam_destroy", "ka_cmp_fam_set_masks", "ka_cmp_fam_score", "ka_cmp_fam_stats",
+           "ka_ens_fam_check", "ka_ens_fam_create", "ka_ens_fam_destroy", "ka_ens_fam_add_member", "ka_ens_fam_score_members", "ka_ens_fam_score",
+           "ka_ens_fam_consensus", "ka_ens_fam_rows_size", "ka_ens_fam_rows", "ka_ens_fam_confidence", "ka_ens_fam_stats",
+           "ka_debug_ens_fam_consensus_host",
            "ka_guide_forest_from", "ka_guide_forest", "ka_aln_guide_forest", "ka_run_encoded_batch", "ka_batch_rows_size", "ka_batch_rows",
            "ka_batch_stats"]
 
@@ -231,6 +234,20 @@ def load_library():
     L.ka_cmp_fam_set_masks.argtypes = [vp, vp, vp, vp]
     L.ka_cmp_fam_score.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ka_cmp_fam_stats.argtypes = [vp, vp]
+    L.ka_ens_fam_check.argtypes = [C.c_int, vp, vp, vp, vp]
+    L.ka_ens_fam_create.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.POINTER(vp)]
+    L.ka_ens_fam_destroy.argtypes = [vp]
+    L.ka_ens_fam_destroy.restype = None
+    L.ka_ens_fam_add_member.argtypes = [vp, C.c_int, vp, vp]
+    L.ka_ens_fam_score_members.argtypes = [vp, vp, vp]
+    L.ka_ens_fam_score.argtypes = [vp, vp, vp, vp, vp]
+    L.ka_ens_fam_consensus.argtypes = [vp, vp, vp, C.c_int, vp]
+    L.ka_ens_fam_rows_size.argtypes = [vp]
+    L.ka_ens_fam_rows_size.restype = C.c_longlong
+    L.ka_ens_fam_rows.argtypes = [vp, vp, C.c_longlong]
+    L.ka_ens_fam_confidence.argtypes = [vp, vp, vp, vp, vp]
+    L.ka_ens_fam_stats.argtypes = [vp, vp]
+    L.ka_debug_ens_fam_consensus_host.argtypes = [C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_longlong]
     _lib = L
     return L
 
@@ -1249,6 +1266,150 @@ def _cmp_fam_create(self, refs):
 
 
 Context.family_comparer = _cmp_fam_create
+
+
+ENS_FAM_STATS = ["maps_ms", "score_ms", "count_ms", "write_ms", "confidence_ms", "greedy_threads_host_ms", "greedy_wall_host_ms",
+                 "wait_host_ms", "chunks", "candidates", "bfs_truncations", "add_member_launches", "add_member_syncs",
+                 "score_members_launches", "score_members_syncs", "score_launches", "score_syncs", "consensus_launches",
+                 "consensus_syncs", "confidence_launches", "confidence_syncs"]
+
+
+def _unpack_families(buf, sizes, widths):
+    """packed rows (pack_families' layout) -> one list of bytes per family"""
+    out, o = [], 0
+    for n, w in zip(sizes, widths):
+        w = int(w)
+        out.append([buf[o + k * (w + 1):o + k * (w + 1) + w].tobytes() for k in range(n)])
+        o += n * (w + 1)
+    return out
+
+
+class FamilyEnsemble(_CtxChild):
+    """The consensus stage of the ensembles of a batch of families with the same number of members (ka_ens_fam): per family
+    what an Ensemble of that family alone returns, in a number of launches and synchronisations that does not grow with
+    the batch.  families_rows: one list of rows per family (what Context.run_families returns is a member as it stands).
+    The POAR table as a file stays with Ensemble."""
+    _destroy = "ka_ens_fam_destroy"
+
+    def __init__(self, ctx, fam_lens, n_runs):
+        self.ctx, self.L = ctx, ctx.L
+        if not ctx.h:
+            raise KalignAmdError("the context is closed")
+        fam_lens = [np.ascontiguousarray(l, np.int32).reshape(-1) for l in fam_lens]
+        if not fam_lens:
+            raise KalignAmdError("a family ensemble needs a family")
+        self.sizes = [len(l) for l in fam_lens]
+        self.first = _fam_first(self.sizes)
+        self.lens = np.ascontiguousarray(np.concatenate(fam_lens), np.int32)
+        self.n_runs = int(n_runs)
+        h = C.c_void_p()
+        ctx._chk(self.L.ka_ens_fam_create(ctx.h, len(self.sizes), _ptr(self.first), _ptr(self.lens), self.n_runs, C.byref(h)))
+        self._adopt(ctx, h)
+
+    def _pack(self, families_rows, skip=False):
+        if not self.h:
+            raise KalignAmdError("the family ensemble is closed")
+        fams = [None if f is None else list(f) for f in families_rows]
+        if len(fams) != len(self.sizes):
+            raise KalignAmdError("%d alignments for %d families" % (len(fams), len(self.sizes)))
+        for f, (t, n) in enumerate(zip(fams, self.sizes)):
+            if t is None:
+                if not skip:
+                    raise KalignAmdError("family %d: no rows" % f)
+            elif len(t) != n:
+                raise KalignAmdError("family %d: the alignment has %d rows, the family %d sequences" % (f, len(t), n))
+        rows, widths = pack_families([t for t in fams if t is not None])
+        w = np.full(len(fams), -1, np.int32)
+        w[[f for f, t in enumerate(fams) if t is not None]] = widths
+        return (rows if len(rows) else np.zeros(1, np.uint8)), w
+
+    def add_member(self, k, families_rows):
+        rows, w = self._pack(families_rows)
+        self.ctx._chk(self.L.ka_ens_fam_add_member(self.h, int(k), _ptr(rows), _ptr(w)))
+
+    def score_members(self):
+        """(sums int64[n_runs, families], scores float64[n_runs, families]): Ensemble.score of every member, from the maps
+        on the device"""
+        F = len(self.sizes)
+        s = np.zeros((self.n_runs, F), np.int64)
+        v = np.zeros((self.n_runs, F), np.float64)
+        self.ctx._chk(self.L.ka_ens_fam_score_members(self.h, _ptr(s), _ptr(v)))
+        return s, v
+
+    def score(self, families_rows):
+        """(sums int64[families], scores float64[families]); a None entry skips that family: its outputs are 0"""
+        rows, w = self._pack(families_rows, skip=True)
+        s = np.zeros(len(self.sizes), np.int64)
+        v = np.zeros(len(self.sizes), np.float64)
+        self.ctx._chk(self.L.ka_ens_fam_score(self.h, _ptr(rows), _ptr(w), _ptr(s), _ptr(v)))
+        return s, v
+
+    def consensus(self, families_letters, min_support, n_threads=4):
+        """build_consensus per family at min_support (an int, or one per family): one list of consensus rows per family;
+        families_letters: per family its sequences (str / bytes)"""
+        if not self.h:
+            raise KalignAmdError("the family ensemble is closed")
+        flat = np.frombuffer(b"".join(x.encode() if isinstance(x, str) else bytes(x) for f in families_letters for x in f), np.uint8)
+        if [len(f) for f in families_letters] != self.sizes or len(flat) != int(self.lens.sum()):
+            raise KalignAmdError("letters do not match the families' sequence lengths")
+        ms = np.ascontiguousarray(np.broadcast_to(np.asarray(min_support, np.int32), (len(self.sizes),)))
+        w = np.zeros(len(self.sizes), np.int32)
+        self.ctx._chk(self.L.ka_ens_fam_consensus(self.h, _ptr(ms), _ptr(flat if len(flat) else np.zeros(1, np.uint8)), int(n_threads), _ptr(w)))
+        need = int(self.L.ka_ens_fam_rows_size(self.h))
+        buf = np.zeros(max(need, 1), np.uint8)
+        self.ctx._chk(self.L.ka_ens_fam_rows(self.h, _ptr(buf), need))
+        return _unpack_families(buf, self.sizes, w)
+
+    def confidence(self, families_rows):
+        """per family (float32[n, width] per residue, 0 at gaps; float32[width] per column), as Ensemble.confidence"""
+        rows, w = self._pack(families_rows)
+        n = np.asarray(self.sizes, np.int64)
+        res = np.zeros(max(int((n * w).sum()), 1), np.float32)
+        col = np.zeros(max(int(w.sum()), 1), np.float32)
+        self.ctx._chk(self.L.ka_ens_fam_confidence(self.h, _ptr(rows), _ptr(w), _ptr(res), _ptr(col)))
+        out, o, c = [], 0, 0
+        for k, x in zip(self.sizes, w):
+            x = int(x)
+            out.append((res[o:o + k * x].reshape(k, x).copy(), col[c:c + x].copy()))
+            o += k * x
+            c += x
+        return out
+
+    def stats(self):
+        """measurements of the last calls (ka_ens_fam_stats) as a dict; the counts as ints"""
+        st = np.zeros(len(ENS_FAM_STATS), np.float64)
+        self.ctx._chk(self.L.ka_ens_fam_stats(self.h, _ptr(st)))
+        return {k: (float(v) if k.endswith("_ms") else int(v)) for k, v in zip(ENS_FAM_STATS, st)}
+
+
+def _ens_fam_create(self, fam_lens, n_runs):
+    """ka_ens_fam_create: a FamilyEnsemble for families of sequences of these lengths (one list per family), n_runs members each"""
+    return FamilyEnsemble(self, fam_lens, n_runs)
+
+
+Context.family_ensemble = _ens_fam_create
+
+
+def ens_fam_consensus_host(fam_lens, cands, families_letters, n_threads=1):
+    """tests only: ka_debug_ens_fam_consensus_host -- the greedy union, column order and fill of every family over given
+    candidate lists (cands[f]: int array [n, 2], residue numbers flat inside the family), dealt to n_threads as
+    FamilyEnsemble.consensus deals them; no GPU needed.  Returns one list of rows per family."""
+    L = load_library()
+    sizes = [len(l) for l in fam_lens]
+    first = _fam_first(sizes)
+    lens = np.ascontiguousarray(np.concatenate([np.asarray(l, np.int32).reshape(-1) for l in fam_lens]), np.int32)
+    cfirst = np.zeros(len(sizes) + 1, np.int64)
+    cfirst[1:] = np.cumsum([len(c) for c in cands])
+    parts = [np.asarray(c, np.int32).reshape(-1, 2) for c in cands]
+    cand = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, 2), np.int32), np.int32)
+    flat = np.frombuffer(b"".join(x.encode() if isinstance(x, str) else bytes(x) for f in families_letters for x in f), np.uint8)
+    w = np.zeros(len(sizes), np.int32)
+    cap = int(sum(n * (int(np.sum(l)) + 1) for n, l in zip(sizes, fam_lens)))         # (no more columns than residues)
+    buf = np.zeros(max(cap, 1), np.uint8)
+    if L.ka_debug_ens_fam_consensus_host(len(sizes), _ptr(first), _ptr(lens), _ptr(cfirst), _ptr(cand if len(cand) else np.zeros((1, 2), np.int32)),
+                                         _ptr(flat if len(flat) else np.zeros(1, np.uint8)), int(n_threads), _ptr(w), _ptr(buf), cap):
+        raise KalignAmdError(L.ka_last_error().decode())
+    return _unpack_families(buf, sizes, w)
 
 
 def guide_tree_from(lens, dist, n_threads=1, dm_scale=None):

@@ -21,157 +21,12 @@
 // back edges (topo_sort, consensus_msa.c:255-370) and filled with the caller's letters.
 #include "ka_ctx.h"
 #include "ka_ens.h"
+#include "ka_ens_union.h"     // Uf, topo_order, ka_ens_fill: shared with ka_ens_fam.cpp
 #include "ka_msa.h"
 
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
 
 namespace {
-
-struct Uf {
-        // union by rank with path halving; per-set member lists; sequence sets as bitmasks, kept for sets of two or
-        // more residues only (a singleton's set is the bit of its own sequence)
-        std::vector<int> parent, rnk, elemSeq, head, next, tail, maskOf;
-        std::vector<uint64_t> pool;
-        std::vector<int> freeSlots;
-        int mw = 1;
-        std::vector<long long> visited;
-        long long visit = 0;
-        long long truncations = 0;
-        const std::vector<int>* offs = nullptr;
-        const std::vector<int>* lens = nullptr;
-
-        void init(const std::vector<int>& o, const std::vector<int>& l, int T)
-        {
-                offs = &o; lens = &l;
-                const int N = (int)l.size();
-                mw = (N + 63) / 64;
-                parent.resize(T); rnk.assign(T, 0); elemSeq.resize(T); head.resize(T); next.assign(T, -1); tail.resize(T);
-                maskOf.assign(T, -1); visited.assign(T, 0);
-                pool.clear(); freeSlots.clear(); visit = 0; truncations = 0;
-                for (int e = 0; e < T; e++) { parent[e] = e; head[e] = e; tail[e] = e; }
-                for (int s = 0; s < N; s++)
-                        for (int p = 0; p < l[s]; p++) elemSeq[o[s] + p] = s;
-        }
-        int find(int x)
-        {
-                while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
-                return x;
-        }
-        bool hasSeq(int root, int s) const
-        {
-                const int m = maskOf[root];
-                if (m < 0) return elemSeq[root] == s;
-                return pool[(size_t)m * mw + s / 64] >> (s % 64) & 1u;
-        }
-        bool share(int a, int b) const
-        {
-                const int ma = maskOf[a], mb = maskOf[b];
-                if (ma < 0) return hasSeq(b, elemSeq[a]);
-                if (mb < 0) return hasSeq(a, elemSeq[b]);
-                for (int w = 0; w < mw; w++)
-                        if (pool[(size_t)ma * mw + w] & pool[(size_t)mb * mw + w]) return true;
-                return false;
-        }
-        int slot()
-        {
-                if (!freeSlots.empty()) { const int s = freeSlots.back(); freeSlots.pop_back(); std::fill_n(&pool[(size_t)s * mw], mw, 0); return s; }
-                pool.resize(pool.size() + mw, 0);
-                return (int)(pool.size() / mw) - 1;
-        }
-        // is `target` reachable from `start` through the column DAG?  Queue of 4096 sets, full = not queued (still marked)
-        bool reaches(int start, int target)
-        {
-                int queue[4096];
-                int qh = 0, qt = 0;
-                if (start == target) return true;
-                visit++;
-                queue[qt++] = start;
-                visited[start] = visit;
-                while (qh < qt) {
-                        const int cur = queue[qh++];
-                        for (int e = head[cur]; e >= 0; e = next[e]) {
-                                const int s = elemSeq[e];
-                                if (e - (*offs)[s] + 1 >= (*lens)[s]) continue;
-                                const int r = find(e + 1);
-                                if (r == target) return true;
-                                if (r != cur && visited[r] != visit) {
-                                        visited[r] = visit;
-                                        if (qt < 4096) queue[qt++] = r;
-                                        else truncations++;
-                                }
-                        }
-                }
-                return false;
-        }
-        void join(int a, int b)
-        {
-                const int ra = find(a), rb = find(b);
-                if (ra == rb) return;
-                if (share(ra, rb)) return;
-                if (reaches(ra, rb)) return;
-                if (reaches(rb, ra)) return;
-                int keep, gone;
-                if (rnk[ra] < rnk[rb]) { keep = rb; gone = ra; }
-                else { keep = ra; gone = rb; if (rnk[ra] == rnk[rb]) rnk[ra]++; }
-                parent[gone] = keep;
-                if (maskOf[keep] < 0) {
-                        const int s = slot();
-                        maskOf[keep] = s;
-                        pool[(size_t)s * mw + elemSeq[keep] / 64] |= 1ull << (elemSeq[keep] % 64);
-                }
-                uint64_t* km = &pool[(size_t)maskOf[keep] * mw];
-                if (maskOf[gone] < 0) km[elemSeq[gone] / 64] |= 1ull << (elemSeq[gone] % 64);
-                else {
-                        const uint64_t* gm = &pool[(size_t)maskOf[gone] * mw];
-                        for (int w = 0; w < mw; w++) km[w] |= gm[w];
-                        freeSlots.push_back(maskOf[gone]);
-                        maskOf[gone] = -1;
-                }
-                if (head[gone] >= 0) {
-                        if (head[keep] < 0) { head[keep] = head[gone]; tail[keep] = tail[gone]; }
-                        else { next[tail[keep]] = head[gone]; tail[keep] = tail[gone]; }
-                }
-                head[gone] = -1;
-        }
-};
-
-// DFS topological sort of the columns, back edges skipped; returns order[position] = column
-std::vector<int> topo_order(const std::vector<int>& colId, const std::vector<int>& offs, const std::vector<int>& lens, int nCols)
-{
-        std::vector<std::vector<int>> adj(nCols);
-        for (size_t s = 0; s < lens.size(); s++)
-                for (int p = 0; p + 1 < lens[s]; p++) {
-                        const int ca = colId[offs[s] + p], cb = colId[offs[s] + p + 1];
-                        if (ca == cb) continue;
-                        std::vector<int>& l = adj[ca];
-                        if (std::find(l.begin(), l.end(), cb) == l.end()) l.push_back(cb);
-                }
-        std::vector<int> out(nCols), state(nCols, 0), stack;
-        stack.reserve(2 * (size_t)nCols);
-        int at = nCols - 1;
-        for (int start = 0; start < nCols; start++) {
-                if (state[start]) continue;
-                stack.push_back(start); stack.push_back(0);
-                state[start] = 1;
-                while (!stack.empty()) {
-                        const int edge = stack.back(); stack.pop_back();
-                        const int node = stack.back(); stack.pop_back();
-                        bool pushed = false;
-                        for (int e = edge; e < (int)adj[node].size(); e++) {
-                                const int nx = adj[node][e];
-                                if (state[nx] == 0) {
-                                        stack.push_back(node); stack.push_back(e + 1);
-                                        stack.push_back(nx); stack.push_back(0);
-                                        state[nx] = 1;
-                                        pushed = true;
-                                        break;
-                                }
-                        }
-                        if (!pushed) { state[node] = 2; out[at--] = node; }
-                }
-        }
-        return out;
-}
 
 double ms_since(std::chrono::steady_clock::time_point t0)
 {
@@ -418,7 +273,7 @@ int ka_ens::stream_rows(KaEnsArgs a, Count count, Write write, Consume consume, 
 int ka_ens::consensus(int minSup, const uint8_t* letters)
 {
         using clk = std::chrono::steady_clock;
-        const int N = q.N, T = q.T;
+        const int T = q.T;
         const std::vector<int>& lens = q.lens;
         const std::vector<int>& offs = q.offs;
         st[2] = st[3] = st[4] = st[5] = st[7] = st[8] = st[9] = 0.0;
@@ -444,19 +299,8 @@ int ka_ens::consensus(int minSup, const uint8_t* letters)
         st[9] = (double)uf.truncations;
         // columns numbered by first residue, ordered, filled
         const auto tt = clk::now();
-        std::vector<int> rootCol(T, -1), colId(T);
         int nCols = 0;
-        for (int e = 0; e < T; e++) {
-                const int r = uf.find(e);
-                if (rootCol[r] < 0) rootCol[r] = nCols++;
-                colId[e] = rootCol[r];
-        }
-        const std::vector<int> order = topo_order(colId, offs, lens, nCols);
-        std::vector<int> pos(nCols);
-        for (int p = 0; p < nCols; p++) pos[order[p]] = p;
-        cacheRows.assign((size_t)N * nCols, '-');
-        for (int s = 0; s < N; s++)
-                for (int p = 0; p < lens[s]; p++) cacheRows[(size_t)s * nCols + pos[colId[offs[s] + p]]] = letters[offs[s] + p];
+        ka_ens_fill(uf, offs, lens, T, letters, cacheRows, &nCols);
         st[5] = ms_since(tt);
         cacheW = nCols; cacheMin = minSup; cacheGen = generation;
         cacheLetters.assign(letters, letters + T);

@@ -9,6 +9,7 @@
 #define KA_ENS_STATS 10            // ka_ens_stats: see include/kalign_amd.h
 #define KA_ENS_TABLE_STATS 6       // ka_ens_table_stats
 #define KA_ENS_JCHUNK 16           // j per workgroup of the support walk (4 waves, one j at a time each)
+#define KA_ENS_FAM_STATS 21        // ka_ens_fam_stats
 
 enum { KA_ENS_SCORE = 0, KA_ENS_CONF = 1, KA_ENS_COUNT = 2, KA_ENS_WRITE = 3 };
 
@@ -75,3 +76,52 @@ void ka_poar_launch_select(int mode, const KaEnsArgs& a, hipStream_t s);      //
 void ka_poar_launch_pair_start(const long long* pairOff, const long long* rowBase, int i0, int i1, int N, long long* pairStart, hipStream_t s);
 // ka_poar.cpp: the checks of ka_poar_check_image; also fills the pairs' first entries (n_pairs + 1) when asked
 int ka_poar_parse(const uint8_t* image, long long nBytes, int numseq, const int* lens, int* nRuns, long long* entries, std::vector<long long>* pairStart);
+
+// ---- a batch of families with the same number of members (ka_ens_fam.hip kernels, ka_ens_fam.cpp host side) ----
+// Sequences and residues are numbered flat over the batch; a table named first...[nFam + 1] ascends and is searched for the
+// family of a flat index.  The residues a candidate names are numbered inside its family.
+struct KaEnsFam {
+        int firstSeq, firstRes, N, maxlen;
+        int nJC;                   // chunks of KA_ENS_JCHUNK sequences j: the family has N * nJC workgroups in a walk
+        int colInLds;              // the member columns of a sequence fit in LDS next to the three per-residue arrays
+        int minSup;                // the last consensus: levels n_runs .. minSup
+        int pad;
+        long long cntFirst;        // the count table of one level: [N][N] entries per family, those of the families before this one
+};
+
+struct KaEnsFamArgs {
+        int nFam, S, T, R;
+        const KaEnsFam* fams;
+        const int* firstSeq;       // [nFam + 1]
+        const int* blkFirst;       // [nFam + 1] walk workgroups of the families before f
+        const int* offs;           // [S + 1] first residue of flat sequence s
+        const int* lens;           // [S]
+        const int* col;            // [R][T]
+        const int16_t* res;        // member k at resBase[k]; in it family f at memCell[k * (nFam + 1) + f]: [N_f][memW[k * nFam + f]]
+        long long resBase[KA_ENS_MAX_RUNS];
+        const int* memCell;
+        const int* memW;
+        // the alignments X of SCORE / CONF, one per family: their own tables (or those of a member)
+        const int* colX;           // [T]
+        const int16_t* resX;       // family f at xCell[f]: [N_f][xW[f]]
+        const int* xCell;          // [nFam + 1]
+        const int* xW;             // [nFam]; <= 0: the family is skipped
+        const int* xCol;           // [nFam + 1] CONF: columns of the families before f
+        int blk0;                  // first workgroup of this launch (WRITE: the first of the chunk's families)
+        int level;                 // WRITE: support value of the candidates
+        long long E;               // entries of one level of the count table (level n_runs - lv at lv * E; its rows at lv * S)
+        unsigned long long* score; // SCORE: [nFam]
+        int* supSum;               // CONF: [T]
+        int* nPair;                // CONF: [T]
+        int* cnt;                  // COUNT: candidates per (level, family, i, j)
+        const long long* pairOff;  // WRITE: the same entries scanned along j
+        const long long* rowBase;  // WRITE: first slot of row (level, flat i), relative to its chunk
+        int2* out;                 // WRITE: (residue of i, residue of j), numbered inside the family
+};
+
+// ka_ens_fam.hip
+void ka_ensf_launch_maps(const KaEnsFamArgs& a, const uint8_t* rows, const long long* rowOff, const int* W, const int* cell, int* col, int16_t* res,
+                         hipStream_t s);                                       // rows of family f at rowOff[f], W[f] + 1 bytes apart
+void ka_ensf_launch_walk(int mode, const KaEnsFamArgs& a, int nBlocks, size_t lds, hipStream_t s);
+void ka_ensf_launch_row_scan(const KaEnsFamArgs& a, int nRows, long long* pairOff, long long* rowTot, hipStream_t s);
+void ka_ensf_launch_conf(const KaEnsFamArgs& a, int cells, int cols, float* conf, float* colConf, hipStream_t s);

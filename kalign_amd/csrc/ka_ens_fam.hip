@@ -1,0 +1,296 @@
+// ka_ens_fam.hip -- the ensemble consensus stage for a batch of families: the kernels of ka_ens.hip (and msa_maps) in the
+// form that takes every family of the batch in one launch (ka_ens_fam.cpp is the host side, ka_ens.h the shared tables).
+//
+// Sequences and residues are numbered flat over the batch.  A wave or workgroup finds the family of its flat index by a
+// search of an ascending first-index table (ensf_find: wave-uniform), then works with that family's geometry from its
+// KaEnsFam and the per-family entries of the member tables.
+//
+//   ensf_maps      a wave per packed row: msa_maps' ballot-prefix rank with the row's own start and width
+//   ensf_walk      a workgroup per (flat sequence i, chunk of KA_ENS_JCHUNK sequences j of i's family): ens_walk.  SCORE adds
+//                  into the family's sum with a 64-bit vector atomic (exact integers: the order does not matter); CONF is
+//                  ens_walk's.  COUNT takes every support level n_runs .. minSup of the family in ONE pass: the n_runs
+//                  gathers of (i, ri, j) give the level of each distinct partner, and a wave's per-level counters live in its
+//                  lanes (lane L - 1 holds level L).  WRITE is ens_walk's, one level at a time, for the families of a chunk.
+//   ensf_row_scan  a workgroup per row (level, flat sequence i) of the count table: ens_row_scan
+//   ensf_conf_res  a thread per cell of the packed X maps, ensf_conf_col a thread per flat column: ens_conf_res / ens_conf_col,
+//                  a column's confidences added in row order in double as the reference adds them
+#include <hip/hip_runtime.h>
+#include "ka_ens.h"
+#include "ka_msa.h"
+
+#define ENSF_THREADS 256
+#define ENSF_WAVES (ENSF_THREADS / 64)
+
+// the last f in [0, n) with first[f] <= x (first ascends, first[0] <= x; equal neighbours are empty ranges and are skipped)
+__device__ __forceinline__ int ensf_find(const int* first, int n, int x)
+{
+        int lo = 0, hi = n - 1;
+        while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (first[mid] <= x) lo = mid;
+                else hi = mid - 1;
+        }
+        return lo;
+}
+
+__device__ __forceinline__ int ensf_wave_sum_all(int v)
+{
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        return v;
+}
+
+__global__ __launch_bounds__(ENSF_THREADS) void ensf_maps(KaEnsFamArgs a, const uint8_t* rows, const long long* rowOff, const int* Wt, const int* cell,
+                                                          int* col, int16_t* res)
+{
+        const int s = blockIdx.x * ENSF_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+        if (s >= a.S) return;
+        const int f = ensf_find(a.firstSeq, a.nFam, s);
+        const int W = Wt[f];
+        if (W <= 0) return;                                      // (a skipped family of a score call)
+        const int loc = s - a.firstSeq[f];
+        const uint8_t* row = rows + rowOff[f] + (long long)loc * (W + 1);
+        int16_t* rs = res + cell[f] + (long long)loc * W;
+        int* cs = col + a.offs[s];
+        const int len = a.lens[s];
+        const unsigned long long below = (1ull << lane) - 1ull;
+        int run = 0;
+        for (int cb = 0; cb < W; cb += 64) {
+                const int c = cb + lane;
+                const bool isr = c < W && ka_msa_is_residue(row[c]);
+                const unsigned long long m = __ballot(isr);
+                const int r = run + __popcll(m & below);
+                const bool put = isr && r < len;
+                if (c < W) rs[c] = put ? (int16_t)r : (int16_t)-1;
+                if (put) cs[r] = c;
+                run += __popcll(m);
+        }
+}
+
+template <int MODE, int RM>
+__global__ __launch_bounds__(ENSF_THREADS) void ensf_walk(KaEnsFamArgs a)
+{
+        extern __shared__ int lds[];
+        const int b = a.blk0 + (int)blockIdx.x;
+        const int f = ensf_find(a.blkFirst, a.nFam, b);
+        const KaEnsFam d = a.fams[f];
+        const int t0 = b - a.blkFirst[f];
+        const int il = t0 / d.nJC;                               // i and j inside the family
+        const int j0 = (t0 % d.nJC) * KA_ENS_JCHUNK;
+        const int j1 = min(d.N, j0 + KA_ENS_JCHUNK);
+        if (MODE != KA_ENS_CONF && j1 <= il + 1) return;         // only pairs j > i (uniform over the workgroup)
+        if (MODE == KA_ENS_WRITE && a.level < d.minSup) return;  // the family stops above this level
+        constexpr bool withX = MODE == KA_ENS_SCORE || MODE == KA_ENS_CONF;
+        int Wx = 0;
+        const int16_t* resX = nullptr;
+        if (withX) {
+                Wx = a.xW[f];
+                if (Wx <= 0) return;                             // a skipped family (uniform)
+                resX = a.resX + a.xCell[f];
+        }
+        const int si = d.firstSeq + il;
+        const int li = a.lens[si], oi = a.offs[si], R = a.R;
+        int* cxL = lds;                                          // SCORE / CONF: column of X of residue ri
+        int* sumL = lds + d.maxlen;                              // CONF: per-residue sums of this workgroup
+        int* npL = lds + 2 * d.maxlen;
+        int* colL = lds + (withX ? 3 * d.maxlen : 0);            // [R][li] when staged (COUNT / WRITE: nothing else)
+        const int* colP;
+        long long cs;
+        if (d.colInLds) {
+                for (int t = threadIdx.x; t < R * li; t += ENSF_THREADS) {
+                        const int k = t / li;
+                        colL[t] = a.col[(long long)k * a.T + oi + (t - k * li)];
+                }
+                colP = colL; cs = li;
+        } else {
+                colP = a.col + oi; cs = a.T;
+        }
+        if (withX)
+                for (int t = threadIdx.x; t < li; t += ENSF_THREADS) {
+                        cxL[t] = a.colX[oi + t];
+                        if (MODE == KA_ENS_CONF) { sumL[t] = 0; npL[t] = 0; }
+                }
+        __syncthreads();
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        long long acc = 0;
+        for (int j = j0 + wave; j < j1; j += ENSF_WAVES) {
+                if (MODE == KA_ENS_CONF ? j == il : j <= il) continue;
+                const int oj = a.offs[d.firstSeq + j];
+                long long rowK[RM];                              // row j of this family in member k's res map (wave-uniform)
+#pragma unroll
+                for (int k = 0; k < RM; k++)
+                        rowK[k] = k < R ? a.resBase[k] + a.memCell[(long long)k * (a.nFam + 1) + f] + (long long)j * a.memW[(long long)k * a.nFam + f] : 0;
+                int perLevel = 0;                                // COUNT: lane L - 1 counts level L
+                long long base = 0;                              // WRITE: the pair's next slot
+                if (MODE == KA_ENS_WRITE)
+                        base = a.rowBase[(long long)(R - a.level) * a.S + si] + a.pairOff[(long long)(R - a.level) * a.E + d.cntFirst + (long long)il * d.N + j];
+                for (int rb = 0; rb < li; rb += 64) {
+                        const int ri = rb + lane;
+                        const bool ok = ri < li;
+                        if (withX) {
+                                if (!ok) continue;
+                                const int rj = resX[(long long)j * Wx + cxL[ri]];
+                                if (rj < 0) continue;
+                                int sup = 0;
+#pragma unroll
+                                for (int k = 0; k < RM; k++)
+                                        if (k < R) sup += a.res[rowK[k] + colP[k * cs + ri]] == rj;
+                                if (MODE == KA_ENS_SCORE) acc += sup - 1;
+                                else { atomicAdd(&sumL[ri], sup); atomicAdd(&npL[ri], 1); }
+                        } else {
+                                // the residues of j that the members put next to (i, ri); lev[k]: the number of members that hold
+                                // v[k], at the first k that holds it (0 elsewhere and at gaps) -- its support level
+                                int v[RM], lev[RM];
+#pragma unroll
+                                for (int k = 0; k < RM; k++)
+                                        v[k] = (ok && k < R) ? (int)a.res[rowK[k] + colP[k * cs + ri]] : -1;
+#pragma unroll
+                                for (int k = 0; k < RM; k++) {
+                                        int m = 0;
+                                        bool first = true;
+#pragma unroll
+                                        for (int k2 = 0; k2 < RM; k2++) {
+                                                m += v[k2] == v[k];
+                                                if (k2 < k && v[k2] == v[k]) first = false;
+                                        }
+                                        lev[k] = (v[k] >= 0 && first) ? m : 0;
+                                }
+                                if (MODE == KA_ENS_COUNT) {
+                                        for (int L = d.minSup; L <= R; L++) {
+                                                int c = 0;
+#pragma unroll
+                                                for (int k = 0; k < RM; k++) c += lev[k] == L;
+                                                c = ensf_wave_sum_all(c);
+                                                if (lane == L - 1) perLevel += c;
+                                        }
+                                        continue;
+                                }
+                                // WRITE, one level: the distinct partners held by exactly `level` members, in ascending order (the
+                                // reference's key order ri << 20 | rj)
+                                unsigned q = 0;
+#pragma unroll
+                                for (int k = 0; k < RM; k++) q |= (unsigned)(lev[k] == a.level) << k;
+                                const int c = __popc(q);
+                                const int incl = ens_wave_incl_scan(c, lane);
+                                const int total = __shfl(incl, 63, 64);
+                                const long long at = base + incl - c;
+#pragma unroll
+                                for (int k = 0; k < RM; k++) {
+                                        if (!(q >> k & 1u)) continue;
+                                        int rank = 0;
+#pragma unroll
+                                        for (int k2 = 0; k2 < RM; k2++) rank += (q >> k2 & 1u) && v[k2] < v[k];
+                                        a.out[at + rank] = make_int2(oi - d.firstRes + ri, oj - d.firstRes + v[k]);
+                                }
+                                base += total;
+                        }
+                }
+                if (MODE == KA_ENS_COUNT && lane < R && lane + 1 >= d.minSup)
+                        a.cnt[(long long)(R - 1 - lane) * a.E + d.cntFirst + (long long)il * d.N + j] = perLevel;
+        }
+        if (MODE == KA_ENS_SCORE) {
+                const long long t = ka_msa_wave_sum(acc);
+                if (lane == 0 && t) atomicAdd(&a.score[f], (unsigned long long)t);
+        }
+        if (MODE == KA_ENS_CONF) {
+                __syncthreads();
+                for (int t = threadIdx.x; t < li; t += ENSF_THREADS)
+                        if (npL[t]) { atomicAdd(&a.supSum[oi + t], sumL[t]); atomicAdd(&a.nPair[oi + t], npL[t]); }
+        }
+}
+
+// one workgroup per row (level, flat sequence i) of the count table: exclusive scan of the pair counts over j, and the row's total
+__global__ __launch_bounds__(ENSF_THREADS) void ensf_row_scan(KaEnsFamArgs a, long long* pairOff, long long* rowTot)
+{
+        __shared__ long long wsum[ENSF_WAVES];
+        const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int lv = r / a.S, si = r - lv * a.S;
+        const int f = ensf_find(a.firstSeq, a.nFam, si);
+        const int N = a.fams[f].N;
+        const long long at = (long long)lv * a.E + a.fams[f].cntFirst + (long long)(si - a.firstSeq[f]) * N;
+        const int* c = a.cnt + at;
+        long long* po = pairOff + at;
+        long long run = 0;
+        for (int b = 0; b < N; b += ENSF_THREADS) {
+                const int j = b + threadIdx.x;
+                const int v = j < N ? c[j] : 0;
+                const int incl = ens_wave_incl_scan(v, lane);
+                if (lane == 63) wsum[wave] = incl;
+                __syncthreads();
+                long long before = run;
+                for (int w = 0; w < wave; w++) before += wsum[w];
+                if (j < N) po[j] = before + incl - v;
+                long long tot = 0;
+                for (int w = 0; w < ENSF_WAVES; w++) tot += wsum[w];
+                __syncthreads();
+                run += tot;
+        }
+        if (threadIdx.x == 0) rowTot[r] = run;
+}
+
+// compute_residue_confidence (consensus_msa.c:564-692): per residue (float)(sum / ((double)n_pairs * n_runs)), gaps 0
+__global__ void ensf_conf_res(KaEnsFamArgs a, float* conf)
+{
+        const long long tt = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (tt >= a.xCell[a.nFam]) return;
+        const int t = (int)tt, f = ensf_find(a.xCell, a.nFam, t);
+        const int s = a.firstSeq[f] + (t - a.xCell[f]) / a.xW[f];
+        const int r = a.resX[t];
+        float v = 0.0f;
+        if (r >= 0) {
+                const int e = a.offs[s] + r;
+                const int np = a.nPair[e];
+                if (np > 0) v = (float)((double)a.supSum[e] / ((double)np * (double)a.R));
+        }
+        conf[t] = v;
+}
+
+// ... per column: the residues' confidences added in row order in double, (float)(sum / count)
+__global__ void ensf_conf_col(KaEnsFamArgs a, const float* conf, float* colConf)
+{
+        const long long cc = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (cc >= a.xCol[a.nFam]) return;
+        const int c = (int)cc, f = ensf_find(a.xCol, a.nFam, c);
+        const int W = a.xW[f], N = a.fams[f].N;
+        const long long at = (long long)a.xCell[f] + (c - a.xCol[f]);
+        double sum = 0.0;
+        int count = 0;
+        for (int s = 0; s < N; s++)
+                if (a.resX[at + (long long)s * W] >= 0) { sum += conf[at + (long long)s * W]; count++; }
+        colConf[c] = count > 0 ? (float)(sum / count) : 0.0f;
+}
+
+template <int MODE>
+static void walk(const KaEnsFamArgs& a, int nBlocks, size_t lds, hipStream_t s)
+{
+        if (nBlocks <= 0) return;
+        if (a.R <= 8) ensf_walk<MODE, 8><<<(unsigned)nBlocks, ENSF_THREADS, lds, s>>>(a);
+        else ensf_walk<MODE, KA_ENS_MAX_RUNS><<<(unsigned)nBlocks, ENSF_THREADS, lds, s>>>(a);
+}
+
+void ka_ensf_launch_maps(const KaEnsFamArgs& a, const uint8_t* rows, const long long* rowOff, const int* W, const int* cell, int* col, int16_t* res,
+                         hipStream_t s)
+{
+        ensf_maps<<<(a.S + ENSF_WAVES - 1) / ENSF_WAVES, ENSF_THREADS, 0, s>>>(a, rows, rowOff, W, cell, col, res);
+}
+
+void ka_ensf_launch_walk(int mode, const KaEnsFamArgs& a, int nBlocks, size_t lds, hipStream_t s)
+{
+        switch (mode) {
+        case KA_ENS_SCORE: walk<KA_ENS_SCORE>(a, nBlocks, lds, s); break;
+        case KA_ENS_CONF: walk<KA_ENS_CONF>(a, nBlocks, lds, s); break;
+        case KA_ENS_COUNT: walk<KA_ENS_COUNT>(a, nBlocks, lds, s); break;
+        default: walk<KA_ENS_WRITE>(a, nBlocks, lds, s); break;
+        }
+}
+
+void ka_ensf_launch_row_scan(const KaEnsFamArgs& a, int nRows, long long* pairOff, long long* rowTot, hipStream_t s)
+{
+        if (nRows > 0) ensf_row_scan<<<nRows, ENSF_THREADS, 0, s>>>(a, pairOff, rowTot);
+}
+
+void ka_ensf_launch_conf(const KaEnsFamArgs& a, int cells, int cols, float* conf, float* colConf, hipStream_t s)
+{
+        ensf_conf_res<<<(unsigned)(((long long)cells + 255) / 256), 256, 0, s>>>(a, conf);
+        ensf_conf_col<<<(unsigned)(((long long)cols + 255) / 256), 256, 0, s>>>(a, conf, colConf);
+}

@@ -69,6 +69,66 @@ def finish_ensemble(ctx, member_rows, letters, min_support=0, rerun_refined=None
         ens.close()
 
 
+def finish_ensembles(ctx, member_rows, letters, min_support=0, rerun_refined=None, n_threads=4):
+    """finish_ensemble for a batch of families with the same number of members, in a number of launches that does not grow
+    with the batch (Context.family_ensemble).  member_rows[k][f]: the rows of member k of family f (what k calls of
+    Context.run_families return); letters[f]: the sequences of family f.  min_support as finish_ensemble's, for every family.
+    rerun_refined(list of (f, best_k)) is asked once, for the families whose selected member beat the consensus, and
+    returns their refined rows in that order.  n_threads: host threads of the consensus (1..16).
+    Returns one dict per family with finish_ensemble's keys, each equal to finish_ensemble run on that family alone
+    (stats: the batch's, the same dict in every family)."""
+    n_runs = len(member_rows)
+    if n_runs < 1:
+        raise KalignAmdError("an ensemble needs members")
+    letters = [[x.encode() if isinstance(x, str) else bytes(x) for x in f] for f in letters]
+    F = len(letters)
+    ens = ctx.family_ensemble([residue_lens(f) for f in letters], n_runs)
+    try:
+        for k, fams in enumerate(member_rows):
+            ens.add_member(k, fams)
+        scores = ens.score_members()[1]
+        outs = []
+        for f in range(F):
+            sc = [float(scores[k, f]) for k in range(n_runs)]
+            outs.append(dict(scores=sc, best_k=select(sc), use_consensus=False, consensus_score=None, refined_score=None, refined=False))
+        chosen = [[bytes(r.encode() if isinstance(r, str) else r) for r in member_rows[o["best_k"]][f]] for f, o in enumerate(outs)]
+        if min_support > 0:
+            chosen = ens.consensus(letters, int(min_support), n_threads)
+            for o in outs:
+                o["use_consensus"] = True
+        else:
+            cons = ens.consensus(letters, auto_min_support(n_runs), n_threads)
+            cscore = ens.score(cons)[1]
+            for f, o in enumerate(outs):
+                o["consensus_score"] = float(cscore[f])
+                if o["consensus_score"] > o["scores"][o["best_k"]]:
+                    chosen[f] = cons[f]
+                    o["use_consensus"] = True
+        ask = [(f, o["best_k"]) for f, o in enumerate(outs) if not o["use_consensus"]]
+        if ask and rerun_refined is not None:
+            refined = [[bytes(r.encode() if isinstance(r, str) else r) for r in rows] for rows in rerun_refined(ask)]
+            if len(refined) != len(ask):
+                raise KalignAmdError("rerun_refined returned %d alignments for %d families" % (len(refined), len(ask)))
+            rows = [None] * F
+            for (f, _), r in zip(ask, refined):
+                rows[f] = r
+            rscore = ens.score(rows)[1]
+            for (f, k), r in zip(ask, refined):
+                outs[f]["refined_score"] = float(rscore[f])
+                if outs[f]["refined_score"] > outs[f]["scores"][k]:
+                    chosen[f] = r
+                    outs[f]["refined"] = True
+        conf = ens.confidence(chosen)
+        stats = ens.stats()
+        for f, o in enumerate(outs):
+            o["rows"] = chosen[f]
+            o["residue_confidence"], o["column_confidence"] = conf[f]
+            o["stats"] = stats
+        return outs
+    finally:
+        ens.close()
+
+
 def consensus_from_poar(ctx, letters, poar_path, min_support):
     """kalign_consensus_from_poar (ensemble.c:500-543): the consensus alignment at min_support and its confidences from a
     saved POAR table, no members at hand.  letters: the sequences, in the order of the run that wrote the table.
