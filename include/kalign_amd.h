@@ -662,7 +662,7 @@ int  ka_cmp_score_batch(ka_cmp* h, int n_tests, const uint8_t* const* test_rows,
                         long long* counts_out, double* scores_out, float* sp_out);
 int  ka_cmp_stats(ka_cmp* h, double* stats_out);
 
-/* ---- scoring a batch of families, each against its own reference alignment (ka_cmp_fam.hip, ka_cmp_fam.cpp) ------------------
+/* ---- scoring a batch of families, each against its own reference alignment (ka_cmp.hip, ka_cmp.cpp, ka_cmp_fam.cpp) --------
  * What ka_cmp_create + ka_cmp_set_mask + ka_cmp_score return for every family alone -- twelve counts, five doubles and the
  * float SP score, bit for bit -- for all families of a batch in a number of launches that does not grow with the batch,
  * with one copy back and one synchronisation per score call.  The references stay on the device: the loop of a benchmark

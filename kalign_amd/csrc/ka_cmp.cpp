@@ -1,113 +1,230 @@
-// ka_cmp.cpp -- host side of scoring alignments against a reference alignment (kalign_msa_compare*, lib/src/msa_cmp.c):
-// the ka_cmp handle of the C ABI.
+// ka_cmp.cpp -- host side of scoring alignments against reference alignments (kalign_msa_compare*, lib/src/msa_cmp.c):
+// the core both handles of the C ABI stand on, and the ka_cmp handle (K test alignments of one reference).  The ka_cmp_fam
+// handle (a batch of families, one test each) is ka_cmp_fam.cpp.
 //
-// The reference alignment's position maps and per-column residue counts are built once (ka_cmp_create); each test
-// alignment gets its own maps, then the pair walk and the TC pass (ka_cmp.hip).  The device returns exact integer counts;
-// the final doubles are computed on the host with the reference's expressions, in its order (ka_cmp_finish, ka_cmp.h).
+// The core holds the references of a handle -- their position maps, per-column residue counts and scored columns, built
+// once -- and scores a call's jobs (ka_cmp.h: one test alignment against one reference) in one sequence: the rows
+// uploaded, the test maps, the pair walk (one launch per LDS class in use), the TC pass, every job's eight sums back in
+// one copy behind one synchronisation (ka_cmp.hip).  The device returns exact integer counts; the final doubles are
+// computed on the host with the reference's expressions, in its order (ka_cmp_finish, ka_cmp.h).
+//
+// A handle's front checks its arguments on the host before anything is launched and says how its rows are laid out; a
+// refused call launches nothing and leaves the handle usable.
 //
 // Unlike the reference, the two alignments must hold the same sequences: numseq rows each, row s with lens[s] letters
 // (the reference reads out of bounds otherwise).  Two sequences at least.
-#include "ka_ctx.h"
-#include "ka_cmp.h"
-#include "ka_msa.h"
+#include "ka_cmp_core.h"
 
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
 
 namespace {
 
-constexpr int kGroup = 32;         // test alignments per device pass of ka_cmp_score_batch
+constexpr int kGroup = 32;         // test alignments per device pass of ka_cmp_score_batch: the bound on device memory
 
-} // namespace
-
-struct ka_cmp {
-        int device = 0;
-        hipStream_t stream = nullptr;
-        KaSeqSet q;
-        int WR = 0, WRp = 0;
-        DevBuf<int> dSeqOf, dColR, dColCnt, dMask, dColT, dTWp;
-        DevBuf<int16_t> dResR, dResT;
-        DevBuf<uint8_t> dRows, dScored;
-        DevBuf<long long> dTResOff, dSlab, dSums;
-        DevBuf<unsigned long long> dTc;
-        hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-        double st[KA_CMP_STATS] = {};
-
-        ~ka_cmp()
-        {
-                for (auto& e : ev)
-                        if (e) (void)hipEventDestroy(e);
-                q.release();
-                dSeqOf.release(); dColR.release(); dColCnt.release(); dMask.release();
-                dColT.release(); dTWp.release(); dResR.release(); dResT.release(); dRows.release(); dScored.release();
-                dTResOff.release(); dSlab.release(); dSums.release(); dTc.release();
-        }
-
-        float ms(int a, int b) { float m = 0.0f; (void)hipEventElapsedTime(&m, ev[a], ev[b]); return m; }
-
-        int score(int K, const uint8_t* const* rows, const long long* strides, const int* alnlens, long long* counts, double* scores, float* sp);
-};
-
-// K <= kGroup test alignments, checked by the caller
-int ka_cmp::score(int K, const uint8_t* const* rows, const long long* strides, const int* alnlens, long long* counts, double* scores, float* sp)
+// the LDS the walk needs for a job: TJ rows of both maps, as many as the budget holds, one at least; *tj = 0 when one row
+// pair does not fit a CU
+size_t walk_lds(int N, int WRp, int WTp, int* tj)
 {
-        const int N = q.N, T = q.T;
-        std::vector<long long> rowOff(K + 1, 0), resOff(K + 1, 0);
-        std::vector<int> wp(K);
-        int maxWTp = 0;
-        for (int k = 0; k < K; k++) {
-                wp[k] = ka_cmp_pad(alnlens[k]);
-                maxWTp = std::max(maxWTp, wp[k]);
-                rowOff[k + 1] = rowOff[k] + (long long)N * alnlens[k];
-                resOff[k + 1] = resOff[k] + (long long)N * wp[k];
-        }
-        // the walk stages TJ rows of both maps in LDS: as many as the budget holds, one at least
-        const size_t rowBytes = (size_t)(WRp + maxWTp) * sizeof(int16_t);
+        const size_t rowBytes = (size_t)(WRp + WTp) * sizeof(int16_t);
         int TJ = (int)std::min<size_t>(KA_CMP_TJ, KA_CMP_LDS / rowBytes);
         TJ = std::max(1, std::min(TJ, N));
         const size_t lds = (size_t)TJ * rowBytes;
-        if (lds > KA_CMP_MAX_LDS - 1024)
-                return fail("ka_cmp_score: reference width " + std::to_string(WR) + " and test width " + std::to_string(maxWTp) +
-                            " together exceed the LDS of one CU (one row of each is staged)");
-        const int nTI = (N + KA_CMP_TI - 1) / KA_CMP_TI, nTJ = (N + TJ - 1) / TJ;
-        const int nTiles = nTI * nTJ;
-        const int gridX = std::max(1, std::min(nTiles, (KA_CMP_GRID + K - 1) / K));
-        if (dRows.alloc((size_t)rowOff[K]) || dColT.alloc((size_t)K * std::max(T, 1)) || dResT.alloc((size_t)resOff[K]) ||
-            dTResOff.alloc(K) || dTWp.alloc(K) || dSlab.alloc((size_t)K * gridX * KA_CMP_WALK) || dSums.alloc((size_t)K * KA_CMP_WALK) ||
-            dTc.alloc((size_t)2 * K))
-                return fail("ka_cmp_score: out of device memory");
-        for (int k = 0; k < K; k++)
-                if (ka_msa_upload_rows(q, dRows.p + rowOff[k], rows[k], strides[k], alnlens[k], stream)) return KA_FAIL;
-        HIPCHK(hipMemcpyAsync(dTResOff.p, resOff.data(), sizeof(long long) * K, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(dTWp.p, wp.data(), sizeof(int) * K, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemsetAsync(dTc.p, 0, sizeof(unsigned long long) * 2 * K, stream));
+        *tj = lds > KA_CMP_MAX_LDS - 1024 ? 0 : TJ;
+        return lds;
+}
+
+int lds_class(size_t lds)
+{
+        int c = 0;
+        while (c < KA_CMP_CLASSES - 1 && lds > ((size_t)KA_CMP_LDS >> (KA_CMP_CLASSES - 2 - c))) c++;
+        return c;
+}
+
+// "<who>" or "<who>: <item> <k>"
+std::string at(const char* who, const char* item, int k)
+{
+        return item ? std::string(who) + ": " + item + " " + std::to_string(k) : std::string(who);
+}
+
+} // namespace
+
+KaCmpCore::~KaCmpCore()
+{
+        for (auto& e : ev)
+                if (e) (void)hipEventDestroy(e);
+        dRefs.release(); dJobs.release(); dRefFirst.release(); dJobFirst.release(); dOffs.release(); dLens.release(); dSeqOf.release();
+        dColR.release(); dColT.release(); dColCnt.release(); dMasks.release(); dResR.release(); dResT.release(); dRows.release();
+        dScored.release(); dFrac.release(); dMaskOff.release(); dSums.release();
+}
+
+int KaCmpCore::attach(ka_ctx* ctx) { return ka_ctx_device_stream(ctx, &device, &stream); }
+
+void KaCmpCore::close()
+{
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream);
+}
+
+KaCmpTab KaCmpCore::tab() const
+{
+        KaCmpTab a{};
+        const int nRef = (int)refs.size();
+        a.nRef = nRef; a.S = S; a.cols = cols;
+        a.refs = dRefs.p; a.refSeq = dRefFirst.p; a.refCol = dRefFirst.p + nRef + 1;
+        a.offs = dOffs.p; a.lens = dLens.p; a.seqOf = dSeqOf.p; a.rows = dRows.p;
+        a.colR = dColR.p; a.colT = dColT.p; a.resR = dResR.p; a.resT = dResT.p;
+        a.colCnt = dColCnt.p; a.scored = dScored.p; a.sums = dSums.p;
+        return a;
+}
+
+int KaCmpCore::create(const char* who, const char* item, int nRef, const int* first, const int* l, const int* widths, int pad, const KaCmpUpload& upload)
+{
+        const std::string me(who);
+        S = first[nRef];
+        lens.assign(l, l + S);
+        offs.resize(S + 1);
+        int t = 0;
+        for (int s = 0; s < S; s++) { offs[s] = t; t += l[s]; }
+        offs[S] = T = t;
+        refs.assign(nRef, KaCmpJob{});
+        std::vector<int> refFirst((size_t)2 * (nRef + 1)), seqOf((size_t)std::max(T, 1), 0);
+        long long rowOff = 0, resOff = 0;
+        int col = 0;
+        for (int f = 0; f < nRef; f++) {
+                KaCmpJob& d = refs[f];
+                d.firstSeq = first[f]; d.firstRes = offs[first[f]]; d.firstCol = col;
+                d.N = first[f + 1] - first[f];
+                d.r.W = widths[f]; d.r.Wp = ka_cmp_pad(widths[f]); d.r.stride = widths[f] + pad; d.r.rowOff = rowOff; d.r.resOff = resOff;
+                if ((size_t)d.r.Wp * 2 * sizeof(int16_t) > KA_CMP_MAX_LDS - 1024)
+                        return fail(at(who, item, f) + ": reference width " + std::to_string(d.r.W) +
+                                    " exceeds the LDS of one CU (a row of each alignment is staged)");
+                for (int s = 0; s < d.N; s++) std::fill_n(seqOf.begin() + offs[d.firstSeq + s], l[d.firstSeq + s], s);
+                refFirst[f] = first[f];
+                refFirst[nRef + 1 + f] = col;
+                col += d.r.W;
+                rowOff += d.N * d.r.stride;
+                resOff += (long long)d.N * d.r.Wp;
+        }
+        refFirst[nRef] = S;
+        refFirst[2 * nRef + 1] = cols = col;
+        HIPCHK(hipSetDevice(device));
+        for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+        if (dRefs.alloc(nRef) || dRefFirst.alloc(refFirst.size()) || dOffs.alloc(S + 1) || dLens.alloc(S) || dSeqOf.alloc(seqOf.size()) ||
+            dColR.alloc(seqOf.size()) || dResR.alloc((size_t)resOff) || dColCnt.alloc(col) || dScored.alloc(col) || dRows.alloc((size_t)rowOff) ||
+            dFrac.alloc(nRef) || dMaskOff.alloc(nRef))
+                return fail(me + ": out of device memory");
+        HIPCHK(hipMemcpyAsync(dRefs.p, refs.data(), sizeof(KaCmpJob) * nRef, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dRefFirst.p, refFirst.data(), sizeof(int) * refFirst.size(), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dOffs.p, offs.data(), sizeof(int) * (S + 1), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dLens.p, lens.data(), sizeof(int) * S, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dSeqOf.p, seqOf.data(), sizeof(int) * seqOf.size(), hipMemcpyHostToDevice, stream));
+        if (upload(dRows.p, stream)) return KA_FAIL;
         HIPCHK(hipEventRecord(ev[0], stream));
-        for (int k = 0; k < K; k++)
-                ka_msa_launch_maps(dRows.p + rowOff[k], alnlens[k], alnlens[k], wp[k], q, dColT.p + (long long)k * T, dResT.p + resOff[k], stream);
+        const KaCmpTab a = tab();                                // (no fractions, no masks: every column is scored)
+        ka_cmp_run_maps(a, 0, stream);
+        ka_cmp_run_col_count(a, stream);
+        ka_cmp_run_mask(a, stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev[1], stream));
-        KaCmpArgs a{};
-        a.N = N; a.T = T; a.offs = q.dOffs; a.seqOf = dSeqOf.p;
-        a.colR = dColR.p; a.resR = dResR.p; a.WR = WR; a.WRp = WRp; a.scored = dScored.p;
-        a.colT = dColT.p; a.resT = dResT.p; a.tResOff = dTResOff.p; a.tWp = dTWp.p; a.maxWTp = maxWTp;
-        a.TJ = TJ; a.nTI = nTI; a.nTJ = nTJ;
-        a.slab = dSlab.p; a.sums = dSums.p; a.colCnt = dColCnt.p; a.tc = dTc.p;
-        if (ka_cmp_launch_walk(a, K, gridX, lds, stream)) return fail("ka_cmp_score: the walk's LDS (" + std::to_string(lds) + " bytes) was refused");
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev[2], stream));
-        ka_cmp_launch_tc(a, K, stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev[3], stream));
-        std::vector<long long> sums((size_t)K * KA_CMP_WALK);
-        std::vector<unsigned long long> tc((size_t)2 * K);
-        HIPCHK(hipMemcpyAsync(sums.data(), dSums.p, sizeof(long long) * sums.size(), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemcpyAsync(tc.data(), dTc.p, sizeof(unsigned long long) * tc.size(), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        st[1] += ms(0, 1); st[2] += ms(1, 2); st[3] += ms(2, 3);
-        for (int k = 0; k < K; k++)
-                ka_cmp_finish(&sums[(size_t)k * KA_CMP_WALK], (long long)tc[2 * k], (long long)tc[2 * k + 1], N, T,
-                              counts ? counts + (size_t)k * 12 : nullptr, scores ? scores + (size_t)k * 5 : nullptr, sp ? sp + k : nullptr);
+        HIPCHK(hipStreamSynchronize(stream));                    // (refFirst and seqOf are read until here)
+        st[0] = ms(0, 1);
         return KA_OK;
 }
+
+int KaCmpCore::set_rule(const char* who, const float* frac, const int* masks, const long long* maskOff, long long nMask)
+{
+        const int nRef = (int)refs.size();
+        HIPCHK(hipSetDevice(device));
+        if (nMask && dMasks.alloc((size_t)nMask)) return fail(std::string(who) + ": out of device memory");
+        if (nMask) HIPCHK(hipMemcpyAsync(dMasks.p, masks, sizeof(int) * (size_t)nMask, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dFrac.p, frac, sizeof(float) * nRef, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dMaskOff.p, maskOff, sizeof(long long) * nRef, hipMemcpyHostToDevice, stream));
+        KaCmpTab a = tab();
+        a.frac = dFrac.p; a.masks = dMasks.p; a.maskOff = dMaskOff.p;
+        ka_cmp_run_mask(a, stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));                    // (the caller's arrays are read until here)
+        return KA_OK;
+}
+
+int KaCmpCore::score(const char* who, const char* item, int nJob, const int* refOf, const int* widths, int pad, const KaCmpUpload& upload,
+                     long long* counts, double* scores, float* sp)
+{
+        const std::string me(who);
+        // every job's test side, tile geometry and LDS class, and the ascending tables of what the call numbers: test
+        // rows, job columns and the tiles of every LDS class
+        enum { ROWS = 0, COLS = 1, TILES = 2, TABLES = TILES + KA_CMP_CLASSES };
+        static const char* const what[3] = { "rows", "columns", "tiles" };
+        std::vector<KaCmpJob> jobs(nJob);
+        std::vector<int> first((size_t)TABLES * (nJob + 1), 0);
+        size_t classLds[KA_CMP_CLASSES] = {};
+        long long rowOff = 0, resOff = 0, colOff = 0;
+        for (int k = 0; k < nJob; k++) {
+                KaCmpJob& d = jobs[k] = refs[refOf ? refOf[k] : k];
+                d.t.W = widths[k]; d.t.Wp = ka_cmp_pad(widths[k]); d.t.stride = widths[k] + pad; d.t.rowOff = rowOff; d.t.resOff = resOff;
+                d.colOff = colOff - d.firstRes;
+                const size_t lds = walk_lds(d.N, d.r.Wp, d.t.Wp, &d.TJ);
+                if (!d.TJ)
+                        return fail(at(who, item, k) + ": reference width " + std::to_string(d.r.W) + " and test width " + std::to_string(d.t.Wp) +
+                                    " together exceed the LDS of one CU (one row of each is staged)");
+                d.nTJ = (d.N + d.TJ - 1) / d.TJ;
+                const int nTI = (d.N + KA_CMP_TI - 1) / KA_CMP_TI, cls = lds_class(lds);
+                classLds[cls] = std::max(classLds[cls], lds);
+                for (int c = 0; c < TABLES; c++) {
+                        const long long n = c == ROWS ? d.N : c == COLS ? d.r.W : c - TILES == cls ? (long long)nTI * d.nTJ : 0;
+                        const long long next = first[(size_t)c * (nJob + 1) + k] + n;
+                        if (next > INT32_MAX) return fail(me + ": more than 2^31 - 1 " + what[std::min<int>(c, TILES)] + " in the batch");
+                        first[(size_t)c * (nJob + 1) + k + 1] = (int)next;
+                }
+                rowOff += d.N * d.t.stride;
+                resOff += (long long)d.N * d.t.Wp;
+                colOff += offs[d.firstSeq + d.N] - d.firstRes;
+        }
+        std::vector<unsigned long long> sums((size_t)nJob * KA_CMP_SUMS);
+        HIPCHK(hipSetDevice(device));
+        if (dRows.alloc((size_t)rowOff) || dResT.alloc((size_t)resOff) || dColT.alloc((size_t)std::max<long long>(colOff, 1)) || dJobs.alloc(nJob) ||
+            dJobFirst.alloc(first.size()) || dSums.alloc(sums.size()))
+                return fail(me + ": out of device memory");
+        HIPCHK(hipMemcpyAsync(dJobs.p, jobs.data(), sizeof(KaCmpJob) * nJob, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dJobFirst.p, first.data(), sizeof(int) * first.size(), hipMemcpyHostToDevice, stream));
+        if (upload(dRows.p, stream)) return KA_FAIL;
+        HIPCHK(hipMemsetAsync(dSums.p, 0, sizeof(unsigned long long) * sums.size(), stream));
+        HIPCHK(hipEventRecord(ev[0], stream));
+        KaCmpTab a = tab();
+        a.nJob = nJob; a.jobs = dJobs.p;
+        a.jobRow = dJobFirst.p + (size_t)ROWS * (nJob + 1); a.jobRows = first[(size_t)ROWS * (nJob + 1) + nJob];
+        a.jobCol = dJobFirst.p + (size_t)COLS * (nJob + 1); a.jobCols = first[(size_t)COLS * (nJob + 1) + nJob];
+        ka_cmp_run_maps(a, 1, stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev[1], stream));
+        for (int c = 0; c < KA_CMP_CLASSES; c++) {
+                const size_t at0 = (size_t)(TILES + c) * (nJob + 1);
+                if (!first[at0 + nJob]) continue;
+                if (ka_cmp_run_walk(a, dJobFirst.p + at0, first[at0 + nJob], classLds[c], stream))
+                        return fail(me + ": the walk's LDS (" + std::to_string(classLds[c]) + " bytes) was refused");
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev[2], stream));
+        ka_cmp_run_tc(a, stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev[3], stream));
+        HIPCHK(hipMemcpyAsync(sums.data(), dSums.p, sizeof(unsigned long long) * sums.size(), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        st[1] += ms(0, 1); st[2] += ms(1, 2); st[3] += ms(2, 3);
+        for (int k = 0; k < nJob; k++) {
+                const KaCmpJob& d = jobs[k];
+                const long long* w = (const long long*)&sums[(size_t)k * KA_CMP_SUMS];
+                ka_cmp_finish(w, w[KA_CMP_WALK], w[KA_CMP_WALK + 1], d.N, offs[d.firstSeq + d.N] - d.firstRes,
+                              counts ? counts + (size_t)k * 12 : nullptr, scores ? scores + (size_t)k * 5 : nullptr, sp ? sp + k : nullptr);
+        }
+        return KA_OK;
+}
+
+// ---- one reference, K tests: rows `row_stride` apart on the host, uploaded back to back ----
+struct ka_cmp {
+        KaCmpCore core;
+        KaSeqSet q;                // (host side only: the row checks and the strided upload)
+};
 
 extern "C" int ka_cmp_create(ka_ctx* ctx, int numseq, const int* lens, const uint8_t* ref_rows, long long row_stride, int alnlen, ka_cmp** out)
 {
@@ -115,32 +232,16 @@ extern "C" int ka_cmp_create(ka_ctx* ctx, int numseq, const int* lens, const uin
         *out = nullptr;
         if (numseq < 2) return fail("ka_cmp_create: " + std::to_string(numseq) + " sequences; a comparison needs two at least");
         std::unique_ptr<ka_cmp> h(new ka_cmp);
-        if (ka_ctx_device_stream(ctx, &h->device, &h->stream)) return fail("ka_cmp_create: bad context");
-        HIPCHK(hipSetDevice(h->device));
+        if (h->core.attach(ctx)) return fail("ka_cmp_create: bad context");
         const std::string why = "the position maps hold at most " + std::to_string(KA_CMP_MAX_RES);
-        if (h->q.init("ka_cmp_create", numseq, lens, KA_CMP_MAX_RES, why.c_str())) return KA_FAIL;
+        if (h->q.set("ka_cmp_create", numseq, lens, KA_CMP_MAX_RES, why.c_str())) return KA_FAIL;
         if (ka_msa_check_rows("ka_cmp_create", h->q, ref_rows, row_stride, alnlen)) return KA_FAIL;
-        h->WR = alnlen;
-        h->WRp = ka_cmp_pad(alnlen);
-        if ((size_t)h->WRp * 2 * sizeof(int16_t) > KA_CMP_MAX_LDS - 1024)
-                return fail("ka_cmp_create: reference width " + std::to_string(alnlen) + " exceeds the LDS of one CU (a row of each alignment is staged)");
-        const int T = h->q.T;
-        for (auto& e : h->ev) HIPCHK(hipEventCreate(&e));
-        std::vector<int> seqOf((size_t)std::max(T, 1), 0);
-        for (int s = 0; s < numseq; s++) std::fill_n(seqOf.begin() + h->q.offs[s], lens[s], s);
-        if (h->dSeqOf.alloc(seqOf.size()) || h->dColR.alloc((size_t)std::max(T, 1)) ||
-            h->dResR.alloc((size_t)numseq * h->WRp) || h->dColCnt.alloc(alnlen) || h->dScored.alloc(alnlen) || h->dRows.alloc((size_t)numseq * alnlen))
-                return fail("ka_cmp_create: out of device memory");
-        HIPCHK(hipMemcpyAsync(h->dSeqOf.p, seqOf.data(), sizeof(int) * seqOf.size(), hipMemcpyHostToDevice, h->stream));
-        if (ka_msa_upload_rows(h->q, h->dRows.p, ref_rows, row_stride, alnlen, h->stream)) return KA_FAIL;
-        HIPCHK(hipEventRecord(h->ev[0], h->stream));
-        ka_msa_launch_maps(h->dRows.p, alnlen, alnlen, h->WRp, h->q, h->dColR.p, h->dResR.p, h->stream);
-        ka_cmp_launch_col_count(h->dResR.p, alnlen, h->WRp, numseq, h->dColCnt.p, h->stream);
-        ka_cmp_launch_mask(h->dColCnt.p, alnlen, numseq, -1.0f, nullptr, h->dScored.p, h->stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(h->ev[1], h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        h->st[0] = h->ms(0, 1);
+        const int first[2] = { 0, numseq };
+        const KaSeqSet& q = h->q;
+        if (h->core.create("ka_cmp_create", nullptr, 1, first, lens, &alnlen, 0, [&](uint8_t* dst, hipStream_t s) {
+                    return ka_msa_upload_rows(q, dst, ref_rows, row_stride, alnlen, s);
+            }))
+                return KA_FAIL;
         *out = h.release();
         return KA_OK;
 }
@@ -148,25 +249,18 @@ extern "C" int ka_cmp_create(ka_ctx* ctx, int numseq, const int* lens, const uin
 extern "C" void ka_cmp_destroy(ka_cmp* h)
 {
         if (!h) return;
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
+        h->core.close();
         delete h;
 }
 
 extern "C" int ka_cmp_set_mask(ka_cmp* h, float max_gap_frac, const int* mask, int n_cols)
 {
         if (!h) return fail("ka_cmp_set_mask: bad arguments");
-        if (mask && n_cols != h->WR)
-                return fail("ka_cmp_set_mask: mask length " + std::to_string(n_cols) + " != reference alignment length " + std::to_string(h->WR));
-        HIPCHK(hipSetDevice(h->device));
-        if (mask) {
-                if (h->dMask.alloc(h->WR)) return fail("ka_cmp_set_mask: out of device memory");
-                HIPCHK(hipMemcpyAsync(h->dMask.p, mask, sizeof(int) * h->WR, hipMemcpyHostToDevice, h->stream));
-        }
-        ka_cmp_launch_mask(h->dColCnt.p, h->WR, h->q.N, max_gap_frac, mask ? h->dMask.p : nullptr, h->dScored.p, h->stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return KA_OK;
+        const int WR = h->core.refs[0].r.W;
+        if (mask && n_cols != WR)
+                return fail("ka_cmp_set_mask: mask length " + std::to_string(n_cols) + " != reference alignment length " + std::to_string(WR));
+        const long long off = mask ? 0 : -1;
+        return h->core.set_rule("ka_cmp_set_mask", &max_gap_frac, mask, &off, mask ? WR : 0);
 }
 
 extern "C" int ka_cmp_score_batch(ka_cmp* h, int n_tests, const uint8_t* const* test_rows, const long long* row_strides, const int* alnlens,
@@ -177,12 +271,18 @@ extern "C" int ka_cmp_score_batch(ka_cmp* h, int n_tests, const uint8_t* const* 
                 const std::string who = "ka_cmp_score: test " + std::to_string(k);
                 if (ka_msa_check_rows(who.c_str(), h->q, test_rows[k], row_strides[k], alnlens[k])) return KA_FAIL;
         }
-        HIPCHK(hipSetDevice(h->device));
-        h->st[1] = h->st[2] = h->st[3] = 0.0;
+        std::fill_n(h->core.st + 1, KA_CMP_STATS - 1, 0.0);
+        const std::vector<int> refOf(kGroup, 0);
+        const KaSeqSet& q = h->q;
         for (int k0 = 0; k0 < n_tests; k0 += kGroup) {
                 const int K = std::min(kGroup, n_tests - k0);
-                if (h->score(K, test_rows + k0, row_strides + k0, alnlens + k0, counts_out ? counts_out + (size_t)k0 * 12 : nullptr,
-                             scores_out ? scores_out + (size_t)k0 * 5 : nullptr, sp_out ? sp_out + k0 : nullptr))
+                auto upload = [&](uint8_t* dst, hipStream_t s) {
+                        for (int k = k0; k < k0 + K; dst += (long long)q.N * alnlens[k], k++)
+                                if (ka_msa_upload_rows(q, dst, test_rows[k], row_strides[k], alnlens[k], s)) return (int)KA_FAIL;
+                        return (int)KA_OK;
+                };
+                if (h->core.score("ka_cmp_score", nullptr, K, refOf.data(), alnlens + k0, 0, upload, counts_out ? counts_out + (size_t)k0 * 12 : nullptr,
+                                  scores_out ? scores_out + (size_t)k0 * 5 : nullptr, sp_out ? sp_out + k0 : nullptr))
                         return KA_FAIL;
         }
         return KA_OK;
@@ -196,6 +296,6 @@ extern "C" int ka_cmp_score(ka_cmp* h, const uint8_t* test_rows, long long row_s
 extern "C" int ka_cmp_stats(ka_cmp* h, double* stats_out)
 {
         if (!h) return fail("ka_cmp_stats: bad arguments");
-        if (stats_out) std::copy_n(h->st, KA_CMP_STATS, stats_out);
+        if (stats_out) std::copy_n(h->core.st, KA_CMP_STATS, stats_out);
         return KA_OK;
 }

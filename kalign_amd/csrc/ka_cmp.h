@@ -1,17 +1,20 @@
-// ka_cmp.h -- scoring an alignment against a reference alignment (ka_cmp.hip kernels, ka_cmp.cpp host side): what the
-// two units share.
+// ka_cmp.h -- scoring alignments against reference alignments (ka_cmp.hip kernels, ka_cmp.cpp host side): what the two
+// units share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #define KA_CMP_MAX_RES 32767       // residue index in an int16 map entry
-#define KA_CMP_WALK 6              // the walk's counters per test: see KaCmpArgs
+#define KA_CMP_WALK 6              // the walk's counters per job: see the enum below
+#define KA_CMP_SUMS 8              // a job's sums: the walk's six counters, tc_correct, tc_total
 #define KA_CMP_STATS 4             // ka_cmp_stats: see include/kalign_amd.h
 #define KA_CMP_TI 16               // sequences i per tile of the pair walk
 #define KA_CMP_TJ 32               // at most this many sequences j per tile (fewer when their rows do not fit the LDS budget)
 #define KA_CMP_LDS 65536           // LDS budget of a walk workgroup for the staged rows (more only when one j row needs it)
 #define KA_CMP_MAX_LDS 163840      // gfx950: LDS of one CU
-#define KA_CMP_GRID 1024           // workgroups of the walk per test at most (each then walks several tiles)
+#define KA_CMP_WALK_WGS 2048       // workgroups of a walk launch at most (8 per CU): more tiles are strided over
+#define KA_CMP_CLASSES 4           // walk launches by LDS need: up to 16, 32 and 64 KiB (KA_CMP_LDS), and what is larger
+#define KA_CMP_TCCHUNK 8           // consecutive job columns per wave of the TC pass at most
 
 // res maps are stored with a row stride padded to 8 entries (16 bytes): a tile's rows copy as whole uint4s
 static inline int ka_cmp_pad(int w) { return (w + 7) & ~7; }
@@ -27,35 +30,60 @@ enum {
         KA_CMP_COMMON_SCORED = 5,  // [pR >= 0 && pR == pT && scored[colR]]
 };
 
-struct KaCmpArgs {
-        int N, T;                  // sequences, residues
-        const int* offs;           // [N + 1] first residue of sequence s in the flat numbering (offs[N] = T)
-        const int* seqOf;          // [T] sequence of a flat residue
-        const int* colR;           // [T] reference column of residue e
-        const int16_t* resR;       // [N][WRp] residue of s at reference column c, or -1
-        int WR, WRp;
-        const uint8_t* scored;     // [WR] column mask of the reference
-        const int* colT;           // test k at k * T
-        const int16_t* resT;       // test k at tResOff[k]: [N][tWp[k]]
-        const long long* tResOff;  // [K]
-        const int* tWp;            // [K]
-        int maxWTp;                // widest test (LDS layout)
-        int TJ, nTI, nTJ;          // tile geometry: KA_CMP_TI x TJ sequences
-        long long* slab;           // [K][gridDim.x][KA_CMP_WALK]
-        long long* sums;           // [K][KA_CMP_WALK]
-        const int* colCnt;         // [WR] residues in reference column c
-        unsigned long long* tc;    // [K][2] tc_correct, tc_total
+// ---- the job table ----
+// A handle holds one reference alignment or more (ka_cmp: one; ka_cmp_fam: one per family).  Their sequences, residues
+// and columns are numbered flat over the handle, references in order.  A JOB is one test alignment scored against one
+// reference: a score call of ka_cmp_fam has one job per family, a group of ka_cmp_score_batch has K jobs that share the
+// one reference.  What counts the call's items -- test rows, job columns, tiles -- is numbered flat over the jobs of the
+// call.  A kernel finds the reference or job of such a flat index by a search of an ascending first-index table
+// (ka_fam_find, ka_msa.h).
+struct KaCmpSide {                 // one alignment
+        int W, Wp;                 // columns; res row stride (ka_cmp_pad)
+        long long stride;          // bytes from a row to the next in the uploaded rows
+        long long rowOff;          // first byte of its rows in the uploaded rows
+        long long resOff;          // first entry of its res map [N][Wp]
+};
+
+struct KaCmpJob {
+        int firstSeq, firstRes, firstCol;      // its reference: first sequence, flat residue and flat column in the handle
+        int N;
+        KaCmpSide r, t;                        // reference, test (a reference of the handle's table: r alone)
+        long long colOff;                      // the test column of flat residue e of the reference is colT[colOff + e]
+        int TJ, nTJ;                           // tile geometry of the walk: KA_CMP_TI x TJ sequences, nTJ j-tiles
+};
+
+struct KaCmpTab {
+        int nRef, nJob;                        // references of the handle, jobs of the call
+        int S, cols;                           // sequences and columns of the references
+        int jobRows, jobCols;                  // test rows and job columns (a job has its reference's columns) of the call
+        const KaCmpJob* refs;                  // [nRef]
+        const KaCmpJob* jobs;                  // [nJob]
+        const int* refSeq; const int* refCol;  // [nRef + 1] first sequence / column of a reference
+        const int* jobRow; const int* jobCol;  // [nJob + 1] first test row / job column of a job
+        const int* offs;                       // [S + 1] first flat residue of a sequence
+        const int* lens;                       // [S]
+        const int* seqOf;                      // [T] sequence of a flat residue, counted from its reference's first
+        const uint8_t* rows;                   // uploaded rows of the side being mapped
+        int* colR; int* colT;                  // column (in its own alignment) of a residue: colR[e], colT[job.colOff + e]
+        int16_t* resR; int16_t* resT;          // res maps, at r.resOff / t.resOff
+        int* colCnt;                           // [cols] residues in a reference column
+        uint8_t* scored;                       // [cols]
+        const float* frac;                     // [nRef] max_gap_frac
+        const int* masks; const long long* maskOff;   // reference f's mask at masks + maskOff[f], or maskOff[f] < 0
+        unsigned long long* sums;              // [nJob][KA_CMP_SUMS]
 };
 
 // ka_cmp.hip
-void ka_cmp_launch_col_count(const int16_t* res, int W, int Wp, int N, int* colCnt, hipStream_t s);
-void ka_cmp_launch_mask(const int* colCnt, int W, int N, float maxGapFrac, const int* mask, uint8_t* scored, hipStream_t s);
-int ka_cmp_launch_walk(const KaCmpArgs& a, int K, int gridX, size_t lds, hipStream_t s);
-void ka_cmp_launch_tc(const KaCmpArgs& a, int K, hipStream_t s);
+void ka_cmp_run_maps(const KaCmpTab& a, int test, hipStream_t s);     // the references' maps (test 0) or the jobs' test maps
+void ka_cmp_run_col_count(const KaCmpTab& a, hipStream_t s);
+void ka_cmp_run_mask(const KaCmpTab& a, hipStream_t s);
+// the tiles first[k] .. first[k + 1] - 1 (device, [nJob + 1]) of the jobs of one LDS class
+int ka_cmp_run_walk(const KaCmpTab& a, const int* first, int nTiles, size_t lds, hipStream_t s);
+void ka_cmp_run_tc(const KaCmpTab& a, hipStream_t s);
 
 // the doubles of one scored alignment from its exact counts, with the reference's expressions in its order: w = the walk's
 // six sums, N sequences with T residues in all.  counts[12], scores[5] and sp (each optional) as ka_cmp_score hands them out.
-// The one place these expressions live: ka_cmp_score and ka_cmp_fam_score both end here.
+// The one place these expressions live: every job ends here.
 static inline void ka_cmp_finish(const long long* w, long long tcCorrect, long long tcTotal, int N, long long T, long long* counts,
                                  double* scores, float* sp)
 {
@@ -88,50 +116,3 @@ static inline void ka_cmp_finish(const long long* w, long long tcCorrect, long l
                 scores[0] = recall; scores[1] = precision; scores[2] = f1; scores[3] = tcv; scores[4] = spd;
         }
 }
-
-// ---- a batch of families, each with its own reference and test alignment (ka_cmp_fam.hip kernels, ka_cmp_fam.cpp host side) ----
-// Sequences, residues and reference columns are numbered flat over the batch, families in order; a family's kernels find
-// their family from such a flat index by a search of the ascending first-index tables.
-#define KA_CMPF_GRID 2048          // workgroups of a walk launch at most (8 per CU): more tiles are strided over
-#define KA_CMPF_CLASSES 4          // walk launches by LDS need: up to 16, 32 and 64 KiB (KA_CMP_LDS), and what is larger
-#define KA_CMPF_TCCHUNK 8          // consecutive flat reference columns per wave of the TC pass
-
-struct KaCmpSide {                 // one alignment of a family
-        int W, Wp;                 // columns; res row stride (ka_cmp_pad)
-        long long rowOff;          // first byte of the family's rows in the packed rows (rows W + 1 bytes apart)
-        long long resOff;          // first entry of the family's res map [N][Wp]
-};
-
-struct KaCmpFam {
-        int firstSeq, firstRes, firstCol;      // first sequence, flat residue and flat reference column of the family
-        int N;
-        KaCmpSide r, t;                        // reference, test
-        int TJ, nTJ;                           // tile geometry of the walk: KA_CMP_TI x TJ sequences, nTJ j-tiles
-};
-
-struct KaCmpFamArgs {
-        int nFam, S, cols;                     // families, sequences, flat reference columns
-        const KaCmpFam* fams;                  // [nFam]
-        const int* firstSeq;                   // [nFam + 1]
-        const int* firstCol;                   // [nFam + 1]
-        const int* offs;                       // [S + 1] first flat residue of a sequence
-        const int* lens;                       // [S]
-        const int* seqOf;                      // [T] sequence of a flat residue, counted from its family's first
-        const uint8_t* rows;                   // packed rows of the side being mapped
-        int* colR; int* colT;                  // [T] column (in its family's alignment) of a flat residue
-        int16_t* resR; int16_t* resT;          // res maps, family f at fams[f].r.resOff / .t.resOff
-        int* colCnt;                           // [cols] residues in a reference column
-        uint8_t* scored;                       // [cols]
-        const float* frac;                     // [nFam] max_gap_frac
-        const int* masks; const long long* maskOff;   // family f's mask at masks + maskOff[f], or maskOff[f] < 0
-        unsigned long long* sums;              // [nFam][KA_CMPF_SUMS]: the walk's six counters, tc_correct, tc_total
-};
-#define KA_CMPF_SUMS 8
-
-// ka_cmp_fam.hip
-void ka_cmpf_launch_maps(const KaCmpFamArgs& a, int test, hipStream_t s);
-void ka_cmpf_launch_col_count(const KaCmpFamArgs& a, hipStream_t s);
-void ka_cmpf_launch_mask(const KaCmpFamArgs& a, hipStream_t s);
-// the tiles first[f] .. first[f + 1] - 1 (device, [nFam + 1]) of the families of one LDS class
-int ka_cmpf_launch_walk(const KaCmpFamArgs& a, const int* first, int nTiles, size_t lds, hipStream_t s);
-void ka_cmpf_launch_tc(const KaCmpFamArgs& a, hipStream_t s);

@@ -2,10 +2,10 @@
 // form that takes every family of the batch in one launch (ka_ens_fam.cpp is the host side, ka_ens.h the shared tables).
 //
 // Sequences and residues are numbered flat over the batch.  A wave or workgroup finds the family of its flat index by a
-// search of an ascending first-index table (ensf_find: wave-uniform), then works with that family's geometry from its
+// search of an ascending first-index table (ka_fam_find, ka_msa.h: wave-uniform), then works with that family's geometry from its
 // KaEnsFam and the per-family entries of the member tables.
 //
-//   ensf_maps      a wave per packed row: msa_maps' ballot-prefix rank with the row's own start and width
+//   ensf_maps      a wave per packed row: msa_maps' row body (ka_msa_map_row) with the row's own start and width
 //   ensf_walk      a workgroup per (flat sequence i, chunk of KA_ENS_JCHUNK sequences j of i's family): ens_walk.  SCORE adds
 //                  into the family's sum with a 64-bit vector atomic (exact integers: the order does not matter); CONF is
 //                  ens_walk's.  COUNT takes every support level n_runs .. minSup of the family in ONE pass: the n_runs
@@ -21,18 +21,6 @@
 #define ENSF_THREADS 256
 #define ENSF_WAVES (ENSF_THREADS / 64)
 
-// the last f in [0, n) with first[f] <= x (first ascends, first[0] <= x; equal neighbours are empty ranges and are skipped)
-__device__ __forceinline__ int ensf_find(const int* first, int n, int x)
-{
-        int lo = 0, hi = n - 1;
-        while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (first[mid] <= x) lo = mid;
-                else hi = mid - 1;
-        }
-        return lo;
-}
-
 __device__ __forceinline__ int ensf_wave_sum_all(int v)
 {
 #pragma unroll
@@ -45,26 +33,11 @@ __global__ __launch_bounds__(ENSF_THREADS) void ensf_maps(KaEnsFamArgs a, const 
 {
         const int s = blockIdx.x * ENSF_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
         if (s >= a.S) return;
-        const int f = ensf_find(a.firstSeq, a.nFam, s);
+        const int f = ka_fam_find(a.firstSeq, a.nFam, s);
         const int W = Wt[f];
         if (W <= 0) return;                                      // (a skipped family of a score call)
         const int loc = s - a.firstSeq[f];
-        const uint8_t* row = rows + rowOff[f] + (long long)loc * (W + 1);
-        int16_t* rs = res + cell[f] + (long long)loc * W;
-        int* cs = col + a.offs[s];
-        const int len = a.lens[s];
-        const unsigned long long below = (1ull << lane) - 1ull;
-        int run = 0;
-        for (int cb = 0; cb < W; cb += 64) {
-                const int c = cb + lane;
-                const bool isr = c < W && ka_msa_is_residue(row[c]);
-                const unsigned long long m = __ballot(isr);
-                const int r = run + __popcll(m & below);
-                const bool put = isr && r < len;
-                if (c < W) rs[c] = put ? (int16_t)r : (int16_t)-1;
-                if (put) cs[r] = c;
-                run += __popcll(m);
-        }
+        ka_msa_map_row(rows + rowOff[f] + (long long)loc * (W + 1), W, W, a.lens[s], col + a.offs[s], res + cell[f] + (long long)loc * W, lane);
 }
 
 template <int MODE, int RM>
@@ -72,7 +45,7 @@ __global__ __launch_bounds__(ENSF_THREADS) void ensf_walk(KaEnsFamArgs a)
 {
         extern __shared__ int lds[];
         const int b = a.blk0 + (int)blockIdx.x;
-        const int f = ensf_find(a.blkFirst, a.nFam, b);
+        const int f = ka_fam_find(a.blkFirst, a.nFam, b);
         const KaEnsFam d = a.fams[f];
         const int t0 = b - a.blkFirst[f];
         const int il = t0 / d.nJC;                               // i and j inside the family
@@ -205,7 +178,7 @@ __global__ __launch_bounds__(ENSF_THREADS) void ensf_row_scan(KaEnsFamArgs a, lo
         __shared__ long long wsum[ENSF_WAVES];
         const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         const int lv = r / a.S, si = r - lv * a.S;
-        const int f = ensf_find(a.firstSeq, a.nFam, si);
+        const int f = ka_fam_find(a.firstSeq, a.nFam, si);
         const int N = a.fams[f].N;
         const long long at = (long long)lv * a.E + a.fams[f].cntFirst + (long long)(si - a.firstSeq[f]) * N;
         const int* c = a.cnt + at;
@@ -233,7 +206,7 @@ __global__ void ensf_conf_res(KaEnsFamArgs a, float* conf)
 {
         const long long tt = (long long)blockIdx.x * blockDim.x + threadIdx.x;
         if (tt >= a.xCell[a.nFam]) return;
-        const int t = (int)tt, f = ensf_find(a.xCell, a.nFam, t);
+        const int t = (int)tt, f = ka_fam_find(a.xCell, a.nFam, t);
         const int s = a.firstSeq[f] + (t - a.xCell[f]) / a.xW[f];
         const int r = a.resX[t];
         float v = 0.0f;
@@ -250,7 +223,7 @@ __global__ void ensf_conf_col(KaEnsFamArgs a, const float* conf, float* colConf)
 {
         const long long cc = (long long)blockIdx.x * blockDim.x + threadIdx.x;
         if (cc >= a.xCol[a.nFam]) return;
-        const int c = (int)cc, f = ensf_find(a.xCol, a.nFam, c);
+        const int c = (int)cc, f = ka_fam_find(a.xCol, a.nFam, c);
         const int W = a.xW[f], N = a.fams[f].N;
         const long long at = (long long)a.xCell[f] + (c - a.xCol[f]);
         double sum = 0.0;

@@ -18,6 +18,43 @@ __device__ __forceinline__ long long ka_msa_wave_sum(long long v)
         return v;
 }
 
+// the last f in [0, n) with first[f] <= x (first ascends, first[0] <= x; equal neighbours are empty ranges and are
+// skipped): how a wave or workgroup of a batched kernel finds the family (or job) of its flat index -- wave-uniform, a
+// dozen scalar loads for thousands of families
+__device__ __forceinline__ int ka_fam_find(const int* first, int n, int x)
+{
+        int lo = 0, hi = n - 1;
+        while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (first[mid] <= x) lo = mid;
+                else hi = mid - 1;
+        }
+        return lo;
+}
+
+// one row of W bytes -> both maps, by the 64 lanes of one wave: rs[c] for every c below resStride (-1 at gaps and from W
+// on), cs[r] = c for every residue, the residue rank of a column from a ballot prefix.  A step's bytes are loaded one step
+// ahead: the rank chain never waits for memory.  The host has checked the row's letter count against len; the rank guard
+// keeps the writes in place regardless.
+__device__ __forceinline__ void ka_msa_map_row(const uint8_t* row, int W, int resStride, int len, int* cs, int16_t* rs, int lane)
+{
+        const unsigned long long below = (1ull << lane) - 1ull;
+        int run = 0;
+        unsigned b = lane < W ? row[lane] : 0u;                  // (0 is no letter)
+        for (int cb = 0; cb < resStride; cb += 64) {
+                const int c = cb + lane;
+                const unsigned next = c + 64 < W ? row[c + 64] : 0u;
+                const bool isr = ka_msa_is_residue(b);
+                const unsigned long long m = __ballot(isr);
+                const int r = run + __popcll(m & below);
+                const bool put = isr && r < len;
+                if (c < resStride) rs[c] = put ? (int16_t)r : (int16_t)-1;
+                if (put) cs[r] = c;
+                run += __popcll(m);
+                b = next;
+        }
+}
+
 // the sequences whose rows the alignments hold: lengths and flat residue numbering, here and on the device
 struct KaSeqSet {
         int N = 0, T = 0, maxlen = 0;          // sequences, residues, longest sequence

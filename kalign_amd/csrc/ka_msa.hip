@@ -6,30 +6,13 @@
 #define MSA_THREADS 256
 #define MSA_WAVES (MSA_THREADS / 64)
 
-// one wave per row: res[s][c] for every column of the res row (-1 at gaps and padding), col[offs[s] + r] for every
-// residue, the residue rank of a column from a ballot prefix.  The host has checked every row's letter count against
-// lens[s]; the rank guard keeps the writes in place regardless.
+// one wave per row (ka_msa_map_row): res[s][c] for every column of the res row, col[offs[s] + r] for every residue
 __global__ __launch_bounds__(MSA_THREADS) void msa_maps(const uint8_t* rows, int rowStride, int W, int resStride, int N, const int* offs,
                                                         const int* lens, int* col, int16_t* res)
 {
         const int s = blockIdx.x * MSA_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
         if (s >= N) return;
-        const uint8_t* row = rows + (long long)s * rowStride;
-        int16_t* rs = res + (long long)s * resStride;
-        int* cs = col + offs[s];
-        const int len = lens[s];
-        const unsigned long long below = (1ull << lane) - 1ull;
-        int run = 0;
-        for (int cb = 0; cb < resStride; cb += 64) {
-                const int c = cb + lane;
-                const bool isr = c < W && ka_msa_is_residue(row[c]);
-                const unsigned long long m = __ballot(isr);
-                const int r = run + __popcll(m & below);
-                const bool put = isr && r < len;
-                if (c < resStride) rs[c] = put ? (int16_t)r : (int16_t)-1;
-                if (put) cs[r] = c;
-                run += __popcll(m);
-        }
+        ka_msa_map_row(rows + (long long)s * rowStride, W, resStride, lens[s], col + offs[s], res + (long long)s * resStride, lane);
 }
 
 void ka_msa_launch_maps(const uint8_t* rows, int rowStride, int W, int resStride, const KaSeqSet& q, int* col, int16_t* res, hipStream_t s)

@@ -1,7 +1,9 @@
 """GPU: an alignment scored against a reference alignment (ka_cmp; kalign_amd.compare) against the reference's
 kalign_msa_compare, kalign_msa_compare_detailed and kalign_msa_compare_with_mask (lib/src/msa_cmp.c) -- stored cases
 (tests/golden/cmp_*.npz, make_golden_compare.py), live randomized cases when oracle/_ref is built, a numpy restatement
-of every counter (cmp_restate.py), error paths and a property run at 4096 x ~400.  Every value is compared with ==."""
+of every counter (cmp_restate.py), error paths and a property run at 4096 x ~400; and the job table behind score_many
+(per-test tile geometry and LDS class, groups of 32) at its edges against the restatement.  Every value is compared
+with ==."""
 import glob
 import os
 import sys
@@ -17,6 +19,7 @@ CASES = sorted(os.path.basename(f)[4:-4] for f in glob.glob(os.path.join(GOLDEN,
 sys.path.insert(0, GOLDEN)
 
 import cmp_restate as R  # noqa: E402
+from cmp_cases import check_restated, letters, placed  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -228,6 +231,107 @@ def test_property_4096(ctx):
     assert self_["sp"] == 100.0 and self_["recall"] == 1.0 and self_["precision"] == 1.0 and self_["tc"] == 1.0
     assert self_["identical_aligned"] == self_["ref_total_aligned_pairs"]
     assert self_["identical_gaps"] == self_["ref_total_gap_pairs"]
+    cmp.close()
+
+
+# ---- the job table behind score_many: every test its own tile geometry and LDS class, groups of 32 ----
+def _tests_of(rng, seqs, widths):
+    return [placed(rng, seqs, W) for W in widths]
+
+
+@pytest.mark.parametrize("WR", [7, 8, 9, 64, 65])
+@pytest.mark.parametrize("N", [2, 16, 17, 32, 33, 47])
+def test_score_many_tile_and_padding_edges(ctx, N, WR):
+    """N at the KA_CMP_TI / KA_CMP_TJ boundaries, five tests narrower and wider than the reference and on both sides
+    of the multiples of 8 (ka_cmp_pad); 17 x 64 with an all-gap reference column, 33 x 9 with a sequence without residues"""
+    rng = np.random.RandomState(1000 * N + WR)
+    free = 9 if (N, WR) == (17, 64) else None
+    widths = [WR - 2, WR - 1, WR, WR + 1, (WR + 7) // 8 * 8 + 9]
+    seqs = letters(rng, N, WR - 2, zero=(N, WR) == (33, 9))
+    ref = placed(rng, seqs, WR, free)
+    tests = _tests_of(rng, seqs, widths)
+    assert free is None or all(r[free] == 45 for r in ref)
+    mask = (rng.rand(WR) < 0.6).astype(np.int32)
+    cmp = ctx.comparer(ref)
+    for kw, scored in ((dict(), R.scored_mask(ref)), (dict(max_gap_frac=0.2), R.scored_mask(ref, 0.2)),
+                       (dict(column_mask=mask), R.scored_mask(ref, -1.0, mask))):
+        got = cmp.score_many(tests, **kw)
+        assert len(got) == 5
+        for g, t in zip(got, tests):
+            check_restated(g, ref, t, scored)
+    cmp.close()
+
+
+def test_score_many_three_lds_classes_in_one_call(ctx):
+    """3 x 600 against widths 610, 33000 and 5000: the walk stages 3, 1 and 3 row pairs -- up to 16 KiB, above 64 KiB
+    and up to 64 KiB of LDS, one launch each, the widest test in the middle of the list"""
+    rng = np.random.RandomState(71)
+    seqs = letters(rng, 3, 600, alpha=b"ACGT")
+    ref = placed(rng, seqs, 600)
+    tests = _tests_of(rng, seqs, [610, 33000, 5000])
+    assert 3 * (600 + 616) * 2 <= 16384 and (600 + 33000) * 2 > 65536 and 32768 < 3 * (600 + 5000) * 2 <= 65536
+    cmp = ctx.comparer(ref)
+    many = cmp.score_many(tests, max_gap_frac=0.5)
+    assert many == [cmp.score(t, max_gap_frac=0.5) for t in tests]
+    for g, t in zip(many, tests):
+        check_restated(g, ref, t, R.scored_mask(ref, 0.5))
+    cmp.close()
+
+
+@pytest.fixture(scope="module")
+def two_groups():
+    """a 17 x 40 reference and 34 tests of differing widths: (ref, tests, the restated counts), left unchanged"""
+    rng = np.random.RandomState(81)
+    seqs = letters(rng, 17, 36)
+    ref = placed(rng, seqs, 40)
+    tests = _tests_of(rng, seqs, [36 + (5 * k) % 23 for k in range(34)])
+    return ref, tests, [R.counts(ref, t, R.scored_mask(ref)) for t in tests]
+
+
+def test_score_many_two_groups(ctx, two_groups):
+    """33 tests: the job tables are rebuilt between the groups of 32 and every output lands at its k"""
+    ref, tests, want = two_groups
+    assert len({len(t[0]) for t in tests[:33]}) > 8
+    cmp = ctx.comparer(ref)
+    got = cmp.score_many(tests[:33])
+    assert [[g[k] for k in _keys()] for g in got] == want[:33]
+    for g, w in zip(got, want):
+        sp, rc, pr, f1, tc = R.scores(w)
+        assert (np.float32(g["sp"]), g["recall"], g["precision"], g["f1"], g["tc"]) == (sp, rc, pr, f1, tc)
+    cmp.close()
+
+
+def test_refused_test_in_the_second_group(ctx, two_groups):
+    """a wrong letter count in test 32, a stride below the width of test 33: refused before anything runs (no output
+    is written, not even the first group's), and the handle scores the valid tests afterwards"""
+    import ctypes as C
+    from kalign_amd import KalignAmdError
+    from kalign_amd.api import _ptr
+    ref, tests, want = two_groups
+    cmp = ctx.comparer(ref)
+    arrs = [np.frombuffer(b"".join(t), np.uint8) for t in tests]
+    widths = np.array([len(t[0]) for t in tests], np.int32)
+
+    def batch(arrs, strides):
+        counts = np.full((34, 12), -1, np.int64)
+        ptrs = (C.c_void_p * 34)(*[a.ctypes.data for a in arrs])
+        rc = ctx.L.ka_cmp_score_batch(cmp.h, 34, ptrs, _ptr(np.asarray(strides, np.int64)), _ptr(widths), _ptr(counts), None, None)
+        return rc, counts
+
+    lost = tests[32][:3] + [b"-" * int(widths[32])] + tests[32][4:]       # row 3 lost its letters
+    rc, counts = batch(arrs[:32] + [np.frombuffer(b"".join(lost), np.uint8)] + arrs[33:], widths)
+    with pytest.raises(KalignAmdError, match=r"ka_cmp_score: test 32: row 3 holds 0 letters, its sequence \d+ \(every alignment"):
+        ctx._chk(rc)
+    assert (counts == -1).all()
+    strides = widths.astype(np.int64)
+    strides[33] -= 1
+    rc, counts = batch(arrs, strides)
+    with pytest.raises(KalignAmdError, match=r"ka_cmp_score: test 33: alignment width %d does not fit row stride %d" % (widths[33], widths[33] - 1)):
+        ctx._chk(rc)
+    assert (counts == -1).all()
+    rc, counts = batch(arrs, widths)
+    assert rc == 0 and counts.tolist() == want
+    assert [[g[k] for k in _keys()] for g in cmp.score_many(tests[:33])] == want[:33]
     cmp.close()
 
 

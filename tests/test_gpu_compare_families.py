@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, GOLDEN)
 
 import cmp_restate as R  # noqa: E402
+from cmp_cases import check_restated, family, keys as _keys  # noqa: E402
 
 FRACS = [float(np.float32(x)) for x in (-1.0, 0.0, 0.2, 0.5, 1.0)]    # as stored: float32
 
@@ -26,41 +27,6 @@ def ctx():
     c = kalign_amd.Context(0)
     yield c
     c.close()
-
-
-def _keys():
-    from kalign_amd.api import CMP_COUNTS
-    return CMP_COUNTS
-
-
-def placed(rng, letters, W, free=None):
-    """one row per sequence: its letters (uint8 arrays) at random columns of W, never column `free`"""
-    cols_ok = np.array([c for c in range(W) if c != free])
-    rows = []
-    for seq in letters:
-        row = np.full(W, ord("-"), np.uint8)
-        row[np.sort(rng.choice(cols_ok, size=len(seq), replace=False))] = seq
-        rows.append(row.tobytes())
-    return rows
-
-
-def family(rng, N, WR, WT, free=None, zero=False, alpha=b"ACDEFGHIKLMNPQRSTVWY"):
-    """(reference rows, test rows) of N sequences: the same letters placed independently in WR and in WT columns; with
-    `free` that reference column stays all gaps, with `zero` sequence 1 has no residue"""
-    cap = min(WR - (free is not None), WT)
-    lens = rng.randint(max(1, cap // 2), cap + 1, size=N)
-    if zero:
-        lens[1] = 0
-    a = np.frombuffer(alpha, np.uint8)
-    letters = [a[rng.randint(0, len(a), size=n)] for n in lens]
-    return placed(rng, letters, WR, free), placed(rng, letters, WT)
-
-
-def check_restated(got, ref, test, scored):
-    want = R.counts(ref, test, scored)
-    assert [got[k] for k in _keys()] == want
-    sp, rc, pr, f1, tc = R.scores(want)
-    assert (np.float32(got["sp"]), got["recall"], got["precision"], got["f1"], got["tc"]) == (sp, rc, pr, f1, tc)
 
 
 # ---- 1. the stored results of the real reference, all cases as one batch ----
