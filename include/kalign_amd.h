@@ -558,7 +558,8 @@ int ka_multi_adopt(ka_multi* m, const ka_task_rec* recs, const int* gaps);
  *                       Fails for a sequence of more than 4096 residues: the reference packs a pair as ri << 20 | rj in 32 bits,
  *                       which aliases from residue index 4096 on, so its result there is not a defined contract.
  *   ka_ens_add_member   member k's rows: numseq rows of alnlen bytes, row_stride apart.  Fails when alnlen does not fit the stride
- *                       or a row's letter count differs from lens[s].  Every member must be added before the calls below.
+ *                       or a row's letter count differs from lens[s], or when numseq * alnlen exceeds 2^31 - 1 (also for the
+ *                       alignments of ka_ens_score_rows and ka_ens_confidence).  Every member must be added before the calls below.
  *   ka_ens_score_rows   score_alignment_poar (consensus_msa.c:694-740) of any alignment of the sequences: sum_out = the exact sum
  *                       over its residue pairs of (support - 1) (-1 for a pair no member has), score_out = sum / max(n_runs - 1, 1).
  *                       The reference adds the terms one by one in double: equal within rounding, equal for equal pair sets.
@@ -571,8 +572,10 @@ int ka_multi_adopt(ka_multi* m, const ka_task_rec* recs, const int* gaps);
  *   ka_ens_stats        measurements of the last calls: stats_out[10] = device ms of the position maps, of the last score, of the
  *                       consensus' count passes and write passes, host ms of the greedy and of the column order + fill, device ms of
  *                       the last confidence, host ms spent waiting for candidates, number of candidate chunks, breadth-first
- *                       searches that hit the 4096-set queue limit; level_counts_out[33] / level_ms_out[33]: candidates and device
- *                       ms per support level of the last consensus.
+ *                       searches that hit the 4096-set queue limit; level_counts_out[33] / level_ms_out[33]: candidates per support
+ *                       level of the last consensus, and the device ms spent on that level alone: its write passes, plus its count
+ *                       pass on a handle opened from a table, which counts level by level.  (A handle with members counts all
+ *                       levels of a block of rows in one pass: that time is in stats_out[2] only.)
  */
 typedef struct ka_ens ka_ens;
 int  ka_ens_create(ka_ctx* ctx, int numseq, const int* lens, int n_runs, ka_ens** out);
@@ -696,7 +699,7 @@ int  ka_cmp_fam_score(ka_cmp_fam* h, const uint8_t* test_rows, const int* test_a
                       float* sp_out);
 int  ka_cmp_fam_stats(ka_cmp_fam* h, double* stats_out);
 
-/* ---- the ensemble consensus stage for a batch of families (ka_ens_fam.hip, ka_ens_fam.cpp) ------------------------------------
+/* ---- the ensemble consensus stage for a batch of families (ka_ens.hip, ka_ens_fam.cpp) ----------------------------------------
  * What ka_ens_create + ka_ens_add_member + ka_ens_score_rows + ka_ens_consensus + ka_ens_confidence return for every family
  * alone -- equal integer sums, doubles from the same expressions, byte-identical rows, bit-identical confidences -- for all
  * families of a batch with the same number of members.  The number of launches and host synchronisations of a call depends

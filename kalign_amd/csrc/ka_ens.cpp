@@ -1,12 +1,15 @@
-// ka_ens.cpp -- host side of the ensemble consensus stage (kalign_ensemble's tail, lib/src/ensemble.c:341-): the ka_ens
-// handle of the C ABI, and the one part of the stage that stays sequential -- build_consensus' greedy union of the
-// candidate pairs (consensus_msa.c:372-562) and the column order after it.
+// ka_ens.cpp -- host side of the ensemble consensus stage (kalign_ensemble's tail, lib/src/ensemble.c:341-): KaEnsCore
+// (ka_ens_core.h), the one host core of the stage, and over it the ka_ens handle of the C ABI -- a table of one family.
+// (ka_ens_fam.cpp is the front for a batch of families.)
 //
 // The device (ka_ens.hip) turns the members' rows into position maps and walks (i, j, ri) for scores, confidences and
-// candidates.  The candidates come one support level at a time, highest first, in the reference's order inside a level
-// (i, j, ri, rj ascending; the stable counting sort of consensus_msa.c:438-459 over the table order).  A level is cut
-// into chunks of whole rows i; while the greedy replays chunk c from pinned memory, the device writes chunk c + 1.
+// candidates.  The candidates of every support level are counted in one pass over a block of rows and written one level
+// at a time, highest first, in the reference's order inside a level (i, j, ri, rj ascending; the stable counting sort of
+// consensus_msa.c:438-459 over the table order).  A level is cut into chunks (here: of whole rows i); while the host takes
+// chunk c from pinned memory, the device writes chunk c + 1.
 //
+// The one part of the stage that stays sequential is build_consensus' greedy union of the candidate pairs
+// (consensus_msa.c:372-562) and the column order after it (ka_ens_union.h); this front runs it on the calling thread.
 // The greedy is order-dependent in two ways and is replayed candidate by candidate:
 //   * a merge is refused when the two sets share a sequence, or when either set reaches the other in the column DAG
 //     (an edge from a residue's set to the set of the next residue of the same sequence);
@@ -14,46 +17,373 @@
 //     full (dag_reachable, consensus_msa.c:121-160) -- its answer depends on the order of the sets' member lists,
 //     i.e. on the merge history.  The lists are concatenated as the reference does (the absorbed set's list after the
 //     surviving root's), the root chosen by rank as it does.
-// The same chunked hand-over carries the members' POAR table to a file (ka_ens_table_write; poar_table_write,
-// poar.c:203-252), and a handle opened from such a file (ka_ens_open_table; poar_table_read, poar.c:254-325) reads its
-// support and its candidates from the table on the device (ka_poar.hip) and feeds the same greedy.
+// The same count-a-block and hand-over sequences carry the members' POAR table to a file (ka_ens_table_write;
+// poar_table_write, poar.c:203-252), and a handle opened from such a file (ka_ens_open_table; poar_table_read,
+// poar.c:254-325) reads its support and its candidates from the table on the device (ka_poar.hip) and feeds the same greedy.
 // The columns are numbered by the first residue (flat order) of each set, ordered by a DFS topological sort that skips
 // back edges (topo_sort, consensus_msa.c:255-370) and filled with the caller's letters.
-#include "ka_ctx.h"
-#include "ka_ens.h"
+#include "ka_ens_core.h"
 #include "ka_ens_union.h"     // Uf, topo_order, ka_ens_fill: shared with ka_ens_fam.cpp
-#include "ka_msa.h"
 
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
 
-namespace {
+// ---------------------------------------------------------------- the core ----------------------------------------------------------------
 
-double ms_since(std::chrono::steady_clock::time_point t0)
+KaEnsCore::~KaEnsCore()
 {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        for (int b = 0; b < 2; b++) {
+                if (pinned[b]) (void)hipHostFree(pinned[b]);
+                if (ready[b]) (void)hipEventDestroy(ready[b]);
+                if (wBeg[b]) (void)hipEventDestroy(wBeg[b]);
+                if (wEnd[b]) (void)hipEventDestroy(wEnd[b]);
+                dOut[b].release();
+        }
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        for (auto& r : dRows) r.release();
+        dFams.release(); dFirstSeq.release(); dBlkFirst.release(); dOffs.release(); dLens.release(); dCol.release(); dMemW.release();
+        dMemCell.release(); dColX.release(); dXTab.release(); dSup.release(); dNp.release(); dCnt.release();
+        dMemRowOff.release(); dXRowOff.release(); dPairOff.release(); dRowTot.release(); dRowBase.release(); dRes.release(); dResX.release();
+        dRowsX.release(); dScore.release(); dConf.release(); dColConf.release();
 }
 
-} // namespace
+void KaEnsCore::close()
+{
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+}
+
+int KaEnsCore::create(const char* who, ka_ctx* ctx, int n_fam, const int* fam_first, const int* l, int n_runs, int rowPadBytes)
+{
+        const std::string me(who);
+        if (ka_ctx_device_stream(ctx, &device, &stream)) return fail(me + ": bad context");
+        F = n_fam; S = fam_first[n_fam]; R = n_runs; rowPad = rowPadBytes;
+        famFirst.assign(fam_first, fam_first + F + 1);
+        lens.assign(l, l + S);
+        offs.resize(S + 1);
+        int t = 0;
+        for (int s = 0; s < S; s++) { offs[s] = t; t += l[s]; }
+        offs[S] = T = t;
+        fams.resize(F);
+        blkFirst.resize(F + 1);
+        long long blocks = 0;
+        for (int f = 0; f < F; f++) {
+                KaEnsFam& d = fams[f];
+                d = KaEnsFam{};
+                d.firstSeq = fam_first[f]; d.firstRes = offs[fam_first[f]];
+                d.N = fam_first[f + 1] - fam_first[f];
+                for (int s = 0; s < d.N; s++) d.maxlen = std::max(d.maxlen, l[d.firstSeq + s]);
+                d.nJC = (d.N + KA_ENS_JCHUNK - 1) / KA_ENS_JCHUNK;
+                // the member columns of sequence i in LDS when they fit next to the three per-residue arrays (64 KiB)
+                d.colInLds = (long long)(3 + R) * d.maxlen * 4 <= 65536;
+                d.minSup = 1;
+                ldsX = std::max(ldsX, (size_t)(3 * d.maxlen + (d.colInLds ? R * d.maxlen : 0)) * sizeof(int));
+                ldsCand = std::max(ldsCand, (size_t)(d.colInLds ? R * d.maxlen : 0) * sizeof(int));
+                d.cntFirst = E;
+                E += (long long)d.N * d.N;
+                blkFirst[f] = (int)blocks;
+                blocks += (long long)d.N * d.nJC;
+                if (blocks > INT32_MAX) return fail(me + ": more than 2^31 - 1 workgroups in a walk over the batch");
+        }
+        blkFirst[F] = nBlocks = (int)blocks;
+        added.assign(R, 0);
+        memW.assign((size_t)R * F, 0);
+        memCell.assign((size_t)R * (F + 1), 0);
+        memRowOff.assign((size_t)R * F, 0);
+        dRows.resize(R);
+        const char* cc = std::getenv("KA_ENS_CHUNK");                    // candidates per chunk (tests force many chunks)
+        chunkCap = cc && std::atoll(cc) > 0 ? std::atoll(cc) : (1ll << 22);
+        const char* cr = std::getenv("KA_ENS_COUNT_ROWS");               // rows per count block of ka_ens (tests force many blocks)
+        countRows = cr && std::atoi(cr) > 0 ? std::atoi(cr) : 0;
+        HIPCHK(hipSetDevice(device));
+        for (int b = 0; b < 2; b++) {
+                HIPCHK(hipEventCreateWithFlags(&ready[b], hipEventDisableTiming));
+                HIPCHK(hipEventCreate(&wBeg[b]));
+                HIPCHK(hipEventCreate(&wEnd[b]));
+        }
+        HIPCHK(hipEventCreate(&ev0));
+        HIPCHK(hipEventCreate(&ev1));
+        if (dFams.alloc(F) || dFirstSeq.alloc(F + 1) || dBlkFirst.alloc(F + 1) || dOffs.alloc(S + 1) || dLens.alloc(S) ||
+            dMemW.alloc(memW.size()) || dMemCell.alloc(memCell.size()) || dMemRowOff.alloc(memRowOff.size()) ||
+            dXTab.alloc((size_t)3 * F + 2) || dXRowOff.alloc(F) || dScore.alloc((size_t)R * F) ||
+            dSup.alloc((size_t)std::max(t, 1)) || dNp.alloc((size_t)std::max(t, 1)))
+                return fail(me + ": out of device memory");
+        HIPCHK(hipMemcpyAsync(dFams.p, fams.data(), sizeof(KaEnsFam) * F, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dFirstSeq.p, famFirst.data(), sizeof(int) * (F + 1), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dBlkFirst.p, blkFirst.data(), sizeof(int) * (F + 1), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dOffs.p, offs.data(), sizeof(int) * (S + 1), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dLens.p, lens.data(), sizeof(int) * S, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return KA_OK;
+}
+
+KaEnsFamArgs KaEnsCore::args() const
+{
+        KaEnsFamArgs a{};
+        a.nFam = F; a.S = S; a.T = T; a.R = R;
+        a.rows = S; a.E = E;
+        a.fams = dFams.p; a.firstSeq = dFirstSeq.p; a.blkFirst = dBlkFirst.p; a.offs = dOffs.p; a.lens = dLens.p;
+        a.col = dCol.p; a.res = dRes.p; a.memCell = dMemCell.p; a.memW = dMemW.p;
+        std::copy_n(resBase, KA_ENS_MAX_RUNS, a.resBase);
+        return a;
+}
+
+int KaEnsCore::member_fits(const char* who, int k, const int* alnlens) const
+{
+        long long c = 0;
+        for (int f = 0; f < F; f++) c += (long long)fams[f].N * alnlens[f];
+        if (c > INT32_MAX) return fail(std::string(who) + ": more than 2^31 - 1 cells in the maps of member " + std::to_string(k));
+        return KA_OK;
+}
+
+// (the member's entries of the three tables go to the device here, stream-ordered, from vectors that outlive the copies: the
+// maps launches of ensure_maps then follow no upload)
+int KaEnsCore::member_added(int k, const int* alnlens)
+{
+        long long ro = 0, c = 0;
+        for (int f = 0; f < F; f++) {
+                memW[(size_t)k * F + f] = alnlens[f];
+                memRowOff[(size_t)k * F + f] = ro;
+                memCell[(size_t)k * (F + 1) + f] = (int)c;
+                ro += (long long)fams[f].N * (alnlens[f] + rowPad);
+                c += (long long)fams[f].N * alnlens[f];
+        }
+        memCell[(size_t)k * (F + 1) + F] = (int)c;
+        HIPCHK(hipMemcpyAsync(dMemW.p + (size_t)k * F, &memW[(size_t)k * F], sizeof(int) * F, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dMemCell.p + (size_t)k * (F + 1), &memCell[(size_t)k * (F + 1)], sizeof(int) * (F + 1), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dMemRowOff.p + (size_t)k * F, &memRowOff[(size_t)k * F], sizeof(long long) * F, hipMemcpyHostToDevice, stream));
+        added[k] = 1;
+        mapsFresh = false;
+        return KA_OK;
+}
+
+int KaEnsCore::ensure_maps(const char* who)
+{
+        if (mapsFresh) return KA_OK;
+        for (int k = 0; k < R; k++)
+                if (!added[k]) return fail(std::string(who) + ": member " + std::to_string(k) + " not added (all n_runs members are needed)");
+        long long o = 0;
+        for (int k = 0; k < R; k++) { resBase[k] = o; o += memCell[(size_t)k * (F + 1) + F]; }
+        if (dCol.alloc((size_t)R * std::max(T, 1)) || dRes.alloc((size_t)o)) return fail(std::string(who) + ": out of device memory (maps)");
+        HIPCHK(hipEventRecord(ev0, stream));
+        const KaMsaFamRows t{ F, S, dFirstSeq.p, dOffs.p, dLens.p };
+        for (int k = 0; k < R; k++) {
+                ka_msa_launch_maps_fam(t, dRows[k].p, dMemRowOff.p + (size_t)k * F, dMemW.p + (size_t)k * F, dMemCell.p + (size_t)k * (F + 1), rowPad,
+                                   dCol.p + (long long)k * T, dRes.p + resBase[k], stream);
+                nLaunch++;
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev1, stream));
+        HIPCHK(hipEventSynchronize(ev1));
+        nSync++;
+        mapsMs = evMs();
+        mapsFresh = true;
+        return KA_OK;
+}
+
+int KaEnsCore::maps_x(const char* who, const int* alnlens, const KaEnsUpload& upload, KaEnsFamArgs& a, int* cells, int* cols)
+{
+        // xW [F] | xCell [F + 1] | xCol [F + 1]; they and the rows' offsets outlive their copies: no wait on the host here
+        std::vector<int>& tab = xTab;
+        std::vector<long long>& rowOff = xRowOff;
+        tab.resize((size_t)3 * F + 2);
+        rowOff.resize(F);
+        int* xW = tab.data();
+        int* xCell = xW + F;
+        int* xCol = xCell + F + 1;
+        long long ro = 0, c = 0;
+        int w = 0;
+        for (int f = 0; f < F; f++) {
+                const int W = std::max(alnlens[f], 0);
+                xW[f] = W; xCell[f] = (int)c; xCol[f] = w; rowOff[f] = ro;
+                c += (long long)fams[f].N * W;
+                w += W;
+                if (W > 0) ro += (long long)fams[f].N * (W + rowPad);
+                if (c > INT32_MAX) return fail(std::string(who) + ": more than 2^31 - 1 cells in the alignment's maps");
+        }
+        xCell[F] = (int)c; xCol[F] = w;
+        if (dRowsX.alloc((size_t)std::max(ro, 1LL)) || dColX.alloc((size_t)std::max(T, 1)) || dResX.alloc((size_t)std::max(c, 1LL)))
+                return fail(std::string(xWho ? xWho : who) + ": out of device memory");
+        if (upload(dRowsX.p, stream)) return KA_FAIL;
+        HIPCHK(hipMemcpyAsync(dXTab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dXRowOff.p, rowOff.data(), sizeof(long long) * F, hipMemcpyHostToDevice, stream));
+        a.colX = dColX.p; a.resX = dResX.p; a.xW = dXTab.p; a.xCell = dXTab.p + F; a.xCol = dXTab.p + 2 * F + 1;
+        ka_msa_launch_maps_fam(KaMsaFamRows{ F, S, dFirstSeq.p, dOffs.p, dLens.p }, dRowsX.p, dXRowOff.p, a.xW, a.xCell, rowPad, dColX.p, dResX.p, stream);
+        nLaunch++;
+        *cells = (int)c; *cols = w;
+        return KA_OK;
+}
+
+// dScore[0 .. n) to the caller: sums, and score_alignment_poar's doubles
+int KaEnsCore::scores_back(long long* sums_out, double* scores_out, int n)
+{
+        std::vector<unsigned long long> s((size_t)n);
+        HIPCHK(hipMemcpyAsync(s.data(), dScore.p, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        nSync++;
+        scoreMs = evMs();
+        for (int x = 0; x < n; x++) {
+                const long long v = (long long)s[x];
+                if (sums_out) sums_out[x] = v;
+                if (scores_out) scores_out[x] = (double)v / (R > 1 ? (double)(R - 1) : 1.0);
+        }
+        return KA_OK;
+}
+
+int KaEnsCore::score_x(const char* who, const int* alnlens, const KaEnsUpload& upload, const KaEnsSupport* other, long long* sums_out, double* scores_out)
+{
+        KaEnsFamArgs a = args();
+        int cells = 0, cols = 0;
+        HIPCHK(hipEventRecord(ev0, stream));
+        if (maps_x(who, alnlens, upload, a, &cells, &cols)) return KA_FAIL;
+        HIPCHK(hipMemsetAsync(dScore.p, 0, sizeof(unsigned long long) * (size_t)F, stream));
+        a.score = dScore.p;
+        if (other) (*other)(a);
+        else ka_ens_launch_walk(KA_ENS_SCORE, a, nBlocks, ldsX, stream);
+        nLaunch++;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev1, stream));
+        return scores_back(sums_out, scores_out, F);
+}
+
+int KaEnsCore::score_members(long long* sums_out, double* scores_out)
+{
+        HIPCHK(hipEventRecord(ev0, stream));
+        HIPCHK(hipMemsetAsync(dScore.p, 0, sizeof(unsigned long long) * (size_t)R * F, stream));
+        for (int k = 0; k < R; k++) {
+                // member k as the alignment X: its maps are the walk's tables already
+                KaEnsFamArgs a = args();
+                a.colX = dCol.p + (long long)k * T; a.resX = dRes.p + resBase[k];
+                a.xW = dMemW.p + (size_t)k * F; a.xCell = dMemCell.p + (size_t)k * (F + 1);
+                a.score = dScore.p + (size_t)k * F;
+                ka_ens_launch_walk(KA_ENS_SCORE, a, nBlocks, ldsX, stream);
+                nLaunch++;
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev1, stream));
+        return scores_back(sums_out, scores_out, R * F);
+}
+
+int KaEnsCore::confidence(const char* who, const int* alnlens, const KaEnsUpload& upload, const KaEnsSupport* other, float* res_conf_out, float* col_conf_out)
+{
+        KaEnsFamArgs a = args();
+        int cells = 0, cols = 0;
+        HIPCHK(hipEventRecord(ev0, stream));
+        if (maps_x(who, alnlens, upload, a, &cells, &cols)) return KA_FAIL;
+        if (dConf.alloc((size_t)cells) || dColConf.alloc((size_t)cols)) return fail(std::string(who) + ": out of device memory");
+        const size_t T1 = (size_t)std::max(T, 1);
+        HIPCHK(hipMemsetAsync(dSup.p, 0, sizeof(int) * T1, stream));
+        HIPCHK(hipMemsetAsync(dNp.p, 0, sizeof(int) * T1, stream));
+        a.supSum = dSup.p; a.nPair = dNp.p;
+        if (other) (*other)(a);
+        else ka_ens_launch_walk(KA_ENS_CONF, a, nBlocks, ldsX, stream);
+        ka_ens_launch_conf(a, cells, cols, dConf.p, dColConf.p, stream);
+        nLaunch += 3;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev1, stream));
+        HIPCHK(hipMemcpyAsync(res_conf_out, dConf.p, sizeof(float) * (size_t)cells, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(col_conf_out, dColConf.p, sizeof(float) * (size_t)cols, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        nSync++;
+        confMs = evMs();
+        return KA_OK;
+}
+
+int KaEnsCore::count_block(const char* who, KaEnsFamArgs& a, int nLev, const std::function<void(const KaEnsFamArgs&)>& count, std::vector<long long>& rowTot,
+                           std::vector<int>* pairCnt, double* ms)
+{
+        const long long ents = (long long)std::max(nLev, 0) * a.E, rows = (long long)std::max(nLev, 0) * a.rows;
+        if (ents > INT32_MAX) return fail(std::string(who) + ": more than 2^31 - 1 (level, i, j) counters in the batch");
+        const int nRows = (int)rows;
+        if (dCnt.alloc((size_t)std::max(ents, 1LL)) || dPairOff.alloc((size_t)std::max(ents, 1LL)) || dRowTot.alloc((size_t)std::max(nRows, 1)))
+                return fail(std::string(who) + ": out of device memory (counts)");
+        a.cnt = dCnt.p; a.pairOff = dPairOff.p;
+        rowTot.assign((size_t)nRows, 0);
+        HIPCHK(hipEventRecord(ev0, stream));
+        HIPCHK(hipMemsetAsync(dCnt.p, 0, sizeof(int) * (size_t)std::max(ents, 1LL), stream));
+        if (nLev > 0) {
+                count(a);
+                ka_ens_launch_row_scan(a, nRows, dPairOff.p, dRowTot.p, stream);
+                nLaunch += 2;
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev1, stream));
+        if (nRows) HIPCHK(hipMemcpyAsync(rowTot.data(), dRowTot.p, sizeof(long long) * nRows, hipMemcpyDeviceToHost, stream));
+        if (pairCnt) {
+                pairCnt->resize((size_t)ents);
+                if (ents) HIPCHK(hipMemcpyAsync(pairCnt->data(), dCnt.p, sizeof(int) * (size_t)ents, hipMemcpyDeviceToHost, stream));
+        }
+        HIPCHK(hipStreamSynchronize(stream));
+        nSync++;
+        *ms += evMs();
+        return KA_OK;
+}
+
+int KaEnsCore::put_row_base(const char* oom, const std::vector<long long>& rowBase)
+{
+        if (rowBase.empty()) return KA_OK;
+        if (dRowBase.alloc(rowBase.size())) return fail(oom);
+        HIPCHK(hipMemcpyAsync(dRowBase.p, rowBase.data(), sizeof(long long) * rowBase.size(), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));                    // (rowBase is read until here)
+        nSync++;
+        return KA_OK;
+}
+
+int KaEnsCore::hand_over(const char* who, const std::vector<KaEnsChunk>& chunks, const std::function<void(const KaEnsChunk&, int2* out)>& write,
+                         const std::function<int(const KaEnsChunk&, const int2* items)>& consume, double* writeMs, double* waitMs, double* nChunks)
+{
+        long long biggest = 0;
+        for (const KaEnsChunk& c : chunks) biggest = std::max(biggest, c.total);
+        if (biggest > pinnedCap) {                               // (nothing is in flight: every earlier chunk has been consumed)
+                for (int q = 0; q < 2; q++) {
+                        if (pinned[q]) (void)hipHostFree(pinned[q]);
+                        pinned[q] = nullptr;
+                        pinnedCap = 0;
+                        HIPCHK(hipHostMalloc((void**)&pinned[q], sizeof(int2) * (size_t)biggest));
+                        if (dOut[q].alloc((size_t)biggest)) return fail(std::string(who) + ": out of device memory (candidates)");
+                }
+                pinnedCap = biggest;
+        }
+        const int n = (int)chunks.size();
+        auto enqueue = [&](int c) -> int {
+                const int q = c & 1;
+                if (chunks[c].total == 0) return KA_OK;
+                HIPCHK(hipEventRecord(wBeg[q], stream));
+                write(chunks[c], dOut[q].p);
+                nLaunch++;
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipEventRecord(wEnd[q], stream));
+                HIPCHK(hipMemcpyAsync(pinned[q], dOut[q].p, sizeof(int2) * (size_t)chunks[c].total, hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipEventRecord(ready[q], stream));
+                return KA_OK;
+        };
+        if (n && enqueue(0)) return KA_FAIL;
+        for (int c = 0; c < n; c++) {
+                if (c + 1 < n && enqueue(c + 1)) return KA_FAIL;
+                if (chunks[c].total == 0) {
+                        if (consume(chunks[c], nullptr)) return KA_FAIL;
+                        continue;
+                }
+                const auto t0 = std::chrono::steady_clock::now();
+                HIPCHK(hipEventSynchronize(ready[c & 1]));
+                nSync++;
+                *waitMs += ka_ens_ms_since(t0);
+                float wms = 0.0f;
+                (void)hipEventElapsedTime(&wms, wBeg[c & 1], wEnd[c & 1]);
+                *writeMs += wms;
+                *nChunks += 1;
+                if (consume(chunks[c], pinned[c & 1])) return KA_FAIL;
+        }
+        return KA_OK;
+}
+
+// ---------------------------------------------------------------- the one-family front ----------------------------------------------------------------
 
 struct ka_ens {
         ka_ctx* ctx = nullptr;
-        int device = 0;
-        hipStream_t stream = nullptr;
-        KaSeqSet q;
+        KaEnsCore core;                               // a table of one family: F = 1, rows alnlen bytes apart
+        KaSeqSet q;                                   // (host side only: the checks of the caller's rows)
         int R = 0;
-        std::vector<int> W;
-        std::vector<DevBuf<uint8_t>> rows;            // member k's rows, N x W[k]
-        DevBuf<int> dCol, dColX, dCnt, dSup, dNp;
-        DevBuf<int16_t> dRes, dResX;
-        DevBuf<uint8_t> dRowsX;
-        DevBuf<long long> dPairOff, dRowTot, dRowBase[2];
-        DevBuf<unsigned long long> dScore;
-        DevBuf<int2> dOut[2];
-        DevBuf<float> dConf, dColConf;
-        int2* pinned[2] = { nullptr, nullptr };
-        long long pinnedCap = 0, chunkCap = 0;
-        hipEvent_t ready[2] = { nullptr, nullptr }, wBeg[2] = { nullptr, nullptr }, wEnd[2] = { nullptr, nullptr }, ev0 = nullptr, ev1 = nullptr;
-        bool mapsFresh = false;
         long long generation = 0;
         // a handle opened from a POAR table: no members, the table on the device
         bool fromTable = false;
@@ -72,86 +402,69 @@ struct ka_ens {
         long long levelCount[KA_ENS_MAX_RUNS + 1] = {};
         double levelMs[KA_ENS_MAX_RUNS + 1] = {};
 
-        ~ka_ens()
-        {
-                for (int b = 0; b < 2; b++) {
-                        if (pinned[b]) (void)hipHostFree(pinned[b]);
-                        if (ready[b]) (void)hipEventDestroy(ready[b]);
-                        if (wBeg[b]) (void)hipEventDestroy(wBeg[b]);
-                        if (wEnd[b]) (void)hipEventDestroy(wEnd[b]);
-                        dOut[b].release(); dRowBase[b].release();
-                }
-                if (ev0) (void)hipEventDestroy(ev0);
-                if (ev1) (void)hipEventDestroy(ev1);
-                for (auto& r : rows) r.release();
-                q.release();
-                dCol.release(); dColX.release(); dCnt.release(); dSup.release(); dNp.release();
-                dRes.release(); dResX.release(); dRowsX.release(); dPairOff.release(); dRowTot.release(); dScore.release();
-                dConf.release(); dColConf.release(); dPairStart.release(); dEnt.release();
-        }
+        ~ka_ens() { dPairStart.release(); dEnt.release(); }
 
-        float evMs() { float m = 0.0f; (void)hipEventElapsedTime(&m, ev0, ev1); return m; }
+        // the family's tables once n_runs is known
+        int open(const char* who, int n_runs)
+        {
+                const int first[2] = { 0, q.N };
+                R = n_runs;
+                core.xWho = "ka_ens";
+                return core.create(who, ctx, 1, first, q.lens.data(), n_runs, 0);
+        }
 
         int ensure_maps()
         {
-                if (mapsFresh || fromTable) return KA_OK;
-                for (int k = 0; k < R; k++)
-                        if (W[k] <= 0) return fail("ka_ens: member " + std::to_string(k) + " not added (all n_runs members are needed)");
-                const int N = q.N, T = q.T;
-                long long resTot = 0;
-                for (int k = 0; k < R; k++) resTot += (long long)N * W[k];
-                if (dCol.alloc((size_t)R * T) || dRes.alloc((size_t)resTot)) return fail("ka_ens: out of device memory (maps)");
-                HIPCHK(hipEventRecord(ev0, stream));
-                long long o = 0;
-                for (int k = 0; k < R; k++) {
-                        ka_msa_launch_maps(rows[k].p, W[k], W[k], W[k], q, dCol.p + (long long)k * T, dRes.p + o, stream);
-                        o += (long long)N * W[k];
-                }
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipEventRecord(ev1, stream));
-                HIPCHK(hipEventSynchronize(ev1));
-                st[0] = evMs();
-                mapsFresh = true;
-                return KA_OK;
+                if (fromTable) return KA_OK;
+                const int rc = core.ensure_maps("ka_ens");
+                st[0] = core.mapsMs;
+                return rc;
         }
 
-        KaEnsArgs args()
+        // the table passes' view of the same memory (ka_poar.hip); the members' maps are valid after ensure_maps
+        KaEnsArgs args() const
         {
                 KaEnsArgs a{};
-                a.offs = q.dOffs; a.lens = q.dLens; a.N = q.N; a.R = R; a.T = q.T; a.maxlen = q.maxlen;
-                a.col = dCol.p; a.res = dRes.p;
-                long long o = 0;
-                for (int k = 0; k < R; k++) { a.resOff[k] = o; a.W[k] = W[k]; o += (long long)q.N * W[k]; }
+                a.offs = core.dOffs.p; a.lens = core.dLens.p; a.N = q.N; a.R = R; a.T = q.T; a.maxlen = q.maxlen;
+                a.col = core.dCol.p; a.res = core.dRes.p;
+                for (int k = 0; k < R; k++) { a.resOff[k] = core.resBase[k]; a.W[k] = core.memW[k]; }
                 a.i0 = 0; a.i1 = q.N;
-                // the member columns of sequence i in LDS when they fit next to the three per-residue arrays (64 KiB)
-                a.colInLds = (long long)(3 + R) * q.maxlen * 4 <= 65536;
+                a.colInLds = core.fams[0].colInLds;
                 a.pairStart = dPairStart.p; a.ent = dEnt.p;
                 return a;
         }
 
-        // an alignment X's maps in dColX / dResX
-        int maps_x(const uint8_t* r, long long stride, int alnlen, KaEnsArgs& a)
+        // SCORE / CONF of a table-backed handle: the X maps and outputs of the core's call, support looked up in the table
+        KaEnsSupport lookup(int mode, int alnlen)
         {
-                if (dRowsX.alloc((size_t)q.N * alnlen) || dColX.alloc((size_t)std::max(q.T, 1)) || dResX.alloc((size_t)q.N * alnlen))
-                        return fail("ka_ens: out of device memory");
-                if (ka_msa_upload_rows(q, dRowsX.p, r, stride, alnlen, stream)) return KA_FAIL;
-                ka_msa_launch_maps(dRowsX.p, alnlen, alnlen, alnlen, q, dColX.p, dResX.p, stream);
-                a.colX = dColX.p; a.resX = dResX.p; a.Wx = alnlen;
-                return KA_OK;
+                return [this, mode, alnlen](const KaEnsFamArgs& f) {
+                        KaEnsArgs a = args();
+                        a.colX = f.colX; a.resX = f.resX; a.Wx = alnlen;
+                        a.score = f.score; a.supSum = f.supSum; a.nPair = f.nPair;
+                        ka_poar_launch_lookup(mode, a, core.stream);
+                };
         }
 
-        // SCORE / CONF / the candidates' COUNT / WRITE from the handle's source of support
-        void launch_support(int mode, const KaEnsArgs& a)
+        KaEnsUpload upload(const uint8_t* rows, long long stride, int alnlen)
         {
-                if (!fromTable) ka_ens_launch_walk(mode, a, stream);
-                else if (mode == KA_ENS_SCORE || mode == KA_ENS_CONF) ka_poar_launch_lookup(mode, a, stream);
-                else ka_poar_launch_level(mode, a, stream);
+                return [=](uint8_t* dst, hipStream_t s) { return alnlen > 0 ? ka_msa_upload_rows(q, dst, rows, stride, alnlen, s) : KA_OK; };
         }
 
-        template <class Count>
-        int count_rows(KaEnsArgs& a, int b0, int b1, Count count, std::vector<long long>& rowTot, std::vector<int>* pairCnt, double* countMs);
-        template <class Count, class Write, class Consume>
-        int stream_rows(KaEnsArgs a, Count count, Write write, Consume consume, std::vector<int>* pairCnt, double* countMs, double* writeMs, double* waitMs, double* chunks, long long* total);
+        // rows i per count block: the pair counts and offsets of a block are rows x N entries per level
+        int count_rows() const { return core.countRows ? std::min(core.countRows, q.N) : std::max(1, std::min(q.N, (int)((1ll << 24) / std::max(q.N, 1)))); }
+        // a count table of rows b0 .. b1
+        KaEnsFamArgs block_args(int b0, int b1) const
+        {
+                KaEnsFamArgs f = core.args();
+                f.row0 = b0; f.rows = b1 - b0; f.cnt0 = (long long)b0 * q.N; f.E = (long long)(b1 - b0) * q.N;
+                f.blk0 = b0 * core.fams[0].nJC;
+                return f;
+        }
+        void cut_rows(int level, int b0, int b1, const long long* tot, long long* rowBase, std::vector<KaEnsChunk>& out, long long* total) const;
+        typedef std::function<void(const KaEnsArgs&)> Pass;
+        int count_table_block(const KaEnsArgs& a, int b0, int b1, const Pass& count, std::vector<long long>& rowTot, std::vector<int>* pairCnt, double* countMs);
+        typedef std::function<int(int i0, int i1, int b0, const int2* items, long long n)> Consume;
+        int stream_rows(const KaEnsArgs& a, const Pass& count, const Pass& write, const Consume& consume, std::vector<int>* pairCnt, double* countMs, double* writeMs, double* waitMs, double* chunks, long long* total);
         int consensus(int minSup, const uint8_t* letters);
         struct Sink;
         int table_count(long long* entries);
@@ -160,112 +473,59 @@ struct ka_ens {
         struct TabRef { const long long* pairStart; const uint2* ent; long long entries; };
         int pair_starts(int b0, int b1, const std::vector<long long>& rowTot, long long* run, long long* pairStart);
         int table_on_device(DevBuf<long long>& ps, DevBuf<uint2>& ent, TabRef* t);
-        template <class Launch>
-        int derive_table(const char* who, KaEnsArgs a, Launch launch);
+        int derive_table(const char* who, KaEnsArgs a, const std::function<void(int, const KaEnsArgs&)>& launch);
 };
 
-// rows i per count pass: the pair counts and offsets of a block are rows x N entries
-static int ens_count_block(int N) { return std::max(1, std::min(N, (int)((1ll << 24) / std::max(N, 1)))); }
-
-// count(a) over rows b0 .. b1 and the row scan: a.cnt and dPairOff on the device, the rows' totals (and, when asked for, the
-// pairs' counts) on the host
-template <class Count>
-int ka_ens::count_rows(KaEnsArgs& a, int b0, int b1, Count count, std::vector<long long>& rowTot, std::vector<int>* pairCnt, double* countMs)
+// One level's rows b0 .. b1 with tot[i - b0] items each, cut into chunks of whole rows of at most chunkCap items (a longer row
+// is a chunk of its own; the last chunk may be empty); rowBase[i - b0]: the row's first slot in its chunk
+void ka_ens::cut_rows(int level, int b0, int b1, const long long* tot, long long* rowBase, std::vector<KaEnsChunk>& out, long long* total) const
 {
-        const int N = q.N, rb = ens_count_block(N);
-        if (dCnt.alloc((size_t)rb * N) || dPairOff.alloc((size_t)rb * N) || dRowTot.alloc((size_t)rb)) return fail("ka_ens: out of device memory (counts)");
-        rowTot.resize(rb);
-        a.i0 = b0; a.i1 = b1; a.cnt = dCnt.p;
-        HIPCHK(hipEventRecord(ev0, stream));
-        HIPCHK(hipMemsetAsync(dCnt.p, 0, sizeof(int) * (size_t)(b1 - b0) * N, stream));
-        count(a);
-        ka_ens_launch_row_scan(dCnt.p, N, dPairOff.p, dRowTot.p, b1 - b0, stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev1, stream));
-        HIPCHK(hipMemcpyAsync(rowTot.data(), dRowTot.p, sizeof(long long) * (b1 - b0), hipMemcpyDeviceToHost, stream));
-        if (pairCnt) {
-                pairCnt->resize((size_t)(b1 - b0) * N);
-                HIPCHK(hipMemcpyAsync(pairCnt->data(), dCnt.p, sizeof(int) * (size_t)(b1 - b0) * N, hipMemcpyDeviceToHost, stream));
+        const int nJC = core.fams[0].nJC;
+        int c0 = b0;
+        long long run = 0;
+        for (int i = b0; i < b1; i++) {
+                const long long t = tot[i - b0];
+                *total += t;
+                if (run > 0 && run + t > core.chunkCap) { out.push_back(KaEnsChunk{ level, c0, i, c0 * nJC, (i - c0) * nJC, run }); c0 = i; run = 0; }
+                rowBase[i - b0] = run;
+                run += t;
         }
-        HIPCHK(hipStreamSynchronize(stream));
-        *countMs += evMs();
-        return KA_OK;
+        out.push_back(KaEnsChunk{ level, c0, b1, c0 * nJC, (b1 - c0) * nJC, run });
 }
 
-// One pass over all rows i of a per-pair list (candidates of a level, or table entries): count(a) fills a.cnt for rows
-// a.i0 .. a.i1, the rows are scanned and cut into chunks of whole rows of at most chunkCap items (a longer row is a chunk of
-// its own), write(w) puts chunk c + 1 into the other device buffer while consume(i0, i1, b0, items, n) takes chunk c from
-// pinned memory (b0: first row of the count block, for pairCnt -- the block's counts on the host, when asked for).
-template <class Count, class Write, class Consume>
-int ka_ens::stream_rows(KaEnsArgs a, Count count, Write write, Consume consume, std::vector<int>* pairCnt, double* countMs, double* writeMs, double* waitMs, double* chunks, long long* total)
+// count(x) of a table pass over rows b0 .. b1 as one level of the count table: x.cnt, core.dPairOff, the rows' totals
+int ka_ens::count_table_block(const KaEnsArgs& a, int b0, int b1, const Pass& count, std::vector<long long>& rowTot, std::vector<int>* pairCnt, double* countMs)
 {
-        using clk = std::chrono::steady_clock;
-        const int N = q.N;
-        const int rb = ens_count_block(N);
-        std::vector<long long> rowTot;
-        std::vector<long long> rowBase[2];
+        KaEnsFamArgs f = block_args(b0, b1);
+        return core.count_block("ka_ens", f, 1, [&](const KaEnsFamArgs& g) {
+                KaEnsArgs x = a;
+                x.i0 = b0; x.i1 = b1; x.cnt = g.cnt;
+                count(x);
+        }, rowTot, pairCnt, countMs);
+}
+
+// One pass of the table kernels over all rows i of a per-pair list (candidates of a level, or table entries), block by block:
+// count, cut into chunks, hand over.  consume(i0, i1, b0, items, n) takes the rows i0 .. i1 of a chunk (b0: first row of the count
+// block, for pairCnt -- the block's counts on the host, when asked for).
+int ka_ens::stream_rows(const KaEnsArgs& a, const Pass& count, const Pass& write, const Consume& consume, std::vector<int>* pairCnt, double* countMs, double* writeMs, double* waitMs, double* chunks, long long* total)
+{
+        const int N = q.N, rb = count_rows();
+        std::vector<long long> rowTot, rowBase;
         for (int b0 = 0; b0 < N; b0 += rb) {
                 const int b1 = std::min(N, b0 + rb);
-                if (count_rows(a, b0, b1, count, rowTot, pairCnt, countMs)) return KA_FAIL;
-                // chunks of whole rows, each at most chunkCap items (a longer row is a chunk of its own)
-                std::vector<int> cut{ b0 };
-                std::vector<long long> tot;
-                long long run = 0, biggest = 0;
-                for (int i = b0; i < b1; i++) {
-                        const long long t = rowTot[i - b0];
-                        *total += t;
-                        if (run > 0 && run + t > chunkCap) { cut.push_back(i); tot.push_back(run); biggest = std::max(biggest, run); run = 0; }
-                        run += t;
-                }
-                cut.push_back(b1); tot.push_back(run); biggest = std::max(biggest, run);
-                if (biggest > pinnedCap) {
-                        HIPCHK(hipStreamSynchronize(stream));
-                        for (int q = 0; q < 2; q++) {
-                                if (pinned[q]) (void)hipHostFree(pinned[q]);
-                                pinned[q] = nullptr;
-                                HIPCHK(hipHostMalloc((void**)&pinned[q], sizeof(int2) * (size_t)biggest));
-                                if (dOut[q].alloc((size_t)biggest)) return fail("ka_ens: out of device memory (candidates)");
-                        }
-                        pinnedCap = biggest;
-                }
-                const int nChunks = (int)tot.size();
-                auto enqueue = [&](int c) -> int {
-                        const int q = c & 1;
-                        if (tot[c] == 0) return KA_OK;
-                        rowBase[q].assign(cut[c + 1] - cut[c], 0);
-                        // rowBase[i - i0] + pairOff[(i - i0) * N + j]: the write pass indexes both by the launch's i0
-                        long long o = 0;
-                        for (int i = cut[c]; i < cut[c + 1]; i++) { rowBase[q][i - cut[c]] = o; o += rowTot[i - b0]; }
-                        if (dRowBase[q].alloc(rowBase[q].size())) return fail("ka_ens: out of device memory");
-                        HIPCHK(hipMemcpyAsync(dRowBase[q].p, rowBase[q].data(), sizeof(long long) * rowBase[q].size(), hipMemcpyHostToDevice, stream));
+                if (count_table_block(a, b0, b1, count, rowTot, pairCnt, countMs)) return KA_FAIL;
+                std::vector<KaEnsChunk> cut;
+                rowBase.assign((size_t)(b1 - b0), 0);
+                cut_rows(a.level, b0, b1, rowTot.data(), rowBase.data(), cut, total);
+                if (core.put_row_base("ka_ens: out of device memory", rowBase)) return KA_FAIL;
+                const int rc = core.hand_over("ka_ens", cut, [&](const KaEnsChunk& c, int2* out) {
                         KaEnsArgs w = a;
-                        w.i0 = cut[c]; w.i1 = cut[c + 1];
-                        w.pairOff = dPairOff.p + (long long)(cut[c] - b0) * N;
-                        w.rowBase = dRowBase[q].p; w.out = dOut[q].p; w.entOut = reinterpret_cast<uint2*>(dOut[q].p);
-                        HIPCHK(hipEventRecord(wBeg[q], stream));
+                        w.i0 = c.u0; w.i1 = c.u1;
+                        w.pairOff = core.dPairOff.p + (long long)(c.u0 - b0) * N;
+                        w.rowBase = core.dRowBase.p + (c.u0 - b0); w.out = out; w.entOut = reinterpret_cast<uint2*>(out);
                         write(w);
-                        HIPCHK(hipGetLastError());
-                        HIPCHK(hipEventRecord(wEnd[q], stream));
-                        HIPCHK(hipMemcpyAsync(pinned[q], dOut[q].p, sizeof(int2) * (size_t)tot[c], hipMemcpyDeviceToHost, stream));
-                        HIPCHK(hipEventRecord(ready[q], stream));
-                        return KA_OK;
-                };
-                if (enqueue(0)) return KA_FAIL;
-                for (int c = 0; c < nChunks; c++) {
-                        if (c + 1 < nChunks && enqueue(c + 1)) return KA_FAIL;
-                        if (tot[c] == 0) {
-                                if (consume(cut[c], cut[c + 1], b0, (const int2*)nullptr, 0LL)) return KA_FAIL;
-                                continue;
-                        }
-                        const auto t0 = clk::now();
-                        HIPCHK(hipEventSynchronize(ready[c & 1]));
-                        *waitMs += ms_since(t0);
-                        float wms = 0.0f;
-                        (void)hipEventElapsedTime(&wms, wBeg[c & 1], wEnd[c & 1]);
-                        *writeMs += wms;
-                        if (consume(cut[c], cut[c + 1], b0, pinned[c & 1], tot[c])) return KA_FAIL;
-                        *chunks += 1;
-                }
+                }, [&](const KaEnsChunk& c, const int2* p) { return consume(c.u0, c.u1, b0, p, c.total); }, writeMs, waitMs, chunks);
+                if (rc) return rc;
         }
         return KA_OK;
 }
@@ -273,35 +533,79 @@ int ka_ens::stream_rows(KaEnsArgs a, Count count, Write write, Consume consume, 
 int ka_ens::consensus(int minSup, const uint8_t* letters)
 {
         using clk = std::chrono::steady_clock;
-        const int T = q.T;
+        const int T = q.T, N = q.N;
         const std::vector<int>& lens = q.lens;
         const std::vector<int>& offs = q.offs;
         st[2] = st[3] = st[4] = st[5] = st[7] = st[8] = st[9] = 0.0;
         std::fill_n(levelCount, KA_ENS_MAX_RUNS + 1, 0LL);
         std::fill_n(levelMs, KA_ENS_MAX_RUNS + 1, 0.0);
         if (ensure_maps()) return KA_FAIL;
-        KaEnsArgs a = args();
         Uf uf;
         uf.init(offs, lens, T);
-        for (int L = R; L >= std::max(minSup, 1); L--) {
-                a.level = L;
-                double cms = 0.0, wms = 0.0;
-                const int rc = stream_rows(a, [&](const KaEnsArgs& x) { launch_support(KA_ENS_COUNT, x); }, [&](const KaEnsArgs& x) { launch_support(KA_ENS_WRITE, x); },
-                                           [&](int, int, int, const int2* p, long long n) {
-                                                   const auto t1 = clk::now();
-                                                   for (long long x = 0; x < n; x++) uf.join(p[x].x, p[x].y);
-                                                   st[4] += ms_since(t1);
-                                                   return KA_OK;
-                                           }, nullptr, &cms, &wms, &st[7], &st[8], &levelCount[L]);
-                if (rc) return rc;
-                st[2] += cms; st[3] += wms; levelMs[L] += cms + wms;
+        const int lo = std::max(minSup, 1), nLev = R - lo + 1, rb = count_rows();
+        auto join = [&](const int2* p, long long n) {
+                const auto t1 = clk::now();
+                for (long long x = 0; x < n; x++) uf.join(p[x].x, p[x].y);
+                st[4] += ka_ens_ms_since(t1);
+                return KA_OK;
+        };
+        hipStream_t s = core.stream;
+        if (fromTable) {
+                // the table's entries with popcount == level: counted and written level by level
+                KaEnsArgs a = args();
+                for (int L = R; L >= lo; L--) {
+                        a.level = L;
+                        double cms = 0.0, wms = 0.0;
+                        const int rc = stream_rows(a, [s](const KaEnsArgs& x) { ka_poar_launch_level(KA_ENS_COUNT, x, s); },
+                                                   [s](const KaEnsArgs& x) { ka_poar_launch_level(KA_ENS_WRITE, x, s); },
+                                                   [&](int, int, int, const int2* p, long long n) { return join(p, n); }, nullptr, &cms, &wms, &st[7], &st[8],
+                                                   &levelCount[L]);
+                        if (rc) return rc;
+                        st[2] += cms; st[3] += wms; levelMs[L] += cms + wms;
+                }
+        } else if (nLev > 0) {
+                // the walk counts every level of a block of rows in one pass; with one block (any N up to 4096) that is one count pass
+                // in all, with more the block is counted again for each level (the levels go highest first over ALL rows)
+                core.fams[0].minSup = lo;
+                HIPCHK(hipMemcpyAsync(core.dFams.p, core.fams.data(), sizeof(KaEnsFam), hipMemcpyHostToDevice, s));
+                std::vector<long long> rowTot, rowBase;
+                std::vector<std::vector<KaEnsChunk>> cut((size_t)nLev);     // of the counted block, per level
+                std::vector<long long> levTot((size_t)nLev);
+                KaEnsFamArgs f{};
+                for (int L = R; L >= lo; L--)
+                        for (int b0 = 0; b0 < N; b0 += rb) {
+                                const int b1 = std::min(N, b0 + rb), rows = b1 - b0;
+                                if (L == R || rb < N) {
+                                        f = block_args(b0, b1);
+                                        if (core.count_block("ka_ens", f, nLev, [&](const KaEnsFamArgs& g) { ka_ens_launch_walk(KA_ENS_COUNT, g, rows * core.fams[0].nJC, core.ldsCand, s); },
+                                                             rowTot, nullptr, &st[2]))
+                                                return KA_FAIL;
+                                        rowBase.assign(rowTot.size(), 0);
+                                        for (int lv = 0; lv < nLev; lv++) {
+                                                cut[lv].clear();
+                                                levTot[lv] = 0;
+                                                cut_rows(R - lv, b0, b1, rowTot.data() + (size_t)lv * rows, rowBase.data() + (size_t)lv * rows, cut[lv], &levTot[lv]);
+                                        }
+                                        if (core.put_row_base("ka_ens: out of device memory", rowBase)) return KA_FAIL;
+                                        f.rowBase = core.dRowBase.p;
+                                }
+                                double wms = 0.0;
+                                levelCount[L] += levTot[R - L];
+                                const int rc = core.hand_over("ka_ens", cut[R - L], [&](const KaEnsChunk& c, int2* out) {
+                                        KaEnsFamArgs w = f;
+                                        w.blk0 = c.blk0; w.level = c.level; w.out = out;
+                                        ka_ens_launch_walk(KA_ENS_WRITE, w, c.nBlk, core.ldsCand, s);
+                                }, [&](const KaEnsChunk& c, const int2* p) { return join(p, c.total); }, &wms, &st[7], &st[8]);
+                                if (rc) return rc;
+                                st[3] += wms; levelMs[L] += wms;
+                        }
         }
         st[9] = (double)uf.truncations;
         // columns numbered by first residue, ordered, filled
         const auto tt = clk::now();
         int nCols = 0;
         ka_ens_fill(uf, offs, lens, T, letters, cacheRows, &nCols);
-        st[5] = ms_since(tt);
+        st[5] = ka_ens_ms_since(tt);
         cacheW = nCols; cacheMin = minSup; cacheGen = generation;
         cacheLetters.assign(letters, letters + T);
         return KA_OK;
@@ -331,14 +635,15 @@ int ka_ens::table_count(long long* entries)
         if (fromTable) { *entries = tabEntries; return KA_OK; }
         if (ensure_maps()) return KA_FAIL;
         if (tabCountGen != generation) {
-                KaEnsArgs a = args();
-                const int N = q.N, rb = ens_count_block(N);
+                const KaEnsArgs a = args();
+                const int N = q.N, rb = count_rows();
+                hipStream_t s = core.stream;
                 std::vector<long long> rowTot;
                 long long total = 0;
                 double ms = 0.0;
                 for (int b0 = 0; b0 < N; b0 += rb) {
                         const int b1 = std::min(N, b0 + rb);
-                        if (count_rows(a, b0, b1, [&](const KaEnsArgs& x) { ka_poar_launch_table(KA_ENS_COUNT, x, stream); }, rowTot, nullptr, &ms)) return KA_FAIL;
+                        if (count_table_block(a, b0, b1, [s](const KaEnsArgs& x) { ka_poar_launch_table(KA_ENS_COUNT, x, s); }, rowTot, nullptr, &ms)) return KA_FAIL;
                         for (int i = b0; i < b1; i++) total += rowTot[i - b0];
                 }
                 tabEntries = total;
@@ -357,6 +662,7 @@ int ka_ens::table_emit(Sink* sink)
         KaEnsArgs a = args();
         a.level = 0;
         const int N = q.N;
+        hipStream_t stream = core.stream;
         std::fill_n(tab, KA_ENS_TABLE_STATS, 0.0);
         const uint32_t head[4] = { 0x524F4150u, 1u, (uint32_t)N, (uint32_t)R };
         if (sink->put(head, sizeof head)) return KA_FAIL;
@@ -375,7 +681,7 @@ int ka_ens::table_emit(Sink* sink)
                                         if (c && sink->put(p + o, 8 * (size_t)c)) return KA_FAIL;
                                         o += c;
                                 }
-                        tab[2] += ms_since(t0);
+                        tab[2] += ka_ens_ms_since(t0);
                         return KA_OK;
                 }, &cnt, &tab[0], &tab[1], &tab[5], &tab[4], &total);
         if (rc) return rc;
@@ -392,8 +698,8 @@ int ka_ens::load_table(const uint8_t* image, long long nBytes)
         std::vector<long long> ps;
         int runs = 0;
         if (ka_poar_parse(image, nBytes, q.N, q.lens.data(), &runs, &tabEntries, &ps)) return KA_FAIL;
-        R = runs;
-        W.assign(R, 0);
+        if (open("ka_ens_open_table", runs)) return KA_FAIL;
+        hipStream_t stream = core.stream;
         fromTable = true;
         std::vector<uint2> ent((size_t)tabEntries);
         long long at = 16;
@@ -406,22 +712,21 @@ int ka_ens::load_table(const uint8_t* image, long long nBytes)
         HIPCHK(hipMemcpyAsync(dPairStart.p, ps.data(), sizeof(long long) * ps.size(), hipMemcpyHostToDevice, stream));
         if (tabEntries) HIPCHK(hipMemcpyAsync(dEnt.p, ent.data(), sizeof(uint2) * (size_t)tabEntries, hipMemcpyHostToDevice, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        tab[2] = ms_since(t0);
+        tab[2] = ka_ens_ms_since(t0);
         tab[3] = (double)tabEntries;
         return KA_OK;
 }
 
 // rows b0 .. b1 as count_rows left them (dPairOff, rowTot): the first entry of each of their pairs into pairStart, where *run
-// entries lie before row b0; the rows' own first entries stay in dRowBase[0], and *run moves on to row b1
+// entries lie before row b0; the rows' own first entries stay in core.dRowBase, and *run moves on to row b1
 int ka_ens::pair_starts(int b0, int b1, const std::vector<long long>& rowTot, long long* run, long long* pairStart)
 {
         std::vector<long long> base((size_t)(b1 - b0));
         for (int i = b0; i < b1; i++) { base[i - b0] = *run; *run += rowTot[i - b0]; }
-        if (dRowBase[0].alloc(base.size())) return fail("ka_ens: out of device memory");
-        HIPCHK(hipMemcpyAsync(dRowBase[0].p, base.data(), sizeof(long long) * base.size(), hipMemcpyHostToDevice, stream));
-        ka_poar_launch_pair_start(dPairOff.p, dRowBase[0].p, b0, b1, q.N, pairStart, stream);
+        if (core.put_row_base("ka_ens: out of device memory", base)) return KA_FAIL;
+        ka_poar_launch_pair_start(core.dPairOff.p, core.dRowBase.p, b0, b1, q.N, pairStart, core.stream);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipStreamSynchronize(core.stream));
         return KA_OK;
 }
 
@@ -432,20 +737,22 @@ int ka_ens::table_on_device(DevBuf<long long>& ps, DevBuf<uint2>& ent, TabRef* t
         if (fromTable) { *t = TabRef{ dPairStart.p, dEnt.p, tabEntries }; return KA_OK; }
         long long total = 0;
         if (table_count(&total)) return KA_FAIL;
-        const int N = q.N, rb = ens_count_block(N);
+        const int N = q.N, rb = count_rows();
+        hipStream_t stream = core.stream;
         const long long nPairs = (long long)N * (N - 1) / 2;
         if (ps.alloc((size_t)nPairs + 1) || ent.alloc((size_t)std::max(total, 1LL)))
                 return fail("ka_ens: out of device memory (the table of a member-backed operand, " + std::to_string(total) + " entries)");
-        KaEnsArgs a = args();
+        const KaEnsArgs a = args();
         std::vector<long long> rowTot;
         long long run = 0;
         double ms = 0.0;
         for (int b0 = 0; b0 < N; b0 += rb) {
                 const int b1 = std::min(N, b0 + rb);
-                if (count_rows(a, b0, b1, [&](const KaEnsArgs& x) { ka_poar_launch_table(KA_ENS_COUNT, x, stream); }, rowTot, nullptr, &ms)) return KA_FAIL;
+                if (count_table_block(a, b0, b1, [stream](const KaEnsArgs& x) { ka_poar_launch_table(KA_ENS_COUNT, x, stream); }, rowTot, nullptr, &ms)) return KA_FAIL;
                 if (pair_starts(b0, b1, rowTot, &run, ps.p)) return KA_FAIL;
                 KaEnsArgs w = a;
-                w.pairOff = dPairOff.p; w.rowBase = dRowBase[0].p; w.entOut = ent.p;
+                w.i0 = b0; w.i1 = b1;
+                w.pairOff = core.dPairOff.p; w.rowBase = core.dRowBase.p; w.entOut = ent.p;
                 ka_poar_launch_table(KA_ENS_WRITE, w, stream);
                 HIPCHK(hipGetLastError());
         }
@@ -458,10 +765,10 @@ int ka_ens::table_on_device(DevBuf<long long>& ps, DevBuf<uint2>& ent, TabRef* t
 
 // this handle's table from launch(COUNT / WRITE, args): a is ready but for what the passes fill in.  COUNT gives every pair its
 // size, so the pairs' first entries are known before the one WRITE pass, which reads them (a.outStart) as the table's reader will.
-template <class Launch>
-int ka_ens::derive_table(const char* who, KaEnsArgs a, Launch launch)
+int ka_ens::derive_table(const char* who, KaEnsArgs a, const std::function<void(int, const KaEnsArgs&)>& launch)
 {
-        const int N = q.N, rb = ens_count_block(N);
+        const int N = q.N, rb = count_rows();
+        hipStream_t stream = core.stream;
         const long long nPairs = (long long)N * (N - 1) / 2;
         if (dPairStart.alloc((size_t)nPairs + 1)) return fail(std::string(who) + ": out of device memory (the table)");
         std::fill_n(tab, KA_ENS_TABLE_STATS, 0.0);
@@ -469,45 +776,33 @@ int ka_ens::derive_table(const char* who, KaEnsArgs a, Launch launch)
         long long run = 0;
         for (int b0 = 0; b0 < N; b0 += rb) {
                 const int b1 = std::min(N, b0 + rb);
-                if (count_rows(a, b0, b1, [&](const KaEnsArgs& x) { launch(KA_ENS_COUNT, x); }, rowTot, nullptr, &tab[0])) return KA_FAIL;
+                if (count_table_block(a, b0, b1, [&](const KaEnsArgs& x) { launch(KA_ENS_COUNT, x); }, rowTot, nullptr, &tab[0])) return KA_FAIL;
                 if (pair_starts(b0, b1, rowTot, &run, dPairStart.p)) return KA_FAIL;
         }
         if (dEnt.alloc((size_t)std::max(run, 1LL))) return fail(std::string(who) + ": out of device memory (the table, " + std::to_string(run) + " entries)");
         HIPCHK(hipMemcpyAsync(dPairStart.p + nPairs, &run, sizeof(long long), hipMemcpyHostToDevice, stream));
         a.i0 = 0; a.i1 = N;
         a.outStart = dPairStart.p; a.entOut = dEnt.p;
-        HIPCHK(hipEventRecord(ev0, stream));
+        HIPCHK(hipEventRecord(core.ev0, stream));
         launch(KA_ENS_WRITE, a);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev1, stream));
+        HIPCHK(hipEventRecord(core.ev1, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        tab[1] = evMs();
+        tab[1] = core.evMs();
         tabEntries = run;
         tab[3] = (double)run;
         return KA_OK;
 }
 
-// a handle on ctx's device and stream for these sequences, without a source of support yet
+// a handle for these sequences, without a source of support yet (ka_ens::open follows once n_runs is known)
 static int ens_new(const char* who, ka_ctx* ctx, int numseq, const int* lens, std::unique_ptr<ka_ens>& e)
 {
         e.reset(new ka_ens);
         e->ctx = ctx;
-        if (ka_ctx_device_stream(ctx, &e->device, &e->stream)) return fail(std::string(who) + ": bad context");
-        HIPCHK(hipSetDevice(e->device));
-        if (e->q.init(who, numseq, lens, KA_ENS_MAX_RES,
-                      "residue indices must stay below 4096 (the reference's POAR key ri << 20 | rj aliases beyond)"))
-                return KA_FAIL;
-        const char* cc = std::getenv("KA_ENS_CHUNK");                    // candidates per chunk (tests force many chunks)
-        e->chunkCap = cc && std::atoll(cc) > 0 ? std::atoll(cc) : (1ll << 22);
-        if (e->dScore.alloc(1)) return fail(std::string(who) + ": out of device memory");
-        for (int b = 0; b < 2; b++) {
-                HIPCHK(hipEventCreateWithFlags(&e->ready[b], hipEventDisableTiming));
-                HIPCHK(hipEventCreate(&e->wBeg[b]));
-                HIPCHK(hipEventCreate(&e->wEnd[b]));
-        }
-        HIPCHK(hipEventCreate(&e->ev0));
-        HIPCHK(hipEventCreate(&e->ev1));
-        return KA_OK;
+        int device = 0;
+        hipStream_t stream = nullptr;
+        if (ka_ctx_device_stream(ctx, &device, &stream)) return fail(std::string(who) + ": bad context");
+        return e->q.set(who, numseq, lens, KA_ENS_MAX_RES, "residue indices must stay below 4096 (the reference's POAR key ri << 20 | rj aliases beyond)");
 }
 
 extern "C" int ka_ens_create(ka_ctx* ctx, int numseq, const int* lens, int n_runs, ka_ens** out)
@@ -517,10 +812,7 @@ extern "C" int ka_ens_create(ka_ctx* ctx, int numseq, const int* lens, int n_run
                 return fail("ka_ens_create: n_runs " + std::to_string(n_runs) + " outside 1.." + std::to_string(KA_ENS_MAX_RUNS) + " (one bit per member in the reference's POAR table)");
         *out = nullptr;
         std::unique_ptr<ka_ens> e;
-        if (ens_new("ka_ens_create", ctx, numseq, lens, e)) return KA_FAIL;
-        e->R = n_runs;
-        e->W.assign(n_runs, 0);
-        e->rows.resize(n_runs);
+        if (ens_new("ka_ens_create", ctx, numseq, lens, e) || e->open("ka_ens_create", n_runs)) return KA_FAIL;
         *out = e.release();
         return KA_OK;
 }
@@ -528,8 +820,7 @@ extern "C" int ka_ens_create(ka_ctx* ctx, int numseq, const int* lens, int n_run
 extern "C" void ka_ens_destroy(ka_ens* e)
 {
         if (!e) return;
-        (void)hipSetDevice(e->device);
-        (void)hipStreamSynchronize(e->stream);
+        e->core.close();
         delete e;
 }
 
@@ -538,12 +829,12 @@ extern "C" int ka_ens_add_member(ka_ens* e, int k, const uint8_t* rows, long lon
         if (e && e->fromTable) return fail("ka_ens_add_member: this handle was opened from a POAR table and takes no members");
         if (!e || k < 0 || k >= e->R) return fail("ka_ens_add_member: bad arguments");
         if (ka_msa_check_rows("ka_ens_add_member", e->q, rows, row_stride, alnlen)) return KA_FAIL;
-        HIPCHK(hipSetDevice(e->device));
-        if (e->rows[k].alloc((size_t)e->q.N * alnlen)) return fail("ka_ens_add_member: out of device memory");
-        if (ka_msa_upload_rows(e->q, e->rows[k].p, rows, row_stride, alnlen, e->stream)) return KA_FAIL;
-        HIPCHK(hipStreamSynchronize(e->stream));
-        e->W[k] = alnlen;
-        e->mapsFresh = false;
+        if (e->core.member_fits("ka_ens_add_member", k, &alnlen)) return KA_FAIL;
+        HIPCHK(hipSetDevice(e->core.device));
+        if (e->core.dRows[k].alloc((size_t)e->q.N * alnlen)) return fail("ka_ens_add_member: out of device memory");
+        if (ka_msa_upload_rows(e->q, e->core.dRows[k].p, rows, row_stride, alnlen, e->core.stream)) return KA_FAIL;
+        if (e->core.member_added(k, &alnlen)) return KA_FAIL;
+        HIPCHK(hipStreamSynchronize(e->core.stream));
         e->generation++;
         return KA_OK;
 }
@@ -552,30 +843,18 @@ extern "C" int ka_ens_score_rows(ka_ens* e, const uint8_t* rows, long long row_s
 {
         if (!e) return fail("ka_ens_score_rows: bad arguments");
         if (ka_msa_check_rows("ka_ens_score_rows", e->q, rows, row_stride, alnlen)) return KA_FAIL;
-        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipSetDevice(e->core.device));
         if (e->ensure_maps()) return KA_FAIL;
-        KaEnsArgs a = e->args();
-        HIPCHK(hipEventRecord(e->ev0, e->stream));
-        if (e->maps_x(rows, row_stride, alnlen, a)) return KA_FAIL;
-        HIPCHK(hipMemsetAsync(e->dScore.p, 0, sizeof(unsigned long long), e->stream));
-        a.score = e->dScore.p;
-        e->launch_support(KA_ENS_SCORE, a);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e->ev1, e->stream));
-        unsigned long long s = 0;
-        HIPCHK(hipMemcpyAsync(&s, e->dScore.p, sizeof(s), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        e->st[1] = e->evMs();
-        const long long S = (long long)s;
-        if (sum_out) *sum_out = S;
-        if (score_out) *score_out = (double)S / (e->R > 1 ? (double)(e->R - 1) : 1.0);
-        return KA_OK;
+        const KaEnsSupport table = e->lookup(KA_ENS_SCORE, alnlen);
+        const int rc = e->core.score_x("ka_ens_score_rows", &alnlen, e->upload(rows, row_stride, alnlen), e->fromTable ? &table : nullptr, sum_out, score_out);
+        e->st[1] = e->core.scoreMs;
+        return rc;
 }
 
 extern "C" int ka_ens_consensus(ka_ens* e, int min_support, const uint8_t* letters, uint8_t* rows_out, long long row_stride, int* alnlen_out)
 {
         if (!e || !letters || min_support < 1) return fail("ka_ens_consensus: bad arguments (min_support >= 1, letters)");
-        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipSetDevice(e->core.device));
         const bool cached = e->cacheGen == e->generation && e->cacheMin == min_support &&
                             std::equal(e->cacheLetters.begin(), e->cacheLetters.end(), letters) && (int)e->cacheLetters.size() == e->q.T;
         if (!cached && e->consensus(min_support, letters)) return KA_FAIL;
@@ -590,26 +869,12 @@ extern "C" int ka_ens_confidence(ka_ens* e, const uint8_t* rows, long long row_s
 {
         if (!e || !res_conf_out || !col_conf_out) return fail("ka_ens_confidence: bad arguments");
         if (ka_msa_check_rows("ka_ens_confidence", e->q, rows, row_stride, alnlen)) return KA_FAIL;
-        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipSetDevice(e->core.device));
         if (e->ensure_maps()) return KA_FAIL;
-        KaEnsArgs a = e->args();
-        HIPCHK(hipEventRecord(e->ev0, e->stream));
-        if (e->maps_x(rows, row_stride, alnlen, a)) return KA_FAIL;
-        if (e->dSup.alloc((size_t)std::max(e->q.T, 1)) || e->dNp.alloc((size_t)std::max(e->q.T, 1)) ||
-            e->dConf.alloc((size_t)e->q.N * alnlen) || e->dColConf.alloc((size_t)alnlen))
-                return fail("ka_ens_confidence: out of device memory");
-        HIPCHK(hipMemsetAsync(e->dSup.p, 0, sizeof(int) * (size_t)std::max(e->q.T, 1), e->stream));
-        HIPCHK(hipMemsetAsync(e->dNp.p, 0, sizeof(int) * (size_t)std::max(e->q.T, 1), e->stream));
-        a.supSum = e->dSup.p; a.nPair = e->dNp.p;
-        e->launch_support(KA_ENS_CONF, a);
-        ka_ens_launch_conf(a, e->dConf.p, e->dColConf.p, e->stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e->ev1, e->stream));
-        HIPCHK(hipMemcpyAsync(res_conf_out, e->dConf.p, sizeof(float) * (size_t)e->q.N * alnlen, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipMemcpyAsync(col_conf_out, e->dColConf.p, sizeof(float) * (size_t)alnlen, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        e->st[6] = e->evMs();
-        return KA_OK;
+        const KaEnsSupport table = e->lookup(KA_ENS_CONF, alnlen);
+        const int rc = e->core.confidence("ka_ens_confidence", &alnlen, e->upload(rows, row_stride, alnlen), e->fromTable ? &table : nullptr, res_conf_out, col_conf_out);
+        e->st[6] = e->core.confMs;
+        return rc;
 }
 
 extern "C" int ka_ens_stats(ka_ens* e, double* stats_out, long long* level_counts_out, double* level_ms_out)
@@ -626,7 +891,7 @@ extern "C" int ka_ens_n_runs(ka_ens* e) { return e ? e->R : 0; }
 extern "C" int ka_ens_table_size(ka_ens* e, long long* bytes_out, long long* entries_out)
 {
         if (!e) return fail("ka_ens_table_size: bad arguments");
-        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipSetDevice(e->core.device));
         long long n = 0;
         if (e->table_count(&n)) return KA_FAIL;
         if (bytes_out) *bytes_out = 16 + 4 * ((long long)e->q.N * (e->q.N - 1) / 2) + 8 * n;
@@ -637,7 +902,7 @@ extern "C" int ka_ens_table_size(ka_ens* e, long long* bytes_out, long long* ent
 extern "C" int ka_ens_table_write(ka_ens* e, const char* path)
 {
         if (!e || !path) return fail("ka_ens_table_write: bad arguments");
-        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipSetDevice(e->core.device));
         if (e->ensure_maps()) return KA_FAIL;
         ka_ens::Sink sink;
         sink.fp = std::fopen(path, "wb");
@@ -651,7 +916,7 @@ extern "C" int ka_ens_table_write(ka_ens* e, const char* path)
 extern "C" int ka_ens_table_image(ka_ens* e, uint8_t* out, long long cap)
 {
         if (!e || !out || cap < 0) return fail("ka_ens_table_image: bad arguments");
-        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipSetDevice(e->core.device));
         ka_ens::Sink sink;
         sink.mem = out; sink.cap = cap;
         return e->table_emit(&sink);
@@ -687,9 +952,7 @@ extern "C" int ka_ens_open_table(ka_ctx* ctx, int numseq, const int* lens, const
 // a table-backed handle of n_runs members for the sequences of `like`, its table still to come (derive_table)
 static int ens_new_result(const char* who, const ka_ens* like, int n_runs, std::unique_ptr<ka_ens>& o)
 {
-        if (ens_new(who, like->ctx, like->q.N, like->q.lens.data(), o)) return KA_FAIL;
-        o->R = n_runs;
-        o->W.assign(n_runs, 0);
+        if (ens_new(who, like->ctx, like->q.N, like->q.lens.data(), o) || o->open(who, n_runs)) return KA_FAIL;
         o->fromTable = true;
         return KA_OK;
 }
@@ -708,7 +971,7 @@ extern "C" int ka_ens_merge(ka_ens* a, ka_ens* b, ka_ens** out)
         if (a->R + b->R > KA_ENS_MAX_RUNS)
                 return fail("ka_ens_merge: " + std::to_string(a->R) + " + " + std::to_string(b->R) + " members exceed " + std::to_string(KA_ENS_MAX_RUNS) +
                             " (one bit per member in the reference's POAR table)");
-        HIPCHK(hipSetDevice(a->device));
+        HIPCHK(hipSetDevice(a->core.device));
         DevBuf<long long> psA, psB;
         DevBuf<uint2> entA, entB;
         ka_ens::TabRef ta{}, tb{};
@@ -721,7 +984,7 @@ extern "C" int ka_ens_merge(ka_ens* a, ka_ens* b, ka_ens** out)
                 x.pairStart = ta.pairStart; x.ent = ta.ent;
                 x.pairStartB = tb.pairStart; x.entB = tb.ent;
                 x.shift = a->R;
-                hipStream_t s = o->stream;
+                hipStream_t s = o->core.stream;
                 rc = o->derive_table(who, x, [s](int mode, const KaEnsArgs& y) { ka_poar_launch_merge(mode, y, s); });
         }
         psA.release(); psB.release(); entA.release(); entB.release();
@@ -742,7 +1005,7 @@ extern "C" int ka_ens_select(ka_ens* e, const int* members, int n, ka_ens** out)
                 if (seen >> members[t] & 1u) return fail("ka_ens_select: member " + std::to_string(members[t]) + " given twice");
                 seen |= 1u << members[t];
         }
-        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipSetDevice(e->core.device));
         DevBuf<long long> ps;
         DevBuf<uint2> ent;
         ka_ens::TabRef te{};
@@ -754,7 +1017,7 @@ extern "C" int ka_ens_select(ka_ens* e, const int* members, int n, ka_ens** out)
                 x.pairStart = te.pairStart; x.ent = te.ent;
                 x.nSel = n;
                 for (int t = 0; t < n; t++) x.sel[t] = (unsigned char)members[t];
-                hipStream_t s = o->stream;
+                hipStream_t s = o->core.stream;
                 rc = o->derive_table(who, x, [s](int mode, const KaEnsArgs& y) { ka_poar_launch_select(mode, y, s); });
         }
         ps.release(); ent.release();

@@ -1,4 +1,4 @@
-// ka_ens.h -- the ensemble consensus stage (ka_ens.hip kernels, ka_ens.cpp host side): what the two units share.
+// ka_ens.h -- the ensemble consensus stage (ka_ens.hip and ka_poar.hip kernels; ka_ens.cpp, ka_ens_fam.cpp host side): what the units share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,11 +61,7 @@ __device__ __forceinline__ int ens_wave_incl_scan(int v, int lane)
 // index of pair (i, j), i < j, in the table's order (poar.c's pair_index)
 __host__ __device__ inline long long ka_poar_pair(int i, int j, int N) { return (long long)i * N - (long long)i * (i + 1) / 2 + (j - i - 1); }
 
-// ka_ens.hip
-void ka_ens_launch_walk(int mode, const KaEnsArgs& a, hipStream_t s);
-void ka_ens_launch_row_scan(const int* cnt, int N, long long* pairOff, long long* rowTot, int rows, hipStream_t s);
-void ka_ens_launch_conf(const KaEnsArgs& a, float* conf, float* colConf, hipStream_t s);
-// ka_poar.hip: the same modes and launch geometry as ka_ens_launch_walk
+// ka_poar.hip: the walk's modes, over rows i0 .. i1 of one family (a workgroup per sequence i and KA_ENS_JCHUNK sequences j)
 void ka_poar_launch_table(int mode, const KaEnsArgs& a, hipStream_t s);       // COUNT / WRITE: the members' table, pair by pair
 void ka_poar_launch_level(int mode, const KaEnsArgs& a, hipStream_t s);       // COUNT / WRITE over a loaded table: the entries with
                                                                               // popcount == level as candidates; level 0: every entry, as it is
@@ -77,7 +73,8 @@ void ka_poar_launch_pair_start(const long long* pairOff, const long long* rowBas
 // ka_poar.cpp: the checks of ka_poar_check_image; also fills the pairs' first entries (n_pairs + 1) when asked
 int ka_poar_parse(const uint8_t* image, long long nBytes, int numseq, const int* lens, int* nRuns, long long* entries, std::vector<long long>* pairStart);
 
-// ---- a batch of families with the same number of members (ka_ens_fam.hip kernels, ka_ens_fam.cpp host side) ----
+// ---- the walk's tables (ka_ens.hip kernels, KaEnsCore in ka_ens_core.h): a batch of families with the same number of members;
+// one family is a batch of one ----
 // Sequences and residues are numbered flat over the batch; a table named first...[nFam + 1] ascends and is searched for the
 // family of a flat index.  The residues a candidate names are numbered inside its family.
 struct KaEnsFam {
@@ -107,9 +104,11 @@ struct KaEnsFamArgs {
         const int* xCell;          // [nFam + 1]
         const int* xW;             // [nFam]; <= 0: the family is skipped
         const int* xCol;           // [nFam + 1] CONF: columns of the families before f
-        int blk0;                  // first workgroup of this launch (WRITE: the first of the chunk's families)
+        int blk0;                  // first workgroup of this launch (COUNT: of the counted rows; WRITE: of the chunk)
         int level;                 // WRITE: support value of the candidates
-        long long E;               // entries of one level of the count table (level n_runs - lv at lv * E; its rows at lv * S)
+        // the count table of a launch holds the flat rows row0 .. row0 + rows alone: level n_runs - lv at lv * E, its rows at lv * rows
+        int row0, rows;
+        long long E, cnt0;         // entries of one level; the entry (cntFirst + il * N) of row0 in a table of all rows
         unsigned long long* score; // SCORE: [nFam]
         int* supSum;               // CONF: [T]
         int* nPair;                // CONF: [T]
@@ -119,9 +118,7 @@ struct KaEnsFamArgs {
         int2* out;                 // WRITE: (residue of i, residue of j), numbered inside the family
 };
 
-// ka_ens_fam.hip
-void ka_ensf_launch_maps(const KaEnsFamArgs& a, const uint8_t* rows, const long long* rowOff, const int* W, const int* cell, int* col, int16_t* res,
-                         hipStream_t s);                                       // rows of family f at rowOff[f], W[f] + 1 bytes apart
-void ka_ensf_launch_walk(int mode, const KaEnsFamArgs& a, int nBlocks, size_t lds, hipStream_t s);
-void ka_ensf_launch_row_scan(const KaEnsFamArgs& a, int nRows, long long* pairOff, long long* rowTot, hipStream_t s);
-void ka_ensf_launch_conf(const KaEnsFamArgs& a, int cells, int cols, float* conf, float* colConf, hipStream_t s);
+// ka_ens.hip
+void ka_ens_launch_walk(int mode, const KaEnsFamArgs& a, int nBlocks, size_t lds, hipStream_t s);
+void ka_ens_launch_row_scan(const KaEnsFamArgs& a, int nRows, long long* pairOff, long long* rowTot, hipStream_t s);   // nRows = levels * a.rows
+void ka_ens_launch_conf(const KaEnsFamArgs& a, int cells, int cols, float* conf, float* colConf, hipStream_t s);

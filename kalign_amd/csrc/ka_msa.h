@@ -55,24 +55,23 @@ __device__ __forceinline__ void ka_msa_map_row(const uint8_t* row, int W, int re
         }
 }
 
-// the sequences whose rows the alignments hold: lengths and flat residue numbering, here and on the device
+// the sequences whose rows the alignments hold: lengths and flat residue numbering, on the host
 struct KaSeqSet {
         int N = 0, T = 0, maxlen = 0;          // sequences, residues, longest sequence
         std::vector<int> lens, offs;           // offs[s]: first residue of sequence s in the flat numbering, offs[N] = T
-        int* dOffs = nullptr;                  // [N + 1]
-        int* dLens = nullptr;                  // [N]
 
         // checks the lengths (none negative, none above max_res -- `why` ends that message --, fewer than 2^31 residues
-        // in all) and numbers the residues, on the host alone; errors read "<who>: ..."
+        // in all) and numbers the residues; errors read "<who>: ..."
         int set(const char* who, int numseq, const int* lens, int max_res, const char* why);
-        // set(), then the lengths copied to the current device
-        int init(const char* who, int numseq, const int* lens, int max_res, const char* why);
-        void release();
 };
 
 // rows of an alignment of the set: alnlen columns fit the stride, row s holds lens[s] letters
 int ka_msa_check_rows(const char* who, const KaSeqSet& q, const uint8_t* rows, long long stride, int alnlen);
 // the rows to N x alnlen bytes at dst, stream-ordered
 int ka_msa_upload_rows(const KaSeqSet& q, uint8_t* dst, const uint8_t* rows, long long stride, int alnlen, hipStream_t s);
-// both maps of N x W device rows (row stride rowStride); res gets resStride >= W entries per row, -1 at gaps and from W on
-void ka_msa_launch_maps(const uint8_t* rows, int rowStride, int W, int resStride, const KaSeqSet& q, int* col, int16_t* res, hipStream_t s);
+// both maps of the device rows of a batch of families whose S sequences are numbered flat (device tables; one alignment is a
+// batch of one): the rows of family f at rowOff[f], W[f] + rowPad bytes apart (W[f] <= 0: none), its res rows W[f] entries
+// each from res + cell[f], -1 at gaps
+struct KaMsaFamRows { int nFam, S; const int* firstSeq; const int* offs; const int* lens; };
+void ka_msa_launch_maps_fam(const KaMsaFamRows& t, const uint8_t* rows, const long long* rowOff, const int* W, const int* cell, int rowPad, int* col,
+                            int16_t* res, hipStream_t s);

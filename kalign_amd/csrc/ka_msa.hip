@@ -6,18 +6,25 @@
 #define MSA_THREADS 256
 #define MSA_WAVES (MSA_THREADS / 64)
 
-// one wave per row (ka_msa_map_row): res[s][c] for every column of the res row, col[offs[s] + r] for every residue
-__global__ __launch_bounds__(MSA_THREADS) void msa_maps(const uint8_t* rows, int rowStride, int W, int resStride, int N, const int* offs,
-                                                        const int* lens, int* col, int16_t* res)
+// one wave per row (ka_msa_map_row): res[c] for every column of the row's res row, col[offs[s] + r] for every residue.  The rows
+// are those of a batch of families, numbered flat (one alignment is a batch of one): a wave finds the family of its row
+// (ka_fam_find), then the row's own start, width and place in res
+__global__ __launch_bounds__(MSA_THREADS) void msa_maps_fam(KaMsaFamRows t, const uint8_t* rows, const long long* rowOff, const int* Wt, const int* cell,
+                                                            int rowPad, int* col, int16_t* res)
 {
         const int s = blockIdx.x * MSA_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-        if (s >= N) return;
-        ka_msa_map_row(rows + (long long)s * rowStride, W, resStride, lens[s], col + offs[s], res + (long long)s * resStride, lane);
+        if (s >= t.S) return;
+        const int f = ka_fam_find(t.firstSeq, t.nFam, s);
+        const int W = Wt[f];
+        if (W <= 0) return;                                      // (a family without rows in this batch)
+        const int loc = s - t.firstSeq[f];
+        ka_msa_map_row(rows + rowOff[f] + (long long)loc * (W + rowPad), W, W, t.lens[s], col + t.offs[s], res + cell[f] + (long long)loc * W, lane);
 }
 
-void ka_msa_launch_maps(const uint8_t* rows, int rowStride, int W, int resStride, const KaSeqSet& q, int* col, int16_t* res, hipStream_t s)
+void ka_msa_launch_maps_fam(const KaMsaFamRows& t, const uint8_t* rows, const long long* rowOff, const int* W, const int* cell, int rowPad, int* col,
+                            int16_t* res, hipStream_t s)
 {
-        msa_maps<<<(q.N + MSA_WAVES - 1) / MSA_WAVES, MSA_THREADS, 0, s>>>(rows, rowStride, W, resStride, q.N, q.dOffs, q.dLens, col, res);
+        msa_maps_fam<<<(t.S + MSA_WAVES - 1) / MSA_WAVES, MSA_THREADS, 0, s>>>(t, rows, rowOff, W, cell, rowPad, col, res);
 }
 
 int KaSeqSet::set(const char* who, int numseq, const int* l, int max_res, const char* why)
@@ -37,24 +44,6 @@ int KaSeqSet::set(const char* who, int numseq, const int* l, int max_res, const 
         }
         offs[numseq] = T = (int)t;
         return KA_OK;
-}
-
-int KaSeqSet::init(const char* who, int numseq, const int* l, int max_res, const char* why)
-{
-        const std::string w(who);
-        if (set(who, numseq, l, max_res, why)) return KA_FAIL;
-        if (hipMalloc((void**)&dOffs, sizeof(int) * (numseq + 1)) != hipSuccess || hipMalloc((void**)&dLens, sizeof(int) * numseq) != hipSuccess)
-                return fail(w + ": out of device memory");
-        HIPCHK(hipMemcpy(dOffs, offs.data(), sizeof(int) * (numseq + 1), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dLens, lens.data(), sizeof(int) * numseq, hipMemcpyHostToDevice));
-        return KA_OK;
-}
-
-void KaSeqSet::release()
-{
-        if (dOffs) (void)hipFree(dOffs);
-        if (dLens) (void)hipFree(dLens);
-        dOffs = dLens = nullptr;
 }
 
 int ka_msa_check_rows(const char* who, const KaSeqSet& q, const uint8_t* rows, long long stride, int alnlen)

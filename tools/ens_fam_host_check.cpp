@@ -3,7 +3,8 @@
 // threads, compares with one thread, and prints "ok".  Needs no GPU.  Build it from kalign_amd/csrc with the host side
 // instrumented, once per sanitizer set (address,undefined -- then thread):
 //     hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -I../../include -I. \
-//           -x hip ../../tools/ens_fam_host_check.cpp ka_ens_fam.cpp ka_ens_fam.hip ka_msa.hip -o ens_fam_host_check
+//           -x hip ../../tools/ens_fam_host_check.cpp ka_ens_fam.cpp ka_ens.cpp ka_ens.hip ka_poar.cpp ka_poar.hip ka_msa.hip -o ens_fam_host_check
+// (ka_ens.cpp holds the host core ka_ens_fam.cpp is a front of, and with it the one-family front and its table passes)
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
