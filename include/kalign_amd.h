@@ -765,6 +765,66 @@ int  ka_ens_fam_stats(ka_ens_fam* h, double* stats_out);
 int  ka_debug_ens_fam_consensus_host(int n_fam, const int* fam_first, const int* lens, const long long* cand_first, const int* cand,
                                      const uint8_t* letters, int n_threads, int* alnlens_out, uint8_t* rows_out, long long cap);
 
+/* ---- summaries and trimming of the finished rows of a batch of families (ka_sum.hip, ka_sum.cpp) -----------------------------
+ * What python-kalign's kalign.utils computes from one alignment -- alignment_stats, consensus_sequence, remove_gap_columns,
+ * trim_alignment -- for all families of a batch in a number of launches that does not grow with the batch; one alignment is a
+ * batch of one.  Every count is an exact integer and every double the one division named below, so the results equal the
+ * utilities' bit for bit.
+ *   A byte     is a gap when it equals gap_char ('-' gives the utilities' behaviour); every other byte is a character and is
+ *              compared as a byte: upper and lower case differ, '.' and '*' are characters.  (Not the isalpha rule of the
+ *              comparison and ensemble stages.)
+ *   Families   fam_first[n_fam + 1]; a family has one row at least.  No sequence lengths are needed.
+ *   Rows       packed as ka_batch_rows hands them out: families in order, the rows of family f alnlens[f] + 1 bytes apart
+ *              (the byte after a row is not read).  alnlens[f] >= 1, a family holds fewer than 2^31 cells, the batch fewer
+ *              than 2^31 columns and fewer than 2^31 chunks of 256 columns over its rows.
+ *   Columns    are numbered flat over the batch, families in order: the sum of alnlens in all.
+ *   ka_sum_fam_check     every check of a packed batch, on the host alone (no context, no GPU): "ka_sum_fam_check: fam_first
+ *                        does not ascend from 0 to numseq", "ka_sum_fam_check: empty family", "ka_sum_fam_check: family 3:
+ *                        alnlen 0".
+ *   ka_sum_fam_create    runs the check, uploads the rows in one copy and builds the column table, the families' sums and
+ *                        their character sets once.  Runs on ctx's device and stream: destroy it before ctx.
+ *   ka_sum_fam_columns   per column (each output optional): gaps; distinct characters; the most frequent character and its
+ *                        count -- among characters of equal highest count the one whose first occurrence is in the lowest row,
+ *                        as Counter.most_common; gap_char and 0 in an all-gap column --; the sum over the column's characters a
+ *                        of n_a (n_a - 1) / 2.
+ *   ka_sum_fam_summary   counts_out[n_fam * 6]: gaps, cells, conserved columns (a character and one distinct), columns,
+ *                        matching pairs (the sum of same_pairs), compared pairs (the sum of k (k - 1) / 2, k the characters
+ *                        of a column); values_out[n_fam * 3]: gap_fraction = gaps / cells, conservation = conserved / columns,
+ *                        identity = matching / compared (0 when nothing is compared), each (double)a / (double)b.  Over all
+ *                        pairs of rows the matches at columns where both have a character are the matching pairs, the
+ *                        positions compared the compared pairs: alignment_stats' identity without a pair walk.
+ *   ka_sum_fam_consensus thresholds[n_fam] in [0, 1] (NULL: 0.5).  A column's character is gap_char when it holds no
+ *                        character, top_char when (double)top_count / (double)k >= threshold, else the family's ambiguous
+ *                        character: 'N' when every character of the family, upper-cased, lies in ATCGUN, else 'X'.  out: one
+ *                        row per family, packed like the rows (a 0 byte after each); ambiguous_out[n_fam].  Each optional.
+ *   ka_sum_fam_keep      the columns a rule keeps: with mask_off[f] >= 0 the alnlens[f] ints at masks + mask_off[f] (non-zero
+ *                        keeps; masks holds the sum of alnlens ints at most: an offset that passes that end is refused), else
+ *                        (double)n_gap / (double)n_f < gap_thresholds[f] (in [0, 1]; NULL: 1.0 for every family, which drops
+ *                        the all-gap columns).  masks or mask_off NULL: no masks.  keep_out: 0 / 1 per column, the layout
+ *                        ka_cmp_fam_set_masks takes; new_alnlens[n_fam]: kept columns.  Each optional.
+ *   ka_sum_fam_compact   the rows with only the columns the same rule keeps, left on the device; then ka_sum_fam_rows_size
+ *                        and ka_sum_fam_rows hand them out packed with their new widths and a 0 byte after each row (a
+ *                        family that keeps nothing has rows of width 0; -1 / an error before the first compact).  The
+ *                        handle's own rows are untouched: any number of rules can be tried on one upload.
+ *   ka_sum_fam_stats     stats_out[6]: device ms of the column table [0] and of the last consensus [1], keep [2] and compact
+ *                        [3]; kernel launches [4] and host synchronisations [5] of the last create, consensus, keep or compact
+ *                        call (0 and 0 when it was refused).  The hand-outs -- columns, summary, rows -- are copies of what
+ *                        those calls left and do not count.
+ * A refused call (a threshold outside [0, 1] or NaN, a mask offset past the end) launches nothing and leaves the handle usable.
+ */
+typedef struct ka_sum_fam ka_sum_fam;
+int  ka_sum_fam_check(int n_fam, const int* fam_first, const uint8_t* rows, const int* alnlens);
+int  ka_sum_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, const uint8_t* rows, const int* alnlens, int gap_char, ka_sum_fam** out);
+void ka_sum_fam_destroy(ka_sum_fam* h);
+int  ka_sum_fam_columns(ka_sum_fam* h, int* n_gap, int* n_distinct, uint8_t* top_char, int* top_count, long long* same_pairs);
+int  ka_sum_fam_summary(ka_sum_fam* h, long long* counts_out, double* values_out);
+int  ka_sum_fam_consensus(ka_sum_fam* h, const double* thresholds, uint8_t* out, uint8_t* ambiguous_out);
+int  ka_sum_fam_keep(ka_sum_fam* h, const double* gap_thresholds, const int* masks, const long long* mask_off, int* keep_out, int* new_alnlens);
+int  ka_sum_fam_compact(ka_sum_fam* h, const double* gap_thresholds, const int* masks, const long long* mask_off, int* new_alnlens);
+long long ka_sum_fam_rows_size(ka_sum_fam* h);
+int  ka_sum_fam_rows(ka_sum_fam* h, uint8_t* out, long long cap);
+int  ka_sum_fam_stats(ka_sum_fam* h, double* stats_out);
+
 #ifdef __cplusplus
 }
 #endif

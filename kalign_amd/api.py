@@ -64,6 +64,8 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_ens_fam_check", "ka_ens_fam_create", "ka_ens_fam_destroy", "ka_ens_fam_add_member", "ka_ens_fam_score_members", "ka_ens_fam_score",
            "ka_ens_fam_consensus", "ka_ens_fam_rows_size", "ka_ens_fam_rows", "ka_ens_fam_confidence", "ka_ens_fam_stats",
            "ka_debug_ens_fam_consensus_host",
+           "ka_sum_fam_check", "ka_sum_fam_create", "ka_sum_fam_destroy", "ka_sum_fam_columns", "ka_sum_fam_summary", "ka_sum_fam_consensus",
+           "ka_sum_fam_keep", "ka_sum_fam_compact", "ka_sum_fam_rows_size", "ka_sum_fam_rows", "ka_sum_fam_stats",
            "ka_guide_forest_from", "ka_guide_forest", "ka_aln_guide_forest", "ka_run_encoded_batch", "ka_batch_rows_size", "ka_batch_rows",
            "ka_batch_stats"]
 
@@ -248,6 +250,19 @@ def load_library():
     L.ka_ens_fam_confidence.argtypes = [vp, vp, vp, vp, vp]
     L.ka_ens_fam_stats.argtypes = [vp, vp]
     L.ka_debug_ens_fam_consensus_host.argtypes = [C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_longlong]
+    L.ka_sum_fam_check.argtypes = [C.c_int, vp, vp, vp]
+    L.ka_sum_fam_create.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.POINTER(vp)]
+    L.ka_sum_fam_destroy.argtypes = [vp]
+    L.ka_sum_fam_destroy.restype = None
+    L.ka_sum_fam_columns.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ka_sum_fam_summary.argtypes = [vp, vp, vp]
+    L.ka_sum_fam_consensus.argtypes = [vp, vp, vp, vp]
+    L.ka_sum_fam_keep.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ka_sum_fam_compact.argtypes = [vp, vp, vp, vp, vp]
+    L.ka_sum_fam_rows_size.argtypes = [vp]
+    L.ka_sum_fam_rows_size.restype = C.c_longlong
+    L.ka_sum_fam_rows.argtypes = [vp, vp, C.c_longlong]
+    L.ka_sum_fam_stats.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -1214,22 +1229,7 @@ class FamilyComparer(_CtxChild):
     def _set_masks(self, max_gap_frac, column_masks):
         F = len(self.sizes)
         frac = np.ascontiguousarray(np.broadcast_to(np.asarray(max_gap_frac, np.float32), (F,)))
-        if column_masks is None:
-            self.ctx._chk(self.L.ka_cmp_fam_set_masks(self.h, _ptr(frac), None, None))
-            return
-        if len(column_masks) != F:
-            raise KalignAmdError("%d column masks for %d families" % (len(column_masks), F))
-        off, parts, o = np.full(F, -1, np.int64), [], 0
-        for f, m in enumerate(column_masks):
-            if m is None:
-                continue
-            m = np.ascontiguousarray(m, np.int32).reshape(-1)
-            if len(m) != self.widths[f]:
-                raise KalignAmdError("family %d: mask length %d != reference alignment length %d" % (f, len(m), self.widths[f]))
-            off[f] = o
-            parts.append(m)
-            o += len(m)
-        masks = np.concatenate(parts) if parts else None
+        masks, off = pack_masks(column_masks, self.widths, "reference alignment")
         self.ctx._chk(self.L.ka_cmp_fam_set_masks(self.h, _ptr(frac), _ptr(masks), _ptr(off)))
 
     def score(self, tests, max_gap_frac=-1.0, column_masks=None):
@@ -1388,6 +1388,141 @@ def _ens_fam_create(self, fam_lens, n_runs):
 
 
 Context.family_ensemble = _ens_fam_create
+
+
+SUM_COUNTS = ["gaps", "cells", "conserved_columns", "columns", "matching_pairs", "compared_pairs"]
+SUM_STATS = ["table_ms", "consensus_ms", "keep_ms", "compact_ms", "launches", "syncs"]
+
+
+def pack_masks(column_masks, widths, what="alignment"):
+    """per family None or a mask of its width -> (int32 masks back to back or None, int64 offsets, -1 where there is none):
+    what ka_sum_fam_keep and ka_cmp_fam_set_masks take (FamilySummary, FamilyComparer: the one statement of the layout)"""
+    F = len(widths)
+    if column_masks is None:
+        return None, None
+    if len(column_masks) != F:
+        raise KalignAmdError("%d column masks for %d families" % (len(column_masks), F))
+    off, parts, o = np.full(F, -1, np.int64), [], 0
+    for f, m in enumerate(column_masks):
+        if m is None:
+            continue
+        m = np.ascontiguousarray(m, np.int32).reshape(-1)
+        if len(m) != widths[f]:
+            raise KalignAmdError("family %d: mask length %d != %s length %d" % (f, len(m), what, widths[f]))
+        off[f] = o
+        parts.append(m)
+        o += len(m)
+    return (np.concatenate(parts) if parts else None), off
+
+
+class FamilySummary(_CtxChild):
+    """The finished rows of a batch of families on the device (ka_sum_fam) and what python-kalign's kalign.utils computes
+    from each -- column table, alignment_stats, consensus_sequence, the columns remove_gap_columns / trim_alignment keep,
+    the trimmed rows -- bit for bit, in a number of launches that does not grow with the batch.  families_rows: one list
+    of rows per family (what Context.run_families returns).  gap: the gap byte; every other byte is a character."""
+    _destroy = "ka_sum_fam_destroy"
+
+    def __init__(self, ctx, families_rows, gap=b"-"):
+        self.ctx, self.L = ctx, ctx.L
+        if not ctx.h:
+            raise KalignAmdError("the context is closed")
+        # (a str row is its latin-1 bytes, one byte per character, as kalign_amd.summary hands rows over)
+        fams = [[x.encode("latin-1") if isinstance(x, str) else bytes(x) for x in f] for f in families_rows]
+        if not fams:
+            raise KalignAmdError("a family summary needs a family")
+        gap = gap.encode() if isinstance(gap, str) else bytes(gap)
+        if len(gap) != 1:
+            raise KalignAmdError("the gap is one byte")
+        self.gap = gap
+        self.sizes = [len(f) for f in fams]
+        self.first = _fam_first(self.sizes)
+        rows, self.widths = pack_families(fams)
+        self.col_first = np.concatenate([[0], np.cumsum(self.widths, dtype=np.int64)])
+        h = C.c_void_p()
+        ctx._chk(self.L.ka_sum_fam_create(ctx.h, len(fams), _ptr(self.first), _ptr(rows if len(rows) else np.zeros(1, np.uint8)),
+                                          _ptr(self.widths), gap[0], C.byref(h)))
+        self._adopt(ctx, h)
+
+    def _open(self):
+        if not self.h:
+            raise KalignAmdError("the summary is closed")
+        return len(self.sizes)
+
+    def _split(self, a):
+        return [a[self.col_first[f]:self.col_first[f + 1]] for f in range(len(self.sizes))]
+
+    def _thresholds(self, t):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(t, np.float64), (len(self.sizes),)))
+
+    def columns(self):
+        """per family a dict of per-column arrays: n_gap, n_distinct, top_char (uint8), top_count, same_pairs (int64)"""
+        self._open()
+        n = int(self.col_first[-1])
+        g, d, tc, sp = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64)
+        ch = np.zeros(n, np.uint8)
+        self.ctx._chk(self.L.ka_sum_fam_columns(self.h, _ptr(g), _ptr(d), _ptr(ch), _ptr(tc), _ptr(sp)))
+        return [dict(n_gap=a, n_distinct=b, top_char=c, top_count=e, same_pairs=s)
+                for a, b, c, e, s in zip(self._split(g), self._split(d), self._split(ch), self._split(tc), self._split(sp))]
+
+    def summary(self):
+        """per family alignment_stats' dict (length, n_sequences, gap_fraction, conservation, identity) and the six exact
+        counts behind the three values (SUM_COUNTS)"""
+        F = self._open()
+        counts, values = np.zeros((F, 6), np.int64), np.zeros((F, 3), np.float64)
+        self.ctx._chk(self.L.ka_sum_fam_summary(self.h, _ptr(counts), _ptr(values)))
+        out = []
+        for f in range(F):
+            d = dict(length=int(self.widths[f]), n_sequences=self.sizes[f], gap_fraction=float(values[f, 0]),
+                     conservation=float(values[f, 1]), identity=float(values[f, 2]))
+            d.update({k: int(v) for k, v in zip(SUM_COUNTS, counts[f])})
+            out.append(d)
+        return out
+
+    def consensus(self, threshold=0.5, want_ambiguous=False):
+        """consensus_sequence of every family as bytes; threshold one value or one per family.  want_ambiguous: also the
+        families' ambiguous characters (b"N" / b"X")"""
+        F = self._open()
+        out = np.zeros(int(self.col_first[-1]) + F, np.uint8)
+        amb = np.zeros(F, np.uint8)
+        self.ctx._chk(self.L.ka_sum_fam_consensus(self.h, _ptr(self._thresholds(threshold)), _ptr(out), _ptr(amb)))
+        rows = [out[int(self.col_first[f]) + f:int(self.col_first[f + 1]) + f].tobytes() for f in range(F)]
+        return (rows, [bytes([a]) for a in amb]) if want_ambiguous else rows
+
+    def keep(self, gap_threshold=1.0, column_masks=None):
+        """per family the int32 0 / 1 flags of its columns: a family's column mask (non-zero keeps) where column_masks
+        gives one, else n_gap / n < gap_threshold (one value or one per family).  The list is column_masks of
+        FamilyComparer.score / compare.compare_families as it stands."""
+        self._open()
+        masks, off = pack_masks(column_masks, self.widths)
+        keep = np.zeros(int(self.col_first[-1]), np.int32)
+        self.ctx._chk(self.L.ka_sum_fam_keep(self.h, _ptr(self._thresholds(gap_threshold)), _ptr(masks), _ptr(off), _ptr(keep), None))
+        return self._split(keep)
+
+    def compact(self, gap_threshold=1.0, column_masks=None):
+        """the rows of every family with only the columns keep() keeps: one list of bytes per family"""
+        F = self._open()
+        masks, off = pack_masks(column_masks, self.widths)
+        widths = np.zeros(F, np.int32)
+        self.ctx._chk(self.L.ka_sum_fam_compact(self.h, _ptr(self._thresholds(gap_threshold)), _ptr(masks), _ptr(off), _ptr(widths)))
+        n = int(self.L.ka_sum_fam_rows_size(self.h))
+        buf = np.zeros(max(n, 1), np.uint8)
+        self.ctx._chk(self.L.ka_sum_fam_rows(self.h, _ptr(buf), n))
+        return _unpack_families(buf, self.sizes, widths)
+
+    def stats(self):
+        """ka_sum_fam_stats: device ms of the column table and of the last consensus, keep and compact; kernel launches and
+        host synchronisations of the last of those calls (columns(), summary() and the hand-out of rows do not count)"""
+        st = np.zeros(len(SUM_STATS), np.float64)
+        self.ctx._chk(self.L.ka_sum_fam_stats(self.h, _ptr(st)))
+        return {k: (float(v) if k.endswith("_ms") else int(v)) for k, v in zip(SUM_STATS, st)}
+
+
+def _sum_fam_create(self, families_rows, gap=b"-"):
+    """ka_sum_fam_create: a FamilySummary holding the rows of every family on this context's device"""
+    return FamilySummary(self, families_rows, gap)
+
+
+Context.family_summary = _sum_fam_create
 
 
 def ens_fam_consensus_host(fam_lens, cands, families_letters, n_threads=1):

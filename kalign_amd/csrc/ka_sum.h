@@ -1,0 +1,63 @@
+// ka_sum.h -- summaries and trimming of the finished rows of a batch of families (ka_sum.hip kernels, ka_sum.cpp host
+// side): what the two units share.
+//
+// The rule for a byte: a gap is the byte `gap`; every other byte is a character and is compared as a byte (upper and lower
+// case differ).  This is kalign.utils' rule, not the isalpha rule of ka_msa.h: '.' and '*' are characters here.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define KA_SUM_TILE 64             // columns per tile of the column table: one lane of a wave per column
+#define KA_SUM_BINS 256            // a tile's histogram: KA_SUM_BINS x KA_SUM_TILE counters of 32 bits (64 KiB of LDS), bin-major
+#define KA_SUM_THREADS 512         // threads of a column-table workgroup: its waves deal the family's rows among them
+#define KA_SUM_PARTS (KA_SUM_THREADS / KA_SUM_TILE)   // the bins are reduced in this many parts, a wave each (32 bins: one word of the presence mask)
+#define KA_SUM_SCAN 256            // columns per step of the per-family scan (one per thread)
+#define KA_SUM_CHUNK 256           // output columns per wave of the row gather: four bytes per lane
+#define KA_SUM_FAMSUMS 4           // a family's sums from the device: see the enum below
+#define KA_SUM_STATS 6             // ka_sum_fam_stats: see include/kalign_amd.h
+
+enum {
+        KA_SUM_GAPS = 0,           // gap bytes
+        KA_SUM_CONSERVED = 1,      // columns with a character and one distinct character
+        KA_SUM_MATCHING = 2,       // sum over columns and characters a of n_a (n_a - 1) / 2
+        KA_SUM_COMPARED = 3,       // sum over columns of k (k - 1) / 2, k the column's characters
+};
+
+// one family: N rows of W columns from rows + rowOff, W + 1 bytes apart; its columns are firstCol .. firstCol + W - 1 of
+// the batch, its consensus row starts at firstCol + (its number) in a packed consensus
+struct KaSumFam {
+        int N, W;
+        int firstCol;
+        int chunks;                // gather chunks of one of its rows: ceil((W + 1) / KA_SUM_CHUNK)
+        long long rowOff;
+};
+
+struct KaSumTab {
+        int nFam, cols, nTiles;
+        int nItems;                            // gather items: (row, chunk) pairs over the batch
+        uint8_t gap;
+        const KaSumFam* fams;                  // [nFam]
+        const int* tileFirst;                  // [nFam + 1] first column tile of a family
+        const int* colFirst;                   // [nFam + 1] first column
+        const int* itemFirst;                  // [nFam + 1] first gather item
+        const uint8_t* rows;
+        // the column table
+        int* nGap; int* nDistinct; int* topCount; uint8_t* topChar; long long* samePairs;   // [cols]
+        unsigned long long* famSums;           // [nFam][KA_SUM_FAMSUMS]
+        unsigned* present;                     // [nFam][8]: bit b of the 256 is set when byte b is a character of the family
+        // a call's rule and results
+        const double* thr;                     // [nFam]
+        const uint8_t* ambiguous;              // [nFam]
+        const int* masks; const long long* maskOff;   // family f's mask at masks + maskOff[f], or maskOff[f] < 0 (masks NULL: none)
+        int* keep;                             // [cols] 0 / 1
+        int* src;                              // [cols] the kept columns of family f, in order, from src + firstCol
+        int* newW;                             // [nFam] kept columns
+        long long* outOff;                     // [nFam] first byte of a family's compacted rows
+        uint8_t* out;                          // consensus rows, or compacted rows
+};
+
+// ka_sum.hip: every launcher adds the kernels it launches to *launches
+int ka_sum_run_columns(const KaSumTab& a, hipStream_t s, int* launches);     // the column table, the family sums and the presence masks (zeroed first by the caller); 1: the LDS was refused
+void ka_sum_run_consensus(const KaSumTab& a, hipStream_t s, int* launches);
+void ka_sum_run_keep(const KaSumTab& a, hipStream_t s, int* launches);       // keep flags, then the per-family scan: src, newW
+void ka_sum_run_gather(const KaSumTab& a, hipStream_t s, int* launches);     // outOff over the families, then the rows

@@ -1,0 +1,278 @@
+// ka_sum.hip -- summaries and trimming of the finished rows of a batch of families on the device: one kernel set over
+// tables of families (ka_sum.h); one alignment is a batch of one.  No launch count depends on the number of families.
+//
+//   sum_columns    a workgroup per tile of 64 columns of one family (the family found by ka_fam_find over the first-tile
+//                  table): its waves deal the family's rows among them, a lane per column, and count bytes into a
+//                  bin-major LDS histogram (256 bins x 64 columns: the lanes of a wave never share a counter); the bins
+//                  are reduced in eight parts of 32, a wave each, then per column by the first wave: gaps, distinct
+//                  characters, the most frequent character and its count, the sum of C(n_a, 2).  A tie for the highest
+//                  count is settled as Counter.most_common does, by the first row that holds one of the tied characters: a
+//                  second walk of the tied columns, dealt to the waves like the first, that ends at that row (an LDS
+//                  minimum per column).  The family's four sums by 64-bit atomics, its character-presence mask by 32-bit
+//                  ORs.
+//   sum_consensus  flat over the columns of the batch
+//   sum_keep       flat over the columns: the caller's mask or the gap-fraction rule
+//   sum_scan       a workgroup per family: the kept columns numbered in order (256 columns a step, the count carried)
+//   sum_offsets    one workgroup: where every family's compacted rows start
+//   sum_gather     a wave per (row, chunk of 256 output columns): four consecutive output bytes per lane
+#include <algorithm>
+#include "ka_sum.h"
+#include "ka_msa.h"
+
+namespace {
+
+// what one part of the bins knows about a column
+struct SumPart {
+        int dist, k, mx, arg, nmx;             // distinct characters, characters, highest count, its lowest bin, bins that have it
+        long long same;
+};
+
+// ... as it lies in LDS: five words per (part, column), word-major (the lanes of a wave on neighbouring words); dist, arg
+// and nmx share a word (a part has 32 bins: dist and nmx reach 32, arg 255)
+enum { PART_K = 0, PART_MX = 1, PART_PACKED = 2, PART_SAME_LO = 3, PART_SAME_HI = 4, PART_WORDS = 5 };
+constexpr int kPartSlots = KA_SUM_PARTS * KA_SUM_TILE;
+
+__device__ __forceinline__ void part_put(unsigned* part, int slot, const SumPart& p)
+{
+        part[PART_K * kPartSlots + slot] = (unsigned)p.k;
+        part[PART_MX * kPartSlots + slot] = (unsigned)p.mx;
+        part[PART_PACKED * kPartSlots + slot] = (unsigned)p.dist | (unsigned)p.arg << 8 | (unsigned)p.nmx << 16;
+        part[PART_SAME_LO * kPartSlots + slot] = (unsigned)p.same;
+        part[PART_SAME_HI * kPartSlots + slot] = (unsigned)(p.same >> 32);
+}
+
+__device__ __forceinline__ SumPart part_get(const unsigned* part, int slot)
+{
+        SumPart p;
+        const unsigned w = part[PART_PACKED * kPartSlots + slot];
+        p.k = (int)part[PART_K * kPartSlots + slot];
+        p.mx = (int)part[PART_MX * kPartSlots + slot];
+        p.dist = (int)(w & 255u); p.arg = (int)(w >> 8 & 255u); p.nmx = (int)(w >> 16);
+        p.same = (long long)((unsigned long long)part[PART_SAME_HI * kPartSlots + slot] << 32 | part[PART_SAME_LO * kPartSlots + slot]);
+        return p;
+}
+
+// histogram, parts, two ints per column: 76 288 bytes, so that two workgroups share a CU's 160 KiB
+constexpr size_t kColumnsLds = sizeof(unsigned) * (KA_SUM_BINS * KA_SUM_TILE + PART_WORDS * kPartSlots + 2 * KA_SUM_TILE);
+static_assert(2 * kColumnsLds <= 163840, "two column-table workgroups per CU");
+
+__global__ __launch_bounds__(KA_SUM_THREADS) void sum_columns(KaSumTab a)
+{
+        extern __shared__ unsigned sum_lds[];
+        unsigned* hist = sum_lds;                                // [bin][column of the tile]
+        unsigned* part = sum_lds + KA_SUM_BINS * KA_SUM_TILE;
+        const int tile = blockIdx.x;
+        const int f = ka_fam_find(a.tileFirst, a.nFam, tile);
+        const KaSumFam fam = a.fams[f];
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int c = (tile - a.tileFirst[f]) * KA_SUM_TILE + lane;
+        const unsigned gap = a.gap;
+        const long long stride = (long long)fam.W + 1;
+        const uint8_t* col = a.rows + fam.rowOff + c;           // (read only where c < W)
+        int* firstRow = (int*)(part + PART_WORDS * kPartSlots);          // [column]: the row that settles a tie
+        int* tieMx = firstRow + KA_SUM_TILE;                             // [column]: the highest count of a tied column, else 0
+        for (int i = threadIdx.x; i < KA_SUM_BINS * KA_SUM_TILE; i += KA_SUM_THREADS) hist[i] = 0;
+        if (threadIdx.x < KA_SUM_TILE) firstRow[threadIdx.x] = INT32_MAX;
+        __syncthreads();
+        if (c < fam.W) {
+#pragma unroll 4
+                for (int r = wave; r < fam.N; r += KA_SUM_PARTS) atomicAdd(&hist[(unsigned)col[r * stride] * KA_SUM_TILE + lane], 1u);
+        }
+        __syncthreads();
+        {
+                SumPart p{};
+                unsigned present = 0;
+                for (int q = 0; q < KA_SUM_BINS / KA_SUM_PARTS; q++) {
+                        const unsigned b = wave * (KA_SUM_BINS / KA_SUM_PARTS) + q;
+                        const int n = (int)hist[b * KA_SUM_TILE + lane];
+                        if (b == gap || !n) continue;
+                        p.dist++;
+                        p.k += n;
+                        p.same += (long long)n * (n - 1) / 2;
+                        present |= 1u << q;
+                        if (n > p.mx) { p.mx = n; p.arg = (int)b; p.nmx = 1; }
+                        else if (n == p.mx) p.nmx++;
+                }
+                part_put(part, wave * KA_SUM_TILE + lane, p);
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) present |= __shfl_xor(present, o, 64);
+                if (lane == 0 && present) atomicOr(&a.present[(long long)f * 8 + wave], present);
+        }
+        __syncthreads();
+        // the first wave adds the parts up and tells the others which columns are tied, and at which count
+        int dist = 0, k = 0, mx = 0, ties = 0;
+        unsigned top = gap;
+        long long same = 0;
+        if (wave == 0) {
+                for (int w = 0; w < KA_SUM_PARTS; w++) {
+                        const SumPart p = part_get(part, w * KA_SUM_TILE + lane);
+                        dist += p.dist;
+                        k += p.k;
+                        same += p.same;
+                        if (p.mx > mx) { mx = p.mx; top = (unsigned)p.arg; ties = p.nmx; }
+                        else if (p.mx == mx && mx > 0) ties += p.nmx;
+                }
+                tieMx[lane] = ties > 1 ? mx : 0;
+        }
+        __syncthreads();
+        // a tie: the first row that holds a character of the highest count.  Each wave walks its own rows and ends at its
+        // first such row, or where another wave has found a lower one; the lowest row wins.
+        const int tmx = tieMx[lane];
+        if (tmx)
+                for (int r = wave; r < fam.N && r < *(volatile int*)&firstRow[lane]; r += KA_SUM_PARTS) {
+                        const unsigned b = col[r * stride];
+                        if (b != gap && (int)hist[b * KA_SUM_TILE + lane] == tmx) { atomicMin(&firstRow[lane], r); break; }
+                }
+        __syncthreads();
+        if (wave != 0) return;
+        if (ties > 1) top = col[firstRow[lane] * stride];
+        const int nGap = (int)hist[gap * KA_SUM_TILE + lane];    // (0 past the family's width: nothing was counted there)
+        if (c < fam.W) {
+                const long long g = (long long)fam.firstCol + c;
+                a.nGap[g] = nGap;
+                a.nDistinct[g] = dist;
+                a.topChar[g] = (uint8_t)top;
+                a.topCount[g] = mx;
+                a.samePairs[g] = same;
+        }
+        const long long sums[KA_SUM_FAMSUMS] = { nGap, k > 0 && dist == 1, same, (long long)k * (k - 1) / 2 };
+#pragma unroll
+        for (int q = 0; q < KA_SUM_FAMSUMS; q++) {
+                const long long v = ka_msa_wave_sum(sums[q]);
+                if (lane == 0 && v) atomicAdd(&a.famSums[(long long)f * KA_SUM_FAMSUMS + q], (unsigned long long)v);
+        }
+}
+
+__global__ __launch_bounds__(256) void sum_consensus(KaSumTab a)
+{
+        const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+        if (g >= a.cols) return;
+        const int f = ka_fam_find(a.colFirst, a.nFam, (int)g);
+        const KaSumFam fam = a.fams[f];
+        const int k = fam.N - a.nGap[g];
+        uint8_t ch = a.gap;
+        if (k > 0) ch = (double)a.topCount[g] / (double)k >= a.thr[f] ? a.topChar[g] : a.ambiguous[f];
+        uint8_t* o = a.out + g + f;                              // (a 0 byte after each family's row)
+        o[0] = ch;
+        if ((int)g - fam.firstCol == fam.W - 1) o[1] = 0;
+}
+
+__global__ __launch_bounds__(256) void sum_keep(KaSumTab a)
+{
+        const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+        if (g >= a.cols) return;
+        const int f = ka_fam_find(a.colFirst, a.nFam, (int)g);
+        const KaSumFam fam = a.fams[f];
+        const long long mo = a.masks ? a.maskOff[f] : -1;
+        a.keep[g] = mo >= 0 ? a.masks[mo + ((int)g - fam.firstCol)] != 0 : (double)a.nGap[g] / (double)fam.N < a.thr[f];
+}
+
+__global__ __launch_bounds__(KA_SUM_SCAN) void sum_scan(KaSumTab a)
+{
+        __shared__ int waveTot[KA_SUM_SCAN / 64];
+        const int f = blockIdx.x;
+        const KaSumFam fam = a.fams[f];
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        int carry = 0;
+        for (int c0 = 0; c0 < fam.W; c0 += KA_SUM_SCAN) {
+                const int c = c0 + threadIdx.x;
+                const bool kp = c < fam.W && a.keep[fam.firstCol + c] != 0;
+                const unsigned long long m = __ballot(kp);
+                if (lane == 0) waveTot[wave] = __popcll(m);
+                __syncthreads();
+                int before = 0, all = 0;
+                for (int w = 0; w < KA_SUM_SCAN / 64; w++) {
+                        if (w < wave) before += waveTot[w];
+                        all += waveTot[w];
+                }
+                if (kp) a.src[fam.firstCol + carry + before + __popcll(m & ((1ull << lane) - 1ull))] = c;
+                carry += all;
+                __syncthreads();
+        }
+        if (threadIdx.x == 0) a.newW[f] = carry;
+}
+
+__global__ __launch_bounds__(256) void sum_offsets(KaSumTab a)
+{
+        __shared__ long long waveTot[4];
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        long long carry = 0;
+        for (int f0 = 0; f0 < a.nFam; f0 += 256) {
+                const int f = f0 + threadIdx.x;
+                const long long v = f < a.nFam ? (long long)a.fams[f].N * (a.newW[f] + 1) : 0;
+                long long inc = v;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                        const long long t = __shfl_up(inc, o, 64);
+                        if (lane >= o) inc += t;
+                }
+                if (lane == 63) waveTot[wave] = inc;
+                __syncthreads();
+                long long before = 0, all = 0;
+                for (int w = 0; w < 4; w++) {
+                        if (w < wave) before += waveTot[w];
+                        all += waveTot[w];
+                }
+                if (f < a.nFam) a.outOff[f] = carry + before + inc - v;
+                carry += all;
+                __syncthreads();
+        }
+}
+
+__global__ __launch_bounds__(256) void sum_gather(KaSumTab a)
+{
+        const int lane = threadIdx.x & 63;
+        const long long item = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+        if (item >= a.nItems) return;
+        const int f = ka_fam_find(a.itemFirst, a.nFam, (int)item);
+        const KaSumFam fam = a.fams[f];
+        const int local = (int)item - a.itemFirst[f];
+        const int row = local / fam.chunks, chunk = local % fam.chunks;
+        const int nw = a.newW[f];
+        const int j0 = chunk * KA_SUM_CHUNK + lane * 4;
+        if (j0 > nw) return;
+        const uint8_t* in = a.rows + fam.rowOff + (long long)row * (fam.W + 1);
+        uint8_t* o = a.out + a.outOff[f] + (long long)row * (nw + 1);
+        const int* src = a.src + fam.firstCol;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+                const int j = j0 + q;
+                if (j < nw) o[j] = in[src[j]];
+                else if (j == nw) o[j] = 0;
+        }
+}
+
+} // namespace
+
+// Each launcher counts its launches where it makes them (*launches is the caller's counter of the call).
+
+int ka_sum_run_columns(const KaSumTab& a, hipStream_t s, int* launches)
+{
+        static_assert(KA_SUM_BINS / KA_SUM_PARTS == 32, "a part of the bins is one word of the presence mask");
+        if (hipFuncSetAttribute((const void*)sum_columns, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColumnsLds) != hipSuccess) return 1;
+        sum_columns<<<(unsigned)a.nTiles, KA_SUM_THREADS, kColumnsLds, s>>>(a);
+        ++*launches;
+        return 0;
+}
+
+void ka_sum_run_consensus(const KaSumTab& a, hipStream_t s, int* launches)
+{
+        sum_consensus<<<(unsigned)(((long long)a.cols + 255) / 256), 256, 0, s>>>(a);
+        ++*launches;
+}
+
+void ka_sum_run_keep(const KaSumTab& a, hipStream_t s, int* launches)
+{
+        sum_keep<<<(unsigned)(((long long)a.cols + 255) / 256), 256, 0, s>>>(a);
+        ++*launches;
+        sum_scan<<<(unsigned)a.nFam, KA_SUM_SCAN, 0, s>>>(a);
+        ++*launches;
+}
+
+void ka_sum_run_gather(const KaSumTab& a, hipStream_t s, int* launches)
+{
+        sum_offsets<<<1, 256, 0, s>>>(a);
+        ++*launches;
+        sum_gather<<<(unsigned)(((long long)a.nItems + 3) / 4), 256, 0, s>>>(a);
+        ++*launches;
+}
