@@ -60,8 +60,11 @@ extern "C" {
                                    recorded meetups keep the level-order sum. */
 #define KA_FLAG_LEAF_PROFILES 32 /* also write the profile records of the SEQUENCES (make_profile_n, aln_setup.c:40-99) that tasks consume.  Since
                                    round 6 the first pass does not (without sequence weights): a sequence's record is a function of its
-                                   residue, and the merge makes what it needs of it on the fly -- ka_tree_get_profile of a node < numseq then
-                                   returns unwritten memory.  Set this to read leaf profiles back. */
+                                   residue, and the merge makes what it needs of it on the fly -- ka_tree_get_profile and ka_tree_profile_dev
+                                   of a node < numseq then FAIL (ABI 21; before, they returned unwritten memory).  Set this to read leaf
+                                   profiles back.  They succeed as well with sequence weights (scal[5] > 0) and after ka_tree_refine, which
+                                   write the records -- in every case only once the task that consumes the sequence has run: the records
+                                   carry that task's penalties and score offset. */
 
 typedef struct ka_ctx ka_ctx;
 
@@ -208,7 +211,7 @@ int ka_weave_gaps(int numseq, const int* lens, int n_tasks, const ka_task_rec* r
  * (finalise_alignment msa_op.c:546-598, refine_alignment aln_refine.c:36-88, compute_aln_pairwise_dist aln_apair_dist.c:9-86). */
 int ka_tree_adopt_alignment(ka_ctx* ctx, const ka_task_rec* recs, const int* gaps);
 
-/* Merged profile of node `node` ((plen+2)*64 floats) after a run. */
+/* Merged profile of node `node` ((plen+2)*64 floats) after a run.  A sequence (node < numseq): see KA_FLAG_LEAF_PROFILES. */
 int ka_tree_get_profile(ka_ctx* ctx, int node, float* out, long long cap_floats);
 /* Per-task phase timings of the last run (KA_FLAG_TIMING): out[8*t + k], shader-clock cycles:
    0 operand prep, 1 Hirschberg, 2 path coding, 3 profile merge, 4 passes, 5 meetups, 6 recursion

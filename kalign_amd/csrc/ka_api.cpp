@@ -17,7 +17,7 @@ __attribute__((visibility("hidden"))) int ka_fail_message(const char* m) { retur
 extern "C" const char* ka_last_error(void) { return g_err.c_str(); }
 struct ka_ctx;
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_guide.cpp)
-extern "C" int ka_abi_version(void) { return 20; }
+extern "C" int ka_abi_version(void) { return 21; }
 
 extern "C" int ka_ctx_create(int device, ka_ctx** out)
 {
@@ -195,6 +195,7 @@ int tree_reset(ka_ctx* c)
         HIPCHK(hipStreamSynchronize(c->stream));          // the staging vectors above are stack/heap temporaries
         c->state_valid = true;
         c->task_done.assign(c->n_tasks, 0);
+        c->leaf_written.assign(c->n_tasks, 0);
         c->injected.clear();
         return KA_OK;
 }
@@ -349,7 +350,8 @@ int tree_launch(ka_ctx* c, bool reset)
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c->ev1, c->stream));
-        for (auto& L : c->plan_levels) for (int t : L) c->task_done[t] = 1;
+        const char wrote = (D.refine_mode || c->first_pass_writes_leaves()) ? 1 : 0;      // (of the launches above, by the mode they ran in)
+        for (auto& L : c->plan_levels) for (int t : L) { c->task_done[t] = 1; c->leaf_written[t] = wrote; }
         return KA_OK;
 }
 
@@ -1205,7 +1207,7 @@ extern "C" int ka_tree_run_tasks(ka_ctx* c, const int* task_ids, int n)
                 ka_launch_task_level(&D, c->d_blocks_tmp.p, (int)tbl.size(), lean, 0, c->stream);
                 HIPCHK(hipStreamSynchronize(c->stream));
                 c->n_launches++;
-                for (int t : L) c->task_done[t] = 1;
+                for (int t : L) { c->task_done[t] = 1; c->leaf_written[t] = c->first_pass_writes_leaves() ? 1 : 0; }   // (D.refine_mode is 0 here)
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c->ev1, c->stream));
@@ -1300,6 +1302,26 @@ extern "C" int ka_tree_set_profile(ka_ctx* c, int node, const float* prof, int p
         return KA_OK;
 }
 
+// A sequence's records (node < numseq) lie in the arena only where a task wrote them: the first pass makes them from the residue
+// inside the merge instead (ka_task.h: leaf_syn) unless the job carries KA_FLAG_LEAF_PROFILES or sequence weights; a refinement
+// pass always writes them.  They hold the penalties of the ONE task that consumes the sequence, so that task must have run.
+// Everything else is arena memory nobody wrote: an error, not a profile.
+static int leaf_records_written(const ka_ctx* c, int node)
+{
+        if (node >= c->numseq) return KA_OK;
+        for (int t = 0; t < c->n_tasks; t++)
+                if (c->abc[3 * t] == node || c->abc[3 * t + 1] == node) {
+                        // (task_done / leaf_written speak of the device state only while that is valid; leaf_written is what the launch
+                        // that ran the task did -- not what the context's last ka_tree_refine was, which an upload, a reset or a partial
+                        // run does not undo)
+                        if (!c->state_valid || (size_t)t >= c->task_done.size() || !c->task_done[t])
+                                return fail("node " + std::to_string(node) + " is a sequence: the task that consumes it (and writes its records) has not run");
+                        if (c->leaf_written[t]) return KA_OK;
+                        return fail("node " + std::to_string(node) + " is a sequence: the run made its records inside the merge and did not write them; upload the job with KA_FLAG_LEAF_PROFILES");
+                }
+        return fail("node " + std::to_string(node) + " is a sequence no task consumes: it has no profile records");
+}
+
 // Device-to-device hand-over of a subtree root's profile between the GPUs of a sharded tree: the source exposes
 // where the profile lies in its arena, the destination reserves arena space for it; the caller moves the bytes HBM to
 // HBM (RCCL send / recv over xGMI, hipMemcpyPeer) -- no host bounce.
@@ -1307,6 +1329,7 @@ extern "C" int ka_tree_profile_dev(ka_ctx* c, int node, void** dev_ptr, int* ple
 {
         if (!c || !c->have_job) return fail("no uploaded job");
         if (node < 0 || node >= 2 * c->numseq - 1 || !dev_ptr || !plen_out) return fail("bad node");
+        if (leaf_records_written(c, node)) return KA_FAIL;
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(hipStreamSynchronize(c->stream));
         int len = 0;
@@ -1429,6 +1452,7 @@ extern "C" int ka_tree_get_profile(ka_ctx* c, int node, float* out, long long ca
         HIPCHK(hipSetDevice(c->device));
         const int nprof = 2 * c->numseq - 1;
         if (node < 0 || node >= nprof) return fail("bad node");
+        if (leaf_records_written(c, node)) return KA_FAIL;
         int len = 0;
         long long po = -1;
         HIPCHK(hipMemcpy(&len, c->d_node_len.p + node, sizeof(int), hipMemcpyDeviceToHost));

@@ -153,6 +153,9 @@ struct ka_ctx : KaPlan {
         bool state_valid = false;      // device state reset and consistent with task_done
         bool partial = false;          // last launch was ka_tree_run_tasks (no automatic grow + re-run)
         std::vector<char> task_done;
+        std::vector<char> leaf_written;  // per task, set with task_done: the launch that ran it wrote the records of the sequences it consumes
+        // (the first pass writes a sequence's records only for this flag or under sequence weights -- ka_task.h: leaf_syn; a refinement launch always)
+        bool first_pass_writes_leaves() const { return (flags & KA_FLAG_LEAF_PROFILES) || scal[5] > 0.0f; }
         std::vector<int> injected;       // nodes whose profile came from ka_tree_set_profile
         DevBuf<int2> d_blocks_tmp;
         // overlapping launches (KA_OVERLAP): the chained launch on a stream of its own (lowest priority) beside the queued launch, events to

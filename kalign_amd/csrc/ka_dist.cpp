@@ -543,6 +543,7 @@ static int dist_tree_attempt(ka_dist* d, int* status, int* grow)
                         ka_launch_task_level(&D, d->top_blocks[i].p, (int)d->top_blocks[i].n, 0, 0, c->stream);
                         c->n_launches++;
                         c->task_done[t] = 1;
+                        c->leaf_written[t] = (D.refine_mode || c->first_pass_writes_leaves()) ? 1 : 0;
                 }
         }
         HIPCHK(hipGetLastError());

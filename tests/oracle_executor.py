@@ -12,6 +12,47 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def task_penalties(scal, gap_scale, subm_off):
+    """(gpo, gpe, tgpe, soff) of one task as do_align scales them (aln_run.c:226-237), in fp32"""
+    gs, soff = np.float32(gap_scale), np.float32(subm_off)
+    gpo, gpe, tgpe = (np.float32(x) for x in scal[:3])
+    if gs < 1.0 or soff > 0.0:
+        return np.float32(gpo * gs), np.float32(gpe * gs), np.float32(tgpe * gs), soff
+    return gpo, gpe, tgpe, np.float32(0.0)
+
+
+def leaf_profile(code, subm, pen):
+    """make_profile_n: the (len + 2) x 64 records of a sequence for the task with the penalties `pen` (task_penalties)"""
+    out = np.zeros(64 * (len(code) + 2), np.float32)
+    oracledrv.lib().ko_make_profile(_p(code), len(code), _p(subm), C.c_float(pen[0]), C.c_float(pen[1]), C.c_float(pen[2]), C.c_float(pen[3]), _p(out))
+    return out
+
+
+def task_operands(codes, subm, pen, a, b, nsip, plen, prof):
+    """The two operands of task (a, b) as ko_msa_tree hands them to the DP and to the merge: a sequence's records made for this
+    task, a node's merged profile with set_gap_penalties_n for the other side's member count.  prof[] is left as it is: a node's
+    profile stays there AS CREATED."""
+    L = oracledrv.lib()
+    out = []
+    for x, other in ((a, b), (b, a)):
+        if nsip[x] == 1:
+            out.append(leaf_profile(codes[x], subm, pen))
+        else:
+            p = np.array(prof[x], np.float32)
+            L.ko_set_gap_penalties(_p(p), plen[x], nsip[other])
+            out.append(p)
+    return out
+
+
+def merged_profile(pa, pb, coded, na, nb, subm, scal):
+    """update_n along a coded path, with the unscaled penalties (aln_run.c:405-413): (coded[0] + 2) x 64 floats"""
+    out = np.zeros(64 * (int(coded[0]) + 2), np.float32)
+    coded = np.ascontiguousarray(coded, np.int32)
+    oracledrv.lib().ko_update_profile(_p(pa), _p(pb), _p(out), _p(coded), na, nb, _p(subm),
+                                      C.c_float(scal[0]), C.c_float(scal[1]), C.c_float(scal[2]), C.c_float(scal[5]))
+    return out
+
+
 class OracleExecutor:
     def __init__(self, codes, tasks, subm, scal, gap_scale, subm_off):
         """gap_scale / subm_off: per task, as do_align derives them (aln_run.c:226-237); taken from a
@@ -31,28 +72,15 @@ class OracleExecutor:
         self.prof = {}
         self.done = {}
 
-    def _leaf(self, i, gpo, gpe, tgpe, soff):
-        out = np.zeros(64 * (self.plen[i] + 2), np.float32)
-        self.L.ko_make_profile(_p(self.codes[i]), self.plen[i], _p(self.subm), C.c_float(gpo), C.c_float(gpe), C.c_float(tgpe), C.c_float(soff), _p(out))
-        return out
-
     def tree_run_tasks(self, ids):
         for t in sorted(int(x) for x in ids):
             a, b, c = (int(v) for v in self.tasks[t])
-            gs, soff = np.float32(self.gap_scale[t]), np.float32(self.subm_off[t])
-            gpo, gpe, tgpe = self.scal[0], self.scal[1], self.scal[2]
-            if gs < 1.0 or soff > 0.0:
-                gpo, gpe, tgpe = np.float32(gpo * gs), np.float32(gpe * gs), np.float32(tgpe * gs)
-            else:
-                soff = np.float32(0.0)
+            pen = task_penalties(self.scal, self.gap_scale[t], self.subm_off[t])
+            gs = np.float32(self.gap_scale[t])
+            gpo, gpe, tgpe, soff = pen
             la, lb = self.plen[a], self.plen[b]
             na, nb = self.nsip[a], self.nsip[b]
-            pa = self._leaf(a, gpo, gpe, tgpe, soff) if na == 1 else self.prof[a]
-            pb = self._leaf(b, gpo, gpe, tgpe, soff) if nb == 1 else self.prof[b]
-            if na > 1:
-                self.L.ko_set_gap_penalties(_p(pa), la, nb)
-            if nb > 1:
-                self.L.ko_set_gap_penalties(_p(pb), lb, na)
+            pa, pb = task_operands(self.codes, self.subm, pen, a, b, self.nsip, self.plen, self.prof)
             swapped = 0
             if na == 1 and nb == 1:
                 kind = 0
@@ -88,8 +116,7 @@ class OracleExecutor:
             plen = int(coded[0])
             merged = np.zeros(64 * (plen + 2), np.float32)
             if t != len(self.tasks) - 1:
-                self.L.ko_update_profile(_p(pa), _p(pb), _p(merged), _p(coded), na, nb, _p(self.subm),
-                                         C.c_float(self.scal[0]), C.c_float(self.scal[1]), C.c_float(self.scal[2]), C.c_float(self.scal[5]))
+                merged = merged_profile(pa, pb, coded, na, nb, self.subm, self.scal)
             self.prof[c] = merged
             self.plen[c] = plen
             rec = oracledrv.TaskRec()

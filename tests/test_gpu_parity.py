@@ -109,6 +109,11 @@ def test_tree_matches_oracle_seeded(ctx, oracle, n, length, dna, seed):
         assert np.array_equal(paths[r.path_off:r.path_off + r.plen + 2], opaths[o.path_off:o.path_off + o.plen + 2]), t
     for a, b in zip(gaps, ogaps):
         assert np.array_equal(a, b)
+    # merged profiles: the hash of every non-root node
+    L = oracle.lib()
+    for t, (r, o) in enumerate(zip(recs[:-1], orecs)):
+        prof = ctx.tree_profile(r.c, r.plen)
+        assert L.ko_fnv1a(prof.ctypes.data, 4 * 64 * (r.plen + 2)) == o.prof_hash, t
 
 
 def test_pairwise_matches_oracle_seeded(ctx, oracle):

@@ -40,10 +40,10 @@ def _split(flat, lens):
 
 
 @pytest.mark.parametrize("name", refine_cases())
-def test_refinement_matches_reference(ctx, name):
+def test_refinement_matches_reference(ctx, oracle, name):
     """every edge re-aligned with the five flip trials of refine_edge, the best sum-of-pairs trial kept: gap arrays,
     profile lengths and the kept trial's confidence equal the real reference's, coded paths (convert_raw_path flags)
-    equal the pinned oracle's"""
+    equal the pinned oracle's, and so does the hash of every non-root node's merged profile"""
     g = Golden(name)
     recs, paths, gaps = run_refine(ctx, g)
     for t, r in enumerate(recs):
@@ -55,6 +55,13 @@ def test_refinement_matches_reference(ctx, name):
     assert np.array_equal(np.array([r.confidence for r in recs], np.float32), g.conf_after)
     assert int(g.n_differ) > 0 or int(g.mode) == 3      # (the inline trials never beat the baseline on these inputs)
     # mode + 256 = KA_REFINE_ADAPTIVE (--adaptive-budget): 1 .. 8 trials per edge
+    # merged profiles along the refined paths (update_n's open / close adjustments): the hash of every non-root node
+    orecs, _, _ = oracle.msa_tree_refine(g.codes, g.tasks, g.subm, g.scal, g.seq_distances, mode=int(g.mode),
+                                         conf_in=g.conf_before, n_anchors=int(g.n_anchors), weight=float(g.weight))
+    L = oracle.lib()
+    for t, (r, o) in enumerate(zip(recs[:-1], orecs)):
+        prof = ctx.tree_profile(r.c, r.plen)
+        assert L.ko_fnv1a(prof.ctypes.data, 4 * 64 * (r.plen + 2)) == o.prof_hash, (name, t)
 
 
 def test_refine_is_repeatable_and_run_returns_to_the_first_pass(ctx):
