@@ -147,13 +147,25 @@ int ka_tree_run(ka_ctx* ctx);
    (ka_tree_run adds the same margins level by level: equal within 1e-5).  conf_in[n_tasks]: first-pass task
    confidences (the reference reads task->confidence); only read for mode 2; NULL = computed here with a mode-4 pass.  Asynchronous like
    ka_tree_run; ka_tree_sync / ka_tree_download then return the refined records, paths and gaps (records carry the
-   kept trial's confidence). */
+   kept trial's confidence).
+   On a forest job ka_tree_refine takes mode 2's median POOLED, over all tasks of the job whatever tree they are of;
+   ka_tree_refine_trees (below) takes it per tree, which is what the reference does with each alignment. */
 #define KA_REFINE_ADAPTIVE 256      /* mode | KA_REFINE_ADAPTIVE: aln_param's adaptive_budget (`kalign --adaptive-budget`,
                                        aln_refine.c:187-193, 255-282; modes 1 and 2): 1 .. 8 trials per edge, from the share of
                                        very uncertain meetups of its baseline trial */
 #define KA_REFINE_TRIALS(n) (((n) & 255) << 16)   /* 3 | KA_REFINE_TRIALS(n): create_msa_tree_inline_refine with n trials per edge
                                                      (lib/src/aln_run.c:448-475 takes any count; kalign_run passes 3, the default here) */
 int ka_tree_refine(ka_ctx* ctx, int mode, const float* conf_in);
+/* ka_tree_refine with mode 2's rule per TREE of the job: same modes, flags, conf_in and asynchrony; on a job of one tree the
+   same call.  A tree is the set of tasks that lead to one root (a task nobody consumes), trees are numbered by ascending
+   index of their root task, and a tree of n tasks has compute_confidence_threshold's threshold (aln_refine.c:674-712) of
+   its own n confidences: sorted ascending, v[n/2] for odd n, (v[n/2-1] + v[n/2]) / 2.0F in fp32 for even n; an edge is
+   refined when its confidence is <= its tree's threshold (a tree of one task always).  The trees are read from the task
+   list alone, so their tasks may be interleaved.
+     tree_of_out[n_tasks]  (may be NULL) the tree of every task
+     thr_out[n_tasks]      (may be NULL) room for n_tasks values, the first n_trees filled: every tree's threshold (0 in modes 1, 3, 4)
+     n_trees_out           (may be NULL) */
+int ka_tree_refine_trees(ka_ctx* ctx, int mode, const float* conf_in, int* tree_of_out, float* thr_out, int* n_trees_out);
 int ka_tree_sync(ka_ctx* ctx);
 long long ka_tree_paths_size(ka_ctx* ctx);      /* ints needed for paths_out (valid after run+sync) */
 int ka_tree_download(ka_ctx* ctx, ka_task_rec* recs, int* paths_out, long long paths_cap, int* gaps_out);
@@ -252,6 +264,13 @@ int ka_debug_plan(int numseq, const int* lens, int n_tasks, const int* tasks_abc
                   int* scalars, int* per_task, int* blocks, int blocks_cap, int* blocks_off, int* level_lean);
 /* ... and, flattened in the same way, the plan a context holds after ka_tree_upload, ka_tree_plan_tasks or ka_debug_reload_env. */
 int ka_debug_ctx_plan(ka_ctx* ctx, int* scalars, int* per_task, int* blocks, int blocks_cap, int* blocks_off, int* level_lean);
+/* Tests, no GPU and no context: the edges a mode-2 refinement pass marks, by the function ka_tree_refine(_trees) calls.  The task list
+ * as ka_tree_upload takes it (a forest's trees may be interleaved), a confidence per task; pooled != 0: ka_tree_refine's one median
+ * over all tasks, which every tree then has as its threshold; 0: ka_tree_refine_trees' median per tree.  tree_of_out[n_tasks],
+ * thr_out[n_tasks] (the first *n_trees_out filled), marks_out[n_tasks] (1: conf <= the tree's threshold).  A list that ka_tree_upload
+ * would not take is refused with the cause and the task ("children before parents", "a node is consumed twice"). */
+int ka_debug_refine_marks(int numseq, int n_tasks, const int* tasks_abc, const float* conf, int pooled,
+                          int* tree_of_out, float* thr_out, int* marks_out, int* n_trees_out);
 /* Debug: 64 breadcrumb words written by workgroup 0 (context created with KA_TRACE=1 in the
    environment); readable while a kernel is still running. */
 int ka_debug_trace(ka_ctx* ctx, int* out64);
@@ -441,9 +460,10 @@ int ka_aln_guide_forest(ka_ctx* ctx, int n_fam, const int* fam_first, const uint
 /*
  * ka_run_encoded_refine for a batch of families in one call: the guide trees of all families (ka_guide_forest), one forest
  * ka_tree_upload with KA_FLAG_DEVICE_GAPS, ka_tree_build_consistency, ka_tree_run (refine_mode 3: ka_tree_refine), per
- * realignment iteration rows in HBM -> ka_aln_guide_forest -> upload with KA_FLAG_KEEP_CONSISTENCY -> run, refine_mode 1 (|
- * KA_REFINE_ADAPTIVE), rows.  refine_mode 2 (KALIGN_REFINE_CONFIDENT) is refused: its threshold is the median confidence of
- * one alignment's edges, and ka_tree_refine takes it over all tasks of a job.  All families share subm / scal.  Every
+ * realignment iteration rows in HBM -> ka_aln_guide_forest -> upload with KA_FLAG_KEEP_CONSISTENCY -> run, refine_mode 1 / 2 (|
+ * KA_REFINE_ADAPTIVE) through ka_tree_refine_trees, rows.  refine_mode 2 (KALIGN_REFINE_CONFIDENT) takes its threshold, the
+ * median confidence of one alignment's edges, per tree of the forest job: per family (a family of two sequences has one
+ * edge, which is refined).  All families share subm / scal.  Every
  * family comes out as ka_run_encoded_refine aligns it alone (both calls run the same sequence of steps on a forest job,
  * ka_run_encoded_refine on a job of one family): a family of n_f >= 3 sequences gets K_f = min(n_anchors, n_f) anchors, a
  * smaller one no table.  One forest job holds one anchor count, so families of equal K_f are one job and the jobs run one
@@ -458,6 +478,10 @@ int ka_aln_guide_forest(ka_ctx* ctx, int n_fam, const int* fam_first, const uint
  *   ka_batch_stats       measurements of the last batch: out6 = device ms of the guide trees' distance batches, of the
  *                        alignment runs (refinement included), of the realignment distances + UPGMA, of building rows; forest
  *                        jobs run; wall ms of the call
+ *   ka_batch_refine_stats  what refine_mode 2 did in the last batch, per family in input order: thr_out[n_fam] the family's
+ *                        threshold (0 for a family of one sequence), edges_out[n_fam] its tasks, refined_out[n_fam] the tasks
+ *                        at or below the threshold.  Fails, naming the cause, without a finished batch, after a batch of
+ *                        another refine_mode, and when n_fam is not the last batch's.
  */
 int ka_run_encoded_batch(ka_ctx* ctx, int n_fam, const int* fam_first, const uint8_t* tree_codes, const uint8_t* codes,
                          const uint8_t* letters, const int* off, const int* lens, const float* subm, const float* scal,
@@ -466,6 +490,7 @@ int ka_run_encoded_batch(ka_ctx* ctx, int n_fam, const int* fam_first, const uin
 long long ka_batch_rows_size(ka_ctx* ctx);
 int ka_batch_rows(ka_ctx* ctx, uint8_t* rows_out, long long cap_bytes);
 int ka_batch_stats(ka_ctx* ctx, double* out6);
+int ka_batch_refine_stats(ka_ctx* ctx, int n_fam, float* thr_out, int* edges_out, int* refined_out);
 
 /* Kernel time (HIP events on the launch stream) of the last ka_pairwise_batch / ka_bpm_batch, milliseconds. */
 float ka_pairwise_kernel_ms(ka_ctx* ctx);

@@ -44,7 +44,7 @@ DIST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTE
 
 EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_consistency_part",
            "ka_tree_consistency_part_range", "ka_tree_consistency_maps_dev", "ka_debug_set_hooks", "ka_debug_reload_env", "ka_debug_plan", "ka_debug_ctx_plan", "ka_debug_tp_launches", "ka_debug_kmeans_level", "ka_debug_kmeans_host", "ka_ctx_fallback_runs", "ka_ctx_arena_bytes", "ka_ctx_helped_tasks", "ka_ctx_create", "ka_ctx_destroy", "ka_ctx_set_stream", "ka_ctx_set_shared", "ka_last_error", "ka_abi_version",
-           "ka_msa_tree", "ka_tree_upload", "ka_tree_run", "ka_tree_refine", "ka_tree_sync", "ka_tree_paths_size",
+           "ka_msa_tree", "ka_tree_upload", "ka_tree_run", "ka_tree_refine", "ka_tree_refine_trees", "ka_debug_refine_marks", "ka_tree_sync", "ka_tree_paths_size",
            "ka_tree_download", "ka_tree_get_profile", "ka_tree_get_timing", "ka_debug_trace", "ka_tree_cells", "ka_tree_kernel_ms", "ka_tree_launch_ms",
            "ka_pairwise_batch", "ka_pairwise_kernel_ms", "ka_tree_build_consistency", "ka_tree_get_consistency",
            "ka_tree_run_tasks", "ka_tree_reset", "ka_tree_node_len", "ka_tree_set_profile", "ka_tree_download_tasks", "ka_weave_gaps",
@@ -67,7 +67,7 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_sum_fam_check", "ka_sum_fam_create", "ka_sum_fam_destroy", "ka_sum_fam_columns", "ka_sum_fam_summary", "ka_sum_fam_consensus",
            "ka_sum_fam_keep", "ka_sum_fam_compact", "ka_sum_fam_rows_size", "ka_sum_fam_rows", "ka_sum_fam_stats",
            "ka_guide_forest_from", "ka_guide_forest", "ka_aln_guide_forest", "ka_run_encoded_batch", "ka_batch_rows_size", "ka_batch_rows",
-           "ka_batch_stats"]
+           "ka_batch_stats", "ka_batch_refine_stats"]
 
 
 def lib_path():
@@ -117,6 +117,8 @@ def load_library():
     L.ka_tree_upload.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int]
     L.ka_tree_run.argtypes = [vp]
     L.ka_tree_refine.argtypes = [vp, C.c_int, vp]
+    L.ka_tree_refine_trees.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
+    L.ka_debug_refine_marks.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
     L.ka_tree_sync.argtypes = [vp]
     L.ka_tree_paths_size.argtypes = [vp]
     L.ka_tree_paths_size.restype = C.c_longlong
@@ -201,6 +203,7 @@ def load_library():
     L.ka_batch_rows_size.restype = C.c_longlong
     L.ka_batch_rows.argtypes = [vp, vp, C.c_longlong]
     L.ka_batch_stats.argtypes = [vp, vp]
+    L.ka_batch_refine_stats.argtypes = [vp, C.c_int, vp, vp, vp]
     L.ka_tree_get_consistency.argtypes = [vp, vp, vp]
     L.ka_pairwise_batch.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp,
                                     C.c_float, C.c_float, C.c_float, vp, vp, vp]
@@ -379,6 +382,18 @@ class Context:
         if cf is not None and len(cf) != self._job["ntasks"]:
             raise KalignAmdError("tree_refine: one confidence per task")
         self._chk(self.L.ka_tree_refine(self.h, int(mode), None if cf is None else _ptr(cf)))
+
+    def tree_refine_trees(self, mode, conf_in=None):
+        """ka_tree_refine_trees: tree_refine with mode 2's median per tree of a forest job (tree_refine pools it over the
+        job); on a job of one tree the same call.  Returns (tree_of[n_tasks], thr[n_trees]): the tree of every task, trees
+        numbered by their root task, and every tree's threshold (zeros in the other modes)."""
+        nt = self._job["ntasks"]
+        cf = None if conf_in is None else np.ascontiguousarray(conf_in, np.float32)
+        if cf is not None and len(cf) != nt:
+            raise KalignAmdError("tree_refine_trees: one confidence per task")
+        tree_of, thr, n = np.zeros(nt, np.int32), np.zeros(nt, np.float32), C.c_int(0)
+        self._chk(self.L.ka_tree_refine_trees(self.h, int(mode), None if cf is None else _ptr(cf), _ptr(tree_of), _ptr(thr), C.byref(n)))
+        return tree_of, thr[:n.value].copy()
 
     def tree_sync(self):
         self._chk(self.L.ka_tree_sync(self.h))
@@ -858,7 +873,8 @@ Context.aln_guide_forest = _aln_guide_forest
 def _run_families(self, families, subm, scal, n_anchors=0, weight=2.0, realign=0, refine=0, dm_scale=None, n_threads=4, gap=b"-"):
     """ka_run_encoded_batch: a batch of families from letters to rows in one call.  families: a list of
     (tree_codes, codes, letters), each as run_encoded takes them; all share subm / scal.  Every family is aligned as
-    run_encoded aligns it alone.  Returns one list of rows (bytes, in the order of the family's sequences) per family."""
+    run_encoded aligns it alone; refine as run_encoded's (2, KALIGN_REFINE_CONFIDENT: the median of every family's own
+    edges, batch_refine_stats says what it came to).  Returns one list of rows (bytes, in the order of the family's sequences) per family."""
     sizes = [len(f[1]) for f in families]
     if not sizes or min(sizes) < 1:
         raise KalignAmdError("run_families: every family needs a sequence")
@@ -901,7 +917,33 @@ def _batch_stats(self):
     return dict(guide_dist_ms=out[0], dp_ms=out[1], realign_tree_ms=out[2], rows_ms=out[3], jobs=int(out[4]), wall_ms=out[5])
 
 
+def _batch_refine_stats(self, n_fam):
+    """ka_batch_refine_stats of the last run_families(refine=2): per family in input order, dict of thr (float32, the
+    family's median confidence; 0 for a family of one sequence), edges (its tasks) and refined (those at or below thr)"""
+    n_fam = int(n_fam)
+    thr, edges, refined = np.zeros(max(n_fam, 1), np.float32), np.zeros(max(n_fam, 1), np.int32), np.zeros(max(n_fam, 1), np.int32)
+    self._chk(self.L.ka_batch_refine_stats(self.h, n_fam, _ptr(thr), _ptr(edges), _ptr(refined)))
+    return dict(thr=thr[:n_fam], edges=edges[:n_fam], refined=refined[:n_fam])
+
+
+def refine_marks(numseq, tasks, conf, pooled=False):
+    """ka_debug_refine_marks (no GPU, no context): the edges a mode-2 refinement pass marks -- tasks[n_tasks, 3] as
+    tree_upload takes them, a confidence per task; pooled: tree_refine's one median over the job, else tree_refine_trees'
+    median per tree.  Returns (tree_of[n_tasks], thr[n_trees], marks[n_tasks])."""
+    L = load_library()
+    tasks = np.ascontiguousarray(tasks, np.int32).reshape(-1, 3)
+    cf = np.ascontiguousarray(conf, np.float32)
+    nt = len(tasks)
+    if len(cf) != nt:
+        raise KalignAmdError("refine_marks: one confidence per task")
+    tree_of, thr, marks, n = np.zeros(max(nt, 1), np.int32), np.zeros(max(nt, 1), np.float32), np.zeros(max(nt, 1), np.int32), C.c_int(0)
+    if L.ka_debug_refine_marks(int(numseq), nt, _ptr(tasks), _ptr(cf), int(bool(pooled)), _ptr(tree_of), _ptr(thr), _ptr(marks), C.byref(n)):
+        raise KalignAmdError(L.ka_last_error().decode())
+    return tree_of[:nt], thr[:n.value].copy(), marks[:nt]
+
+
 Context.run_families = _run_families
+Context.batch_refine_stats = _batch_refine_stats
 Context.batch_rows = _batch_rows
 Context.batch_stats = _batch_stats
 

@@ -8,6 +8,7 @@
 // paths and all per-task state stay in HBM between levels.  Only the coded paths and the
 // per-task records come back to the host, once, at the end.
 #include "ka_ctx.h"
+#include "ka_marks.h"
 
 static thread_local std::string g_err;
 int fail(const std::string& m) { g_err = m; return KA_FAIL; }
@@ -17,7 +18,7 @@ __attribute__((visibility("hidden"))) int ka_fail_message(const char* m) { retur
 extern "C" const char* ka_last_error(void) { return g_err.c_str(); }
 struct ka_ctx;
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_guide.cpp)
-extern "C" int ka_abi_version(void) { return 21; }
+extern "C" int ka_abi_version(void) { return 22; }
 
 extern "C" int ka_ctx_create(int device, ka_ctx** out)
 {
@@ -428,15 +429,20 @@ static int refine_launch(ka_ctx* c, int mode)
         return KA_OK;
 }
 
-extern "C" int ka_tree_refine(ka_ctx* c, int mode_in, const float* conf_in)
+// The one refinement entry behind ka_tree_refine (pooled: mode 2 takes ONE median over all tasks of the job) and
+// ka_tree_refine_trees (a median per tree, ka_marks.h).  The marks go into descs[t].refine -- not part of the launch plan, so
+// a watchdog re-plan in ka_tree_sync keeps them.  tree_of_out / thr_out / n_trees_out may be null.
+static int tree_refine(const char* who, ka_ctx* c, int mode_in, const float* conf_in, bool pooled,
+                       int* tree_of_out, float* thr_out, int* n_trees_out)
 {
+        const std::string me(who);
         if (!c || !c->have_job) return fail("no uploaded job");
         const int mode = mode_in & 255, adaptive = mode_in & KA_REFINE_ADAPTIVE, trials = mode_in & KA_REFINE_TRIALS(255);
         if (mode < 1 || mode > 4 || (mode_in & ~(255 | KA_REFINE_ADAPTIVE | KA_REFINE_TRIALS(255))))
-                return fail("ka_tree_refine: mode must be 1 (all), 2 (confident), 3 (inline) or 4 (first pass, exact confidences), optionally | KA_REFINE_ADAPTIVE");
-        if (trials && mode != 3) return fail("ka_tree_refine: KA_REFINE_TRIALS goes with mode 3 (create_msa_tree_inline_refine)");
-        if (adaptive && mode != 1 && mode != 2) return fail("ka_tree_refine: KA_REFINE_ADAPTIVE goes with modes 1 and 2 (refine_edge)");
-        if (c->n_tasks < 1) return fail("ka_tree_refine: no tasks");
+                return fail(me + ": mode must be 1 (all), 2 (confident), 3 (inline) or 4 (first pass, exact confidences), optionally | KA_REFINE_ADAPTIVE");
+        if (trials && mode != 3) return fail(me + ": KA_REFINE_TRIALS goes with mode 3 (create_msa_tree_inline_refine)");
+        if (adaptive && mode != 1 && mode != 2) return fail(me + ": KA_REFINE_ADAPTIVE goes with modes 1 and 2 (refine_edge)");
+        if (c->n_tasks < 1) return fail(me + ": no tasks");
         HIPCHK(hipSetDevice(c->device));
         if (c->ran && !c->synced && ka_tree_sync(c)) return KA_FAIL;
         if (!c->have_colof) {                            // the sum-of-pairs score reads every member's column
@@ -456,15 +462,28 @@ extern "C" int ka_tree_refine(ka_ctx* c, int mode_in, const float* conf_in)
                 for (int t = 0; t < c->n_tasks; t++) conf[t] = r[t].confidence;
                 conf_in = conf.data();
         }
-        float thr = 0.0f;
-        if (mode == 2) {                                 // compute_confidence_threshold (aln_refine.c:674-712): the median
-                std::vector<float> v(conf_in, conf_in + c->n_tasks);
-                std::sort(v.begin(), v.end());
-                const int n = c->n_tasks;
-                thr = (n % 2 == 0) ? (v[n / 2 - 1] + v[n / 2]) / 2.0F : v[n / 2];
+        // compute_confidence_threshold (aln_refine.c:674-712): the median, of the job or of every tree; the other modes only ask
+        // for the trees when the caller wants them
+        KaMarks m;
+        if (mode == 2 || tree_of_out || thr_out || n_trees_out) {
+                std::string err;
+                if (ka_refine_marks(c->numseq, c->n_tasks, c->abc.data(), mode == 2 ? conf_in : nullptr, pooled, m, err)) return fail(me + ": " + err);
+                if (tree_of_out) std::copy(m.tree_of.begin(), m.tree_of.end(), tree_of_out);
+                if (thr_out) std::copy(m.thr.begin(), m.thr.end(), thr_out);
+                if (n_trees_out) *n_trees_out = m.n_trees;
         }
-        for (int t = 0; t < c->n_tasks; t++) c->descs[t].refine = mode == 1 ? 1 : (mode == 2 && conf_in[t] <= thr ? 1 : 0);
+        for (int t = 0; t < c->n_tasks; t++) c->descs[t].refine = mode == 1 ? 1 : (mode == 2 && m.mark[t] ? 1 : 0);
         return refine_launch(c, mode | adaptive | trials);
+}
+
+extern "C" int ka_tree_refine(ka_ctx* c, int mode_in, const float* conf_in)
+{
+        return tree_refine("ka_tree_refine", c, mode_in, conf_in, true, nullptr, nullptr, nullptr);
+}
+
+extern "C" int ka_tree_refine_trees(ka_ctx* c, int mode_in, const float* conf_in, int* tree_of_out, float* thr_out, int* n_trees_out)
+{
+        return tree_refine("ka_tree_refine_trees", c, mode_in, conf_in, false, tree_of_out, thr_out, n_trees_out);
 }
 
 extern "C" int ka_tree_sync(ka_ctx* c)
@@ -807,6 +826,8 @@ struct AlignJob {
         int n_tasks; int* tasks; float* sd;                          // the first trees; every realignment pass replaces them
         const float *subm, *scal;
         int n_anchors; float weight; int realign_iterations, refine_mode; uint8_t gap_char;
+        // refine_mode 2, per family of the job (null: not wanted): the threshold, the tasks, the marked tasks (ka_batch_refine_stats)
+        float* thr = nullptr; int* edges = nullptr; int* refined = nullptr;
 };
 
 // ends with rows_prepare done: alen, widest.  clk: the stage times of a batch (null: no event is recorded or waited for)
@@ -834,8 +855,20 @@ static int align_job(ka_ctx* c, const AlignJob& J, std::vector<int>& alen, int* 
                 if (align()) return KA_FAIL;
         }
         if (base == 1 || base == 2) {
-                if (ka_tree_refine(c, J.refine_mode, nullptr) || ka_tree_sync(c)) return KA_FAIL;
+                // (mode 2: a median per tree -- a family is a tree, and trees are numbered by their roots, so in the families' order)
+                const bool stats = base == 2 && J.thr;
+                std::vector<int> tree_of(stats ? J.n_tasks : 0);
+                std::vector<float> thr(stats ? J.n_tasks : 0);
+                int n_trees = 0;
+                if (ka_tree_refine_trees(c, J.refine_mode, nullptr, stats ? tree_of.data() : nullptr, stats ? thr.data() : nullptr, stats ? &n_trees : nullptr) ||
+                    ka_tree_sync(c))
+                        return KA_FAIL;
                 if (clk) clk->run_done(c);
+                if (stats) {
+                        if (n_trees != J.n_fam) return fail("ka_run_encoded_batch: a forest job does not hold one tree per family");
+                        for (int f = 0; f < J.n_fam; f++) { J.thr[f] = thr[f]; J.edges[f] = J.refined[f] = 0; }
+                        for (int t = 0; t < J.n_tasks; t++) { J.edges[tree_of[t]]++; J.refined[tree_of[t]] += c->descs[t].refine ? 1 : 0; }
+                }
         }
         return rows_prepare(c, J.letters, alen, widest);
 }
@@ -1028,10 +1061,7 @@ extern "C" int ka_run_encoded_batch(ka_ctx* c, int n_fam, const int* fam_first, 
         if (!c) return fail("null ctx");
         if (check_fam_first("ka_run_encoded_batch", n_fam, fam_first)) return KA_FAIL;
         if (!tree_codes || !codes || !letters || !off || !lens || !subm || !scal) return fail("ka_run_encoded_batch: bad arguments");
-        if (!refine_mode_ok(refine_mode)) return fail("ka_run_encoded_batch: refine_mode must be 0, 1 (optionally | KA_REFINE_ADAPTIVE) or 3");
-        // KALIGN_REFINE_CONFIDENT refines the edges at or below the MEDIAN confidence of an alignment's edges; ka_tree_refine takes that
-        // median over all tasks of a job, which in a forest job would mix the families
-        if ((refine_mode & 255) == 2) return fail("ka_run_encoded_batch: refine_mode 2 (confident) is not available for a batch: its median would span the families");
+        if (!refine_mode_ok(refine_mode)) return fail("ka_run_encoded_batch: refine_mode must be 0, 1, 2 (optionally | KA_REFINE_ADAPTIVE) or 3");
         if (n_anchors > KA_CONS_MAX_ANCHORS) return fail("this build takes at most 128 consistency anchors (KA_CONS_MAX_ANCHORS)");
         HIPCHK(hipSetDevice(c->device));
         const auto t_start = std::chrono::steady_clock::now();
@@ -1063,6 +1093,11 @@ extern "C" int ka_run_encoded_batch(ka_ctx* c, int n_fam, const int* fam_first, 
                 }
         }
         std::vector<int> width(n_fam, 0);                              // every family's alignment length
+        // KALIGN_REFINE_CONFIDENT refines the edges at or below the MEDIAN confidence of an alignment's edges: every family's own
+        // (ka_tree_refine_trees); what it came to per family, for ka_batch_refine_stats
+        const bool confident = (refine_mode & 255) == 2;
+        std::vector<float> r_thr(confident ? n_fam : 0, 0.0f);
+        std::vector<int> r_edges(confident ? n_fam : 0, 0), r_refined(confident ? n_fam : 0, 0);
         std::vector<std::vector<uint8_t>> group_rows(groups.size());   // a job's rows, its families packed in order
         for (size_t g = 0; g < groups.size(); g++) {
                 const std::vector<int>& G = groups[g];
@@ -1094,11 +1129,15 @@ extern "C" int ka_run_encoded_batch(ka_ctx* c, int n_fam, const int* fam_first, 
                                                 v < numseq ? g_fam_first[x] + (v - fam_first[f]) : gn + g_t_first[x] + (v - numseq - t_first[f]);
                                 }
                 }
-                const AlignJob J{ gn, (int)G.size(), g_fam_first.data(), g_codes.data(), g_letters.data(), g_off.data(), g_lens.data(), gt, g_tasks.data(),
-                                  g_sd.data(), subm, scal, K, weight, realign_iterations, refine_mode, gap_char };
+                AlignJob J{ gn, (int)G.size(), g_fam_first.data(), g_codes.data(), g_letters.data(), g_off.data(), g_lens.data(), gt, g_tasks.data(),
+                            g_sd.data(), subm, scal, K, weight, realign_iterations, refine_mode, gap_char };
+                std::vector<float> g_thr(confident ? G.size() : 0);
+                std::vector<int> g_edges(g_thr.size()), g_refined(g_thr.size());
+                if (confident) { J.thr = g_thr.data(); J.edges = g_edges.data(); J.refined = g_refined.data(); }
                 std::vector<int> alen;
                 int widest = 0;
                 if (align_job(c, J, alen, &widest, &clk)) return KA_FAIL;
+                for (size_t x = 0; confident && x < G.size(); x++) { r_thr[G[x]] = g_thr[x]; r_edges[G[x]] = g_edges[x]; r_refined[G[x]] = g_refined[x]; }
                 // the job's rows, packed, straight into host memory
                 std::vector<long long> row_off(gn);
                 long long bytes = 0;
@@ -1139,6 +1178,8 @@ extern "C" int ka_run_encoded_batch(ka_ctx* c, int n_fam, const int* fam_first, 
                         for (int i = fam_first[f]; i < fam_first[f + 1]; i++) alnlen_out[i] = width[f];
         c->batch_rows.swap(packed);
         c->have_batch = true;
+        c->batch_n_fam = n_fam; c->batch_confident = confident;
+        c->batch_thr.swap(r_thr); c->batch_edges.swap(r_edges); c->batch_refined.swap(r_refined);
         stats[4] = (double)groups.size();
         stats[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
         memcpy(c->batch_stats, stats, sizeof(stats));
@@ -1161,6 +1202,18 @@ extern "C" int ka_batch_stats(ka_ctx* c, double* out6)
 {
         if (!c || !c->have_batch || !out6) return fail("ka_batch_stats: no finished ka_run_encoded_batch on this context");
         memcpy(out6, c->batch_stats, sizeof(c->batch_stats));
+        return KA_OK;
+}
+
+extern "C" int ka_batch_refine_stats(ka_ctx* c, int n_fam, float* thr_out, int* edges_out, int* refined_out)
+{
+        if (!c || !c->have_batch) return fail("ka_batch_refine_stats: no finished ka_run_encoded_batch on this context");
+        if (!thr_out || !edges_out || !refined_out) return fail("ka_batch_refine_stats: null argument");
+        if (!c->batch_confident) return fail("ka_batch_refine_stats: the last batch did not run refine_mode 2 (confident)");
+        if (n_fam != c->batch_n_fam) return fail("ka_batch_refine_stats: n_fam is not the last batch's (" + std::to_string(c->batch_n_fam) + " families)");
+        std::copy(c->batch_thr.begin(), c->batch_thr.end(), thr_out);
+        std::copy(c->batch_edges.begin(), c->batch_edges.end(), edges_out);
+        std::copy(c->batch_refined.begin(), c->batch_refined.end(), refined_out);
         return KA_OK;
 }
 

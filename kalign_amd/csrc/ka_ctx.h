@@ -117,7 +117,7 @@ struct ka_ctx : KaPlan {
         int flags = 0;
         std::vector<int> off;
         std::vector<int> level_ids_flat, level_off;
-        int refine_mode = 0;                         // the run in flight is a refinement pass (ka_tree_refine): 1 all, 2 confident
+        int refine_mode = 0;                         // the run in flight is a refinement pass (ka_tree_refine / _refine_trees): 1 all, 2 confident
         DevBuf<int2> d_refine_blocks;                   // its workgroup table, level after level (refine_blocks)
         std::vector<int> refine_off;                    // [levels + 1] first block of every level in it
         bool shared_by_fallback = false;             // shared_gpu was forced by a join watchdog (ka_tree_sync), not by the caller
@@ -190,6 +190,12 @@ struct ka_ctx : KaPlan {
         std::vector<uint8_t> batch_rows;             // the finished rows of the last ka_run_encoded_batch, packed (ka_batch_rows)
         bool have_batch = false;
         double batch_stats[6] = {0, 0, 0, 0, 0, 0};  // ka_batch_stats
+        // ka_batch_refine_stats: the last batch's families, whether it ran refine_mode 2, and then per family the threshold,
+        // the tasks and the marked tasks
+        int batch_n_fam = 0;
+        bool batch_confident = false;
+        std::vector<float> batch_thr;
+        std::vector<int> batch_edges, batch_refined;
         DevBuf<long long> d_cons_map_off, d_sip_off;
 };
 

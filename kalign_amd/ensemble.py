@@ -74,7 +74,8 @@ def finish_ensembles(ctx, member_rows, letters, min_support=0, rerun_refined=Non
     with the batch (Context.family_ensemble).  member_rows[k][f]: the rows of member k of family f (what k calls of
     Context.run_families return); letters[f]: the sequences of family f.  min_support as finish_ensemble's, for every family.
     rerun_refined(list of (f, best_k)) is asked once, for the families whose selected member beat the consensus, and
-    returns their refined rows in that order.  n_threads: host threads of the consensus (1..16).
+    returns their refined rows in that order (rerun_refined_batch builds one over Context.run_families(refine=2)).
+    n_threads: host threads of the consensus (1..16).
     Returns one dict per family with finish_ensemble's keys, each equal to finish_ensemble run on that family alone
     (stats: the batch's, the same dict in every family)."""
     n_runs = len(member_rows)
@@ -127,6 +128,39 @@ def finish_ensembles(ctx, member_rows, letters, min_support=0, rerun_refined=Non
         return outs
     finally:
         ens.close()
+
+
+def rerun_refined_batch(ctx, families, subm, member, ranks=None, **run_kw):
+    """A rerun_refined for finish_ensembles: the selected members re-run with refine mode 2 (KALIGN_REFINE_CONFIDENT, as
+    kalign_ensemble re-runs them, ensemble.c:403-451) through Context.run_families -- one batch call per distinct
+    member, since a batch call holds one scal.
+    families[f]: (tree_codes, codes, letters) as run_families takes them; member(k, fs) is the caller's and returns
+    (scal_k, dm_scale) for member k and the families fs (a list of indices into families): the member's scoring and None
+    or one block of n * min(32, n) guide-tree multipliers per family of fs (the random numbers stay the caller's);
+    ranks[f], when given, maps family f's rows back to input order (row i belongs to input sequence ranks[f][i]), which
+    is what finish_ensembles takes; run_kw goes to run_families (n_anchors, weight, realign, n_threads, gap).
+    The callable returned takes [(f, best_k), ...] and returns those families' rows in that order."""
+    def rerun(ask):
+        ask = [(int(f), int(k)) for f, k in ask]
+        by_member = {}
+        for f, k in ask:
+            if f in by_member.setdefault(k, []):
+                raise KalignAmdError("rerun_refined_batch: family %d is asked for twice with member %d" % (f, k))
+            by_member[k].append(f)
+        rows = {}
+        for k in sorted(by_member):
+            fs = by_member[k]
+            scal_k, dm_scale = member(k, list(fs))
+            got = ctx.run_families([families[f] for f in fs], subm, scal_k, dm_scale=dm_scale, refine=2, **run_kw)
+            for f, r in zip(fs, got):
+                if ranks is not None:
+                    back = [None] * len(r)
+                    for i, x in enumerate(ranks[f]):
+                        back[int(x)] = r[i]
+                    r = back
+                rows[(f, k)] = r
+        return [rows[fk] for fk in ask]
+    return rerun
 
 
 def consensus_from_poar(ctx, letters, poar_path, min_support):
