@@ -839,6 +839,29 @@ int  ka_debug_ens_fam_consensus_host(int n_fam, const int* fam_first, const int*
  *                        call (0 and 0 when it was refused).  The hand-outs -- columns, summary, rows -- are copies of what
  *                        those calls left and do not count.
  * A refused call (a threshold outside [0, 1] or NaN, a mask offset past the end) launches nothing and leaves the handle usable.
+ *
+ * The pairwise identity matrices (kalign.utils.pairwise_identity_matrix) of the rows a handle holds -- no new upload.  For
+ * family f of N_f rows and every pair (i, j):
+ *   compared[i][j]  the columns where both rows hold a character (the rule for a byte above, with the handle's gap_char);
+ *   matches[i][j]   those of them where the two bytes are equal; on the diagonal both are the characters of row i;
+ *   identity[i][j]  (double)matches / (double)compared for i != j, 0.0 when compared is 0; identity[i][i] is 1.0 always, for
+ *                   an all-gap row too (the utility sets it without looking).
+ * All three are symmetric and both triangles are written.  The matrices are packed, families in order: family f's N_f x N_f
+ * block is row-major and starts at entry sum over g < f of N_g^2.  Counts are int32 (a width is below 2^31).
+ *   ka_sum_fam_identity_entries  host only (no context, no GPU): the entries of each matrix, the sum of N_f^2; -1 with
+ *                        ka_last_error "ka_sum_fam_identity_entries: fam_first does not ascend from 0 to numseq",
+ *                        "ka_sum_fam_identity_entries: empty family" or, when the sum reaches 2^31,
+ *                        "ka_sum_fam_identity_entries: family 0: 46341 rows bring the matrices to 2147488281 entries; a batch
+ *                        holds fewer than 2^31" (the family at which the sum passes the bound, and the sum there).
+ *   ka_sum_fam_identity  each output optional, ka_sum_fam_identity_entries entries long.  The first call -- or the first
+ *                        after calls that computed nothing -- runs one kernel over the upper-triangle tiles of all families
+ *                        and leaves the three matrices on the device; later calls are copies.  One launch and one host
+ *                        synchronisation, whatever the number of families.  A batch that ka_sum_fam_identity_entries refuses
+ *                        is refused here ("ka_sum_fam_identity: family ...") before anything is launched, and the handle
+ *                        stays usable.
+ *   ka_sum_fam_identity_stats  out3: device ms of the identity pass [0]; kernel launches [1] and host synchronisations [2] of
+ *                        the call that computed the matrices (1 and 1; all 0 before).  Later calls, which only copy, leave the
+ *                        three values as they are, and no identity call touches ka_sum_fam_stats' six.
  */
 typedef struct ka_sum_fam ka_sum_fam;
 int  ka_sum_fam_check(int n_fam, const int* fam_first, const uint8_t* rows, const int* alnlens);
@@ -852,6 +875,9 @@ int  ka_sum_fam_compact(ka_sum_fam* h, const double* gap_thresholds, const int* 
 long long ka_sum_fam_rows_size(ka_sum_fam* h);
 int  ka_sum_fam_rows(ka_sum_fam* h, uint8_t* out, long long cap);
 int  ka_sum_fam_stats(ka_sum_fam* h, double* stats_out);
+long long ka_sum_fam_identity_entries(int n_fam, const int* fam_first);
+int  ka_sum_fam_identity(ka_sum_fam* h, int* matches_out, int* compared_out, double* identity_out);
+int  ka_sum_fam_identity_stats(ka_sum_fam* h, double* out3);
 
 #ifdef __cplusplus
 }

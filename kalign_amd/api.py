@@ -66,6 +66,7 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_debug_ens_fam_consensus_host",
            "ka_sum_fam_check", "ka_sum_fam_create", "ka_sum_fam_destroy", "ka_sum_fam_columns", "ka_sum_fam_summary", "ka_sum_fam_consensus",
            "ka_sum_fam_keep", "ka_sum_fam_compact", "ka_sum_fam_rows_size", "ka_sum_fam_rows", "ka_sum_fam_stats",
+           "ka_sum_fam_identity_entries", "ka_sum_fam_identity", "ka_sum_fam_identity_stats",
            "ka_guide_forest_from", "ka_guide_forest", "ka_aln_guide_forest", "ka_run_encoded_batch", "ka_batch_rows_size", "ka_batch_rows",
            "ka_batch_stats", "ka_batch_refine_stats"]
 
@@ -266,6 +267,10 @@ def load_library():
     L.ka_sum_fam_rows_size.restype = C.c_longlong
     L.ka_sum_fam_rows.argtypes = [vp, vp, C.c_longlong]
     L.ka_sum_fam_stats.argtypes = [vp, vp]
+    L.ka_sum_fam_identity_entries.argtypes = [C.c_int, vp]
+    L.ka_sum_fam_identity_entries.restype = C.c_longlong
+    L.ka_sum_fam_identity.argtypes = [vp, vp, vp, vp]
+    L.ka_sum_fam_identity_stats.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -1434,6 +1439,20 @@ Context.family_ensemble = _ens_fam_create
 
 SUM_COUNTS = ["gaps", "cells", "conserved_columns", "columns", "matching_pairs", "compared_pairs"]
 SUM_STATS = ["table_ms", "consensus_ms", "keep_ms", "compact_ms", "launches", "syncs"]
+IDENTITY_STATS = ["identity_ms", "launches", "syncs"]
+
+
+def identity_entries(sizes):
+    """ka_sum_fam_identity_entries: the entries of each identity matrix of a batch of families of these sizes, the sum of
+    n * n -- on the host alone; raises where the batch is refused (an empty family, 2^31 entries or more)"""
+    L = load_library()
+    sizes = [int(n) for n in sizes]
+    if any(n < 0 or n > 2 ** 31 - 1 for n in sizes) or sum(sizes) > 2 ** 31 - 1:
+        raise KalignAmdError("family sizes are counts of rows, fewer than 2^31 in all")
+    n = int(L.ka_sum_fam_identity_entries(len(sizes), _ptr(_fam_first(sizes))))
+    if n < 0:
+        raise KalignAmdError(L.ka_last_error().decode())
+    return n
 
 
 def pack_masks(column_masks, widths, what="alignment"):
@@ -1557,6 +1576,37 @@ class FamilySummary(_CtxChild):
         st = np.zeros(len(SUM_STATS), np.float64)
         self.ctx._chk(self.L.ka_sum_fam_stats(self.h, _ptr(st)))
         return {k: (float(v) if k.endswith("_ms") else int(v)) for k, v in zip(SUM_STATS, st)}
+
+
+    def identity(self, want_counts=False):
+        """pairwise_identity_matrix of every family: a float64 [n, n] array each -- matches / compared over the columns
+        where both rows hold a character, 0.0 where there is none, 1.0 on the diagonal.  want_counts: per family
+        (identity, matches, compared), the counts int32 [n, n].  The first call computes the matrices of the whole batch
+        in one launch and leaves them on the device; later calls copy."""
+        self._open()
+        sq = np.array(self.sizes, np.int64) ** 2
+        if int(sq.sum()) > 2 ** 31 - 1:
+            total = 1                                             # (refused by the call below, which says why)
+        else:
+            total = int(sq.sum())
+        ident = np.zeros(total, np.float64)
+        m = np.zeros(total, np.int32) if want_counts else None
+        c = np.zeros(total, np.int32) if want_counts else None
+        self.ctx._chk(self.L.ka_sum_fam_identity(self.h, _ptr(m), _ptr(c), _ptr(ident)))
+        first = np.concatenate([[0], np.cumsum(sq)])
+
+        def blocks(a):
+            return [a[first[f]:first[f + 1]].reshape(n, n) for f, n in enumerate(self.sizes)]
+
+        return list(zip(blocks(ident), blocks(m), blocks(c))) if want_counts else blocks(ident)
+
+    def identity_stats(self):
+        """ka_sum_fam_identity_stats: device ms of the identity pass, kernel launches and host synchronisations of the
+        identity() call that computed the matrices (zeros before it; unchanged by the calls that only copy)"""
+        self._open()
+        st = np.zeros(len(IDENTITY_STATS), np.float64)
+        self.ctx._chk(self.L.ka_sum_fam_identity_stats(self.h, _ptr(st)))
+        return {k: (float(v) if k.endswith("_ms") else int(v)) for k, v in zip(IDENTITY_STATS, st)}
 
 
 def _sum_fam_create(self, families_rows, gap=b"-"):

@@ -1,6 +1,6 @@
 // ka_sum.cpp -- host side of the summaries and trimming of finished rows (kalign.utils: alignment_stats,
-// consensus_sequence, remove_gap_columns, trim_alignment) for a batch of families: the ka_sum_fam handle of the C ABI.  One
-// alignment is a batch of one.
+// consensus_sequence, remove_gap_columns, trim_alignment, pairwise_identity_matrix) for a batch of families: the ka_sum_fam
+// handle of the C ABI.  One alignment is a batch of one.
 //
 // The rows are packed as ka_batch_rows hands them out (a row of W columns W + 1 bytes) and uploaded in one copy; the
 // column table (ka_sum.hip) is built once at create, with every family's exact sums and its character-presence mask.  The
@@ -39,6 +39,28 @@ int sum_fam_check(const char* who, int n_fam, const int* fam_first, const uint8_
                 if (items > INT32_MAX) return fail(me + ": more than 2^31 - 1 row chunks in the batch");
         }
         return KA_OK;
+}
+
+// the entries of each of the three identity matrices of a batch, the sum of N_f^2, or -1 (ka_sum_fam_identity_entries is
+// its public form; ka_sum_fam_identity runs it over the handle's families before anything is launched)
+long long idm_entries(const char* who, int n_fam, const int* fam_first)
+{
+        const std::string me(who);
+        if (n_fam < 1 || !fam_first) return fail(me + ": bad arguments"), -1;
+        if (fam_first[0] != 0) return fail(me + ": fam_first does not ascend from 0 to numseq"), -1;
+        for (int f = 0; f < n_fam; f++) {
+                if (fam_first[f + 1] < fam_first[f]) return fail(me + ": fam_first does not ascend from 0 to numseq"), -1;
+                if (fam_first[f + 1] == fam_first[f]) return fail(me + ": empty family"), -1;
+        }
+        long long sum = 0;
+        for (int f = 0; f < n_fam; f++) {
+                const long long N = fam_first[f + 1] - fam_first[f];
+                sum += N * N;                                    // (N < 2^31 and the sum so far < 2^31: no overflow)
+                if (sum > INT32_MAX)
+                        return fail(me + ": family " + std::to_string(f) + ": " + std::to_string(N) + " rows bring the matrices to " + std::to_string(sum) +
+                                    " entries; a batch holds fewer than 2^31"), -1;
+        }
+        return sum;
 }
 
 // the doubles of one family from its exact counts (counts[6] as ka_sum_fam_summary lays them out), each the one division
@@ -86,6 +108,13 @@ struct ka_sum_fam {
         hipEvent_t ev[2] = { nullptr, nullptr };
         double st[KA_SUM_STATS] = {};          // device ms [0..3]; [4], [5] are filled from the counters below
         int nLaunch = 0, nSync = 0;            // kernel launches (counted by the launchers, ka_sum.hip) and waits (wait()) of the last call that launches
+        // the identity matrices: computed by the first ka_sum_fam_identity, then kept on the device
+        bool haveIdm = false;
+        long long idmEntries = 0;
+        DevBuf<int> dIdmFirst, dMatches, dCompared;
+        DevBuf<unsigned> dIdmTiles;
+        DevBuf<double> dIdentity;
+        double idmSt[KA_SUM_IDM_STATS] = {};   // device ms, launches and waits of the call that computed them
 
         ~ka_sum_fam()
         {
@@ -94,6 +123,7 @@ struct ka_sum_fam {
                 dFams.release(); dFirst.release(); dNGap.release(); dNDistinct.release(); dTopCount.release(); dKeep.release(); dSrc.release();
                 dNewW.release(); dMasks.release(); dRows.release(); dTopChar.release(); dAmbiguous.release(); dCons.release(); dOut.release(); dSame.release();
                 dMaskOff.release(); dOutOff.release(); dFamSums.release(); dPresent.release(); dThr.release();
+                dIdmFirst.release(); dMatches.release(); dCompared.release(); dIdmTiles.release(); dIdentity.release();
         }
         float ms() { float m = 0.0f; (void)hipEventElapsedTime(&m, ev[0], ev[1]); return m; }
         // a call that launches (create, consensus, keep, compact): nothing launched, nothing waited for yet.  The hand-outs
@@ -123,6 +153,7 @@ struct ka_sum_fam {
         int thresholds(const char* who, const char* what, const double* thr, double dflt);
         // the column rule of keep and compact, checked and uploaded; *masked: the table carries masks
         int rule(const char* who, const double* gapThr, const int* masks, const long long* maskOff, bool* masked);
+        int identity(const char* who, int* matchesOut, int* comparedOut, double* identityOut);
 };
 
 int ka_sum_fam::create(const char* who, int n_fam, const int* fam_first, const uint8_t* rows, const int* alnlens)
@@ -338,6 +369,76 @@ extern "C" int ka_sum_fam_rows(ka_sum_fam* h, uint8_t* out, long long cap)
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipMemcpyAsync(out, h->dOut.p, (size_t)h->outBytes, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
+        return KA_OK;
+}
+
+// The tile table of the batch -- per family the tiles (bi, bj), bi <= bj, of ceil(N / T) tiles a side, tile row after tile
+// row -- and one launch over it; then the copies the caller asked for and the call's one wait.  Matrices that are already on
+// the device are only copied.
+int ka_sum_fam::identity(const char* who, int* matchesOut, int* comparedOut, double* identityOut)
+{
+        const std::string me(who);
+        std::vector<int> first;                                  // (read by the upload until the wait below)
+        std::vector<unsigned> tiles;
+        int launches = 0;
+        const bool compute = !haveIdm;
+        HIPCHK(hipSetDevice(device));
+        if (compute) {
+                std::vector<int> famFirst(nFam + 1, 0);
+                for (int f = 0; f < nFam; f++) famFirst[f + 1] = famFirst[f] + fams[f].N;
+                idmEntries = idm_entries(who, nFam, famFirst.data());
+                if (idmEntries < 0) return KA_FAIL;
+                first.assign((size_t)2 * (nFam + 1), 0);         // tiles, entries
+                long long ent = 0;
+                for (int f = 0; f < nFam; f++) {
+                        const int nt = (fams[f].N + KA_SUM_IDM_T - 1) / KA_SUM_IDM_T;
+                        first[f] = (int)tiles.size(); first[nFam + 1 + f] = (int)ent;
+                        for (int bi = 0; bi < nt; bi++)
+                                for (int bj = bi; bj < nt; bj++) tiles.push_back((unsigned)bi << 16 | (unsigned)bj);
+                        ent += (long long)fams[f].N * fams[f].N;
+                }
+                first[nFam] = (int)tiles.size(); first[2 * nFam + 1] = (int)ent;
+                if (dIdmFirst.alloc(first.size()) || dIdmTiles.alloc(tiles.size()) || dMatches.alloc((size_t)idmEntries) ||
+                    dCompared.alloc((size_t)idmEntries) || dIdentity.alloc((size_t)idmEntries))
+                        return fail(me + ": out of device memory");
+                HIPCHK(hipMemcpyAsync(dIdmFirst.p, first.data(), sizeof(int) * first.size(), hipMemcpyHostToDevice, stream));
+                HIPCHK(hipMemcpyAsync(dIdmTiles.p, tiles.data(), sizeof(unsigned) * tiles.size(), hipMemcpyHostToDevice, stream));
+                KaIdmTab a{};
+                a.nFam = nFam; a.nTiles = (int)tiles.size(); a.gap = gap;
+                a.fams = dFams.p; a.tileFirst = dIdmFirst.p; a.entFirst = dIdmFirst.p + nFam + 1; a.tiles = dIdmTiles.p; a.rows = dRows.p; a.bytes = bytes;
+                a.matches = dMatches.p; a.compared = dCompared.p; a.identity = dIdentity.p;
+                HIPCHK(hipEventRecord(ev[0], stream));
+                if (ka_sum_run_identity(a, stream, &launches)) return fail(me + ": the identity kernel's LDS was refused");
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipEventRecord(ev[1], stream));
+        }
+        const size_t n = (size_t)idmEntries;
+        if (matchesOut) HIPCHK(hipMemcpyAsync(matchesOut, dMatches.p, sizeof(int) * n, hipMemcpyDeviceToHost, stream));
+        if (comparedOut) HIPCHK(hipMemcpyAsync(comparedOut, dCompared.p, sizeof(int) * n, hipMemcpyDeviceToHost, stream));
+        if (identityOut) HIPCHK(hipMemcpyAsync(identityOut, dIdentity.p, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (compute) {
+                idmSt[0] = ms(); idmSt[1] = launches; idmSt[2] = 1;
+                haveIdm = true;
+        }
+        return KA_OK;
+}
+
+extern "C" long long ka_sum_fam_identity_entries(int n_fam, const int* fam_first)
+{
+        return idm_entries("ka_sum_fam_identity_entries", n_fam, fam_first);
+}
+
+extern "C" int ka_sum_fam_identity(ka_sum_fam* h, int* matches_out, int* compared_out, double* identity_out)
+{
+        if (!h) return fail("ka_sum_fam_identity: bad arguments");
+        return h->identity("ka_sum_fam_identity", matches_out, compared_out, identity_out);
+}
+
+extern "C" int ka_sum_fam_identity_stats(ka_sum_fam* h, double* out3)
+{
+        if (!h) return fail("ka_sum_fam_identity_stats: bad arguments");
+        if (out3) std::copy_n(h->idmSt, KA_SUM_IDM_STATS, out3);
         return KA_OK;
 }
 

@@ -15,6 +15,18 @@
 #define KA_SUM_CHUNK 256           // output columns per wave of the row gather: four bytes per lane
 #define KA_SUM_FAMSUMS 4           // a family's sums from the device: see the enum below
 #define KA_SUM_STATS 6             // ka_sum_fam_stats: see include/kalign_amd.h
+// the identity matrices (sum_identity): a workgroup of four waves owns a T x T tile of pairs of rows of one family, a wave a
+// quarter of it (8 x 8 lanes), a lane KA_SUM_IDM_RT x KA_SUM_IDM_RT pairs
+// (both measured against 4 x 4 pairs and 256 columns: DESIGN.md 4p; -DKA_SUM_IDM_RT=4 -DKA_SUM_IDM_CHUNK=256 builds those)
+#ifndef KA_SUM_IDM_RT
+#define KA_SUM_IDM_RT 2
+#endif
+#define KA_SUM_IDM_T (16 * KA_SUM_IDM_RT)      // rows per side of a tile of pairs: 32
+#ifndef KA_SUM_IDM_CHUNK
+#define KA_SUM_IDM_CHUNK 128       // columns staged in LDS per step over the width
+#endif
+#define KA_SUM_IDM_THREADS 256
+#define KA_SUM_IDM_STATS 3         // ka_sum_fam_identity_stats: see include/kalign_amd.h
 
 enum {
         KA_SUM_GAPS = 0,           // gap bytes
@@ -56,8 +68,24 @@ struct KaSumTab {
         uint8_t* out;                          // consensus rows, or compacted rows
 };
 
+// the identity matrices of the batch: family f's N x N block, row-major, starts at entry entFirst[f] of each of the three
+// matrices; its upper-triangle tiles (tile row <= tile column) are tileFirst[f] .. tileFirst[f + 1] - 1 of `tiles`
+struct KaIdmTab {
+        int nFam, nTiles;
+        uint8_t gap;
+        const KaSumFam* fams;                  // [nFam]
+        const int* tileFirst;                  // [nFam + 1]
+        const int* entFirst;                   // [nFam + 1] (the batch holds fewer than 2^31 entries)
+        const unsigned* tiles;                 // [nTiles] tile row << 16 | tile column, inside the family
+        const uint8_t* rows;
+        long long bytes;                       // of the rows: nothing from there on is read
+        int* matches; int* compared;           // [entries]
+        double* identity;                      // [entries]
+};
+
 // ka_sum.hip: every launcher adds the kernels it launches to *launches
 int ka_sum_run_columns(const KaSumTab& a, hipStream_t s, int* launches);     // the column table, the family sums and the presence masks (zeroed first by the caller); 1: the LDS was refused
 void ka_sum_run_consensus(const KaSumTab& a, hipStream_t s, int* launches);
 void ka_sum_run_keep(const KaSumTab& a, hipStream_t s, int* launches);       // keep flags, then the per-family scan: src, newW
 void ka_sum_run_gather(const KaSumTab& a, hipStream_t s, int* launches);     // outOff over the families, then the rows
+int ka_sum_run_identity(const KaIdmTab& a, hipStream_t s, int* launches);     // the three matrices, both triangles; 1: the LDS was refused

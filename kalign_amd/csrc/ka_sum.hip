@@ -15,6 +15,11 @@
 //   sum_scan       a workgroup per family: the kept columns numbered in order (256 columns a step, the count carried)
 //   sum_offsets    one workgroup: where every family's compacted rows start
 //   sum_gather     a wave per (row, chunk of 256 output columns): four consecutive output bytes per lane
+//   sum_identity   the pairwise identity matrices: a workgroup per upper-triangle tile of 32 x 32 pairs of rows of one family
+//                  (a table of tiles; the family by ka_fam_find over its first-tile table).  The width in chunks of 128
+//                  columns staged in LDS with per-row character marks; a lane holds 2 x 2 pairs and takes four columns per
+//                  32-bit operation: XOR, an exact zero-byte test, population counts.  Exact counts, the doubles one
+//                  division each, both triangles written by the tile of the upper one.
 #include <algorithm>
 #include "ka_sum.h"
 #include "ka_msa.h"
@@ -242,6 +247,131 @@ __global__ __launch_bounds__(256) void sum_gather(KaSumTab a)
         }
 }
 
+// ---- the identity matrices ----------------------------------------------------------------------------------------------
+// A row's chunk in LDS: its bytes as they stand, four columns a word (0 past the row's width and in a row past the family),
+// and beside them its marks, 0x80 in every byte that holds a character.  Rows lie kIdmRowWords words apart: a quarter of
+// that is odd, so the 16-byte reads of 8 consecutive rows at one column start at 8 different multiples of 4 modulo 64 and
+// never share a bank.  A wave's lanes are 8 x 8: lane & 7 picks the row on the i side, lane >> 3 on the j side.  In each of
+// ds_read_b128's four groups of 16 lanes an i-side read has 8 distinct rows (each read by two lanes: a broadcast) and a
+// j-side read 4 -- consecutive rows at one column, so distinct banks: no read of the loop has a bank conflict.
+constexpr int kIdmRowWords = KA_SUM_IDM_CHUNK / 4 + 4;
+constexpr int kIdmRows = 2 * KA_SUM_IDM_T;                         // the i side, then the j side (a diagonal tile: one side)
+constexpr size_t kIdmLds = sizeof(unsigned) * 2 * kIdmRows * kIdmRowWords;      // bytes and marks: 18 432 bytes
+static_assert(kIdmRowWords % 4 == 0 && (kIdmRowWords / 4) % 2 == 1, "consecutive rows' 16-byte reads fall into different banks");
+static_assert(2 * kIdmLds <= 163840, "two identity workgroups per CU");
+static_assert(KA_SUM_IDM_THREADS == 256 && KA_SUM_IDM_CHUNK % 16 == 0, "four waves of 8 x 8 lanes; whole 16-byte reads");
+constexpr int kIdmAhead = 16;                                      // words a thread loads before it uses the first, while staging
+struct __attribute__((aligned(4))) IdmTwo { unsigned lo, hi; };     // two aligned words of the upload (which starts on a word)
+
+// one word of two rows: columns where both hold a character, and those of them where the bytes are equal.  x | t has bit 7
+// of a byte set exactly when the byte of x is not 0: t's bit 7 says that the low seven bits are not 0 (0x7f + 0x7f does not
+// carry into the next byte), x's own bit 7 the rest.  Exact for every byte value, 0x01 beside 0x00 and 0x80 included.
+__device__ __forceinline__ void idm_word(unsigned xi, unsigned yi, unsigned xj, unsigned yj, int& m, int& c)
+{
+        const unsigned both = yi & yj;
+        const unsigned x = xi ^ xj;
+        const unsigned t = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
+        c += __popc(both);
+        m += __popc(__builtin_amdgcn_bitop3_b32(both, x, t, 0x10));    // both & ~x & ~t in one operation
+}
+
+__global__ __launch_bounds__(KA_SUM_IDM_THREADS) void sum_identity(KaIdmTab a)
+{
+        constexpr int T = KA_SUM_IDM_T, RT = KA_SUM_IDM_RT, WORDS = KA_SUM_IDM_CHUNK / 4;
+        extern __shared__ __attribute__((aligned(16))) unsigned idm_lds[];
+        unsigned* dat = idm_lds;                                 // [row of the tile's two sides][kIdmRowWords]
+        unsigned* mrk = idm_lds + kIdmRows * kIdmRowWords;
+        const int tile = blockIdx.x;
+        const int f = ka_fam_find(a.tileFirst, a.nFam, tile);
+        const KaSumFam fam = a.fams[f];
+        const unsigned packed = a.tiles[tile];
+        const int i0 = (int)(packed >> 16) * T, j0 = (int)(packed & 0xffffu) * T;
+        const bool diag = i0 == j0;                              // one side is staged, and the quarter below the diagonal idles
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int wi = wave >> 1, wj = wave & 1, ti = lane & 7, tj = lane >> 3;
+        const bool idle = diag && wi > wj;                       // (the whole wave)
+        const unsigned gap4 = a.gap * 0x01010101u;
+        const long long stride = (long long)fam.W + 1;
+        const int nStage = (diag ? T : 2 * T) * WORDS;
+        const int ri = wi * 8 * RT + ti, rj = (diag ? 0 : T) + wj * 8 * RT + tj;    // this lane's first rows in LDS; the others 8 apart
+        int m[RT][RT] = {}, c[RT][RT] = {};
+        for (int c0 = 0; c0 < fam.W; c0 += KA_SUM_IDM_CHUNK) {
+                // stage: neighbouring lanes take neighbouring words of one row.  A row starts at any byte, so a word's four
+                // columns come from the two aligned words of the upload that hold them, shifted together -- where both lie
+                // inside the upload; the few words at its very end are put together byte by byte, no byte past the end is
+                // read.  The loads of kIdmAhead words go out before the first is used.
+                for (int s0 = 0; s0 < nStage; s0 += KA_SUM_IDM_THREADS * kIdmAhead) {
+                        IdmTwo w[kIdmAhead];
+#pragma unroll
+                        for (int u = 0; u < kIdmAhead; u++) {
+                                const int idx = s0 + u * KA_SUM_IDM_THREADS + threadIdx.x;
+                                const int row = idx / WORDS, col = c0 + 4 * (idx % WORDS);
+                                const int gr = row < T ? i0 + row : j0 + row - T;
+                                const long long al = (fam.rowOff + (long long)gr * stride + col) & ~3ll;
+                                w[u] = IdmTwo{ 0, 0 };
+                                if (idx < nStage && gr < fam.N && col < fam.W && al + 8 <= a.bytes) w[u] = *(const IdmTwo*)(a.rows + al);
+                        }
+#pragma unroll
+                        for (int u = 0; u < kIdmAhead; u++) {
+                                const int idx = s0 + u * KA_SUM_IDM_THREADS + threadIdx.x;
+                                if (idx >= nStage) continue;
+                                const int row = idx / WORDS, k = idx % WORDS, col = c0 + 4 * k;
+                                const int gr = row < T ? i0 + row : j0 + row - T;
+                                const int nb = gr < fam.N ? min(4, max(0, fam.W - col)) : 0;       // the word's columns inside the row
+                                const unsigned keep = nb >= 4 ? 0xffffffffu : (1u << (8 * nb)) - 1u;
+                                const long long g = fam.rowOff + (long long)gr * stride + col;
+                                unsigned d = __funnelshift_r(w[u].lo, w[u].hi, 8u * (unsigned)(g & 3));
+                                if (nb > 0 && (g & ~3ll) + 8 > a.bytes) {                          // (the upload's last bytes)
+                                        d = 0;
+                                        for (int q = 0; q < nb; q++) d |= (unsigned)a.rows[g + q] << (8 * q);
+                                }
+                                d &= keep;
+                                const unsigned x = d ^ gap4;                                     // a byte of x is 0 at a gap
+                                dat[row * kIdmRowWords + k] = d;
+                                mrk[row * kIdmRowWords + k] = (x | ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u & keep;
+                        }
+                }
+                __syncthreads();
+                if (!idle) {
+                        const int nq = (min(KA_SUM_IDM_CHUNK, fam.W - c0) + 15) / 16;
+                        for (int q = 0; q < nq; q++) {
+                                uint4 xi[RT], yi[RT];
+#pragma unroll
+                                for (int u = 0; u < RT; u++) {
+                                        xi[u] = *(const uint4*)(dat + (ri + 8 * u) * kIdmRowWords + 4 * q);
+                                        yi[u] = *(const uint4*)(mrk + (ri + 8 * u) * kIdmRowWords + 4 * q);
+                                }
+#pragma unroll
+                                for (int v = 0; v < RT; v++) {
+                                        const uint4 xj = *(const uint4*)(dat + (rj + 8 * v) * kIdmRowWords + 4 * q);
+                                        const uint4 yj = *(const uint4*)(mrk + (rj + 8 * v) * kIdmRowWords + 4 * q);
+#pragma unroll
+                                        for (int u = 0; u < RT; u++) {
+                                                idm_word(xi[u].x, yi[u].x, xj.x, yj.x, m[u][v], c[u][v]);
+                                                idm_word(xi[u].y, yi[u].y, xj.y, yj.y, m[u][v], c[u][v]);
+                                                idm_word(xi[u].z, yi[u].z, xj.z, yj.z, m[u][v], c[u][v]);
+                                                idm_word(xi[u].w, yi[u].w, xj.w, yj.w, m[u][v], c[u][v]);
+                                        }
+                                }
+                        }
+                }
+                __syncthreads();
+        }
+        if (idle) return;
+        const long long ent = a.entFirst[f];
+#pragma unroll
+        for (int u = 0; u < RT; u++)
+#pragma unroll
+                for (int v = 0; v < RT; v++) {
+                        const int i = i0 + wi * 8 * RT + ti + 8 * u, j = j0 + wj * 8 * RT + tj + 8 * v;
+                        if (i >= fam.N || j >= fam.N || i > j) continue;     // (i > j: in a diagonal tile only; its mirror writes it)
+                        const double id = i == j ? 1.0 : c[u][v] > 0 ? (double)m[u][v] / (double)c[u][v] : 0.0;
+                        const long long e = ent + (long long)i * fam.N + j, e2 = ent + (long long)j * fam.N + i;
+                        a.matches[e] = m[u][v]; a.compared[e] = c[u][v]; a.identity[e] = id;
+                        if (i != j) { a.matches[e2] = m[u][v]; a.compared[e2] = c[u][v]; a.identity[e2] = id; }
+                }
+}
+
 } // namespace
 
 // Each launcher counts its launches where it makes them (*launches is the caller's counter of the call).
@@ -275,4 +405,12 @@ void ka_sum_run_gather(const KaSumTab& a, hipStream_t s, int* launches)
         ++*launches;
         sum_gather<<<(unsigned)(((long long)a.nItems + 3) / 4), 256, 0, s>>>(a);
         ++*launches;
+}
+
+int ka_sum_run_identity(const KaIdmTab& a, hipStream_t s, int* launches)
+{
+        if (hipFuncSetAttribute((const void*)sum_identity, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kIdmLds) != hipSuccess) return 1;
+        sum_identity<<<(unsigned)a.nTiles, KA_SUM_IDM_THREADS, kIdmLds, s>>>(a);
+        ++*launches;
+        return 0;
 }

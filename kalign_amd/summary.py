@@ -1,5 +1,5 @@
-"""python-kalign's kalign.utils on the device: alignment_stats, consensus_sequence, remove_gap_columns and trim_alignment
-with the reference's names, arguments and return shapes, for one alignment (a list of str) and -- in one device pass, the
+"""python-kalign's kalign.utils on the device: alignment_stats, consensus_sequence, remove_gap_columns, trim_alignment and
+pairwise_identity_matrix with the reference's names, arguments and return shapes, for one alignment (a list of str) and -- in one device pass, the
 number of launches independent of the batch -- for a list of families (Context.family_summary = ka_sum_fam).
 
 A gap is '-'; every other character counts and is compared as it stands (upper and lower case differ), as in kalign.utils.
@@ -76,6 +76,15 @@ def remove_gap_columns_families(ctx, families, threshold=1.0):
         s.close()
 
 
+def pairwise_identity_matrices(ctx, families):
+    """pairwise_identity_matrix of every alignment of the list: float64 [n, n] arrays, all from one launch"""
+    s = _summary(ctx, _families(families))
+    try:
+        return s.identity()
+    finally:
+        s.close()
+
+
 def alignment_stats(ctx, alignment):
     """kalign.utils.alignment_stats: length, n_sequences, gap_fraction, conservation, identity"""
     return alignment_stats_families(ctx, [alignment])[0]
@@ -89,6 +98,12 @@ def consensus_sequence(ctx, alignment, threshold=0.5):
 def remove_gap_columns(ctx, alignment, threshold=1.0):
     """kalign.utils.remove_gap_columns: the columns whose gap fraction is below the threshold"""
     return remove_gap_columns_families(ctx, [alignment], _threshold(threshold))[0]
+
+
+def pairwise_identity_matrix(ctx, alignment):
+    """kalign.utils.pairwise_identity_matrix: the symmetric [n, n] matrix of identities over the columns where both
+    sequences hold a character; 1.0 on the diagonal, 0.0 for a pair that shares no column"""
+    return pairwise_identity_matrices(ctx, [alignment])[0]
 
 
 def trim_range(length, start=None, end=None):
