@@ -727,6 +727,52 @@ int  ka_cmp_fam_score(ka_cmp_fam* h, const uint8_t* test_rows, const int* test_a
                       float* sp_out);
 int  ka_cmp_fam_stats(ka_cmp_fam* h, double* stats_out);
 
+/* ---- where a test alignment agrees with its reference: per residue and per column (ka_cmp.hip, ka_cmp.cpp, ka_cmp_fam.cpp) ----
+ * The score entries above say how good a test alignment is; these say where it is right.  They are the ground truth that the
+ * confidences of the ensemble stage (ka_ens_fam_confidence) predict: per test column the verdict of _column_correctness of
+ * the reference's benchmarks/downstream/calibration.py, per residue the counts behind it.
+ *   Kept from the comparison stage: a residue is an ASCII letter, every other byte a gap; rows are paired by position; the
+ *   checks are ka_cmp_fam_check's.  Residues are numbered flat over the handle as the stage numbers them: sequences in order,
+ *   a sequence's residues in order; T is their number.  The column rule (ka_cmp_set_mask, ka_cmp_fam_set_masks) plays no
+ *   part: every column is reported.
+ *   For residue e = residue ri of sequence i, over the other sequences j of its family, with col[i][ri] the column of the
+ *   residue and res[j][c] the residue of j at column c (or -1):
+ *       pR = resR[j][colR[i][ri]]        pT = resT[j][colT[i][ri]]
+ *   res_counts[3][T]   int32: plane 0 #[pR >= 0], plane 1 #[pT >= 0], plane 2 #[pR >= 0 && pR == pT] -- its aligned partners
+ *                      in the reference, in the test, and in both.  The planes sum to ref_total_aligned_pairs,
+ *                      test_total_aligned_pairs and identical_aligned of the score call.
+ *   test columns       flat over the call, families in order (the sum of the test alnlens), per column: residues int32 (k);
+ *                      common int64 (plane 2 summed over the column's residues); correct uint8: 1 when k <= 1 or all k
+ *                      residues lie in one column of the reference.  correct == (common == k (k - 1)).
+ *   reference columns  flat over the handle (the sum of the reference alnlens): the same three with the sides swapped --
+ *                      correct is TC's verdict per column: over the scored columns with k >= 2 it sums to tc_correct.
+ *   ka_cmp_detail            one test alignment of a ka_cmp handle, as ka_cmp_score takes it.
+ *   ka_cmp_fam_detail        one test alignment per family, as ka_cmp_fam_score takes them.  Every output is optional.  A
+ *                            refused batch launches nothing and leaves the handle usable; the handle scores exactly as before
+ *                            afterwards.  A call is one upload of the rows, one copy back and one host synchronisation; its
+ *                            launches (the test maps, the detailed walk once per LDS class in use, the column pass) do not
+ *                            depend on the number of families.
+ *   ka_cmp_detail_stats, ka_cmp_fam_detail_stats   out5: device ms of the test maps, the detailed walk and the column pass,
+ *                            then the kernel launches and host synchronisations of the last detail call (all 0 before the
+ *                            first, and after a refused one).
+ *   ka_calibration     host only (no context, no GPU): brier_score, expected_calibration_error and calibration_curve of the
+ *                      same file over (predicted, actual) items.  Segment s is the items seg_first[s] .. seg_first[s + 1] - 1;
+ *                      every output has n_seg + 1 slots, the last the pool of all items in order (_aggregate_summary pools
+ *                      its cases so).  Per slot: brier, ece, bin_fraction[n_bins] (NaN for an empty bin), bin_counts[n_bins];
+ *                      each output optional.  The reference's order of operations: serial double sums in item order,
+ *                      b = (int)(p * n_bins) clamped to the last bin; an empty slot gives 0.0, 0.0, NaNs and zeros.  Refused
+ *                      before anything is written, the message naming the item: n_bins < 1, seg_first not ascending from 0,
+ *                      predicted outside [0, 1] or NaN (the reference would index a negative bin), actual above 1.
+ */
+int  ka_cmp_detail(ka_cmp* h, const uint8_t* test_rows, long long row_stride, int alnlen, int* res_counts, int* tcol_residues,
+                   long long* tcol_common, uint8_t* tcol_correct, int* rcol_residues, long long* rcol_common, uint8_t* rcol_correct);
+int  ka_cmp_fam_detail(ka_cmp_fam* h, const uint8_t* test_rows, const int* test_alnlens, int* res_counts, int* tcol_residues,
+                       long long* tcol_common, uint8_t* tcol_correct, int* rcol_residues, long long* rcol_common, uint8_t* rcol_correct);
+int  ka_cmp_detail_stats(ka_cmp* h, double* out5);
+int  ka_cmp_fam_detail_stats(ka_cmp_fam* h, double* out5);
+int  ka_calibration(int n_seg, const long long* seg_first, const double* predicted, const uint8_t* actual, int n_bins, double* brier,
+                    double* ece, double* bin_fraction, long long* bin_counts);
+
 /* ---- the ensemble consensus stage for a batch of families (ka_ens.hip, ka_ens_fam.cpp) ----------------------------------------
  * What ka_ens_create + ka_ens_add_member + ka_ens_score_rows + ka_ens_consensus + ka_ens_confidence return for every family
  * alone -- equal integer sums, doubles from the same expressions, byte-identical rows, bit-identical confidences -- for all

@@ -61,6 +61,7 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_ens_open_table_image", "ka_ens_n_runs", "ka_ens_table_stats", "ka_poar_check_image", "ka_ens_merge", "ka_ens_select", "ka_cmp_create", "ka_cmp_destroy", "ka_cmp_set_mask", "ka_cmp_score",
            "ka_cmp_score_batch", "ka_cmp_stats",
            "ka_cmp_fam_check", "ka_cmp_fam_create", "ka_cmp_fam_destroy", "ka_cmp_fam_set_masks", "ka_cmp_fam_score", "ka_cmp_fam_stats",
+           "ka_cmp_detail", "ka_cmp_fam_detail", "ka_cmp_detail_stats", "ka_cmp_fam_detail_stats", "ka_calibration",
            "ka_ens_fam_check", "ka_ens_fam_create", "ka_ens_fam_destroy", "ka_ens_fam_add_member", "ka_ens_fam_score_members", "ka_ens_fam_score",
            "ka_ens_fam_consensus", "ka_ens_fam_rows_size", "ka_ens_fam_rows", "ka_ens_fam_confidence", "ka_ens_fam_stats",
            "ka_debug_ens_fam_consensus_host",
@@ -240,6 +241,11 @@ def load_library():
     L.ka_cmp_fam_set_masks.argtypes = [vp, vp, vp, vp]
     L.ka_cmp_fam_score.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ka_cmp_fam_stats.argtypes = [vp, vp]
+    L.ka_cmp_detail.argtypes = [vp, vp, C.c_longlong, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.ka_cmp_fam_detail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ka_cmp_detail_stats.argtypes = [vp, vp]
+    L.ka_cmp_fam_detail_stats.argtypes = [vp, vp]
+    L.ka_calibration.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.ka_ens_fam_check.argtypes = [C.c_int, vp, vp, vp, vp]
     L.ka_ens_fam_create.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.POINTER(vp)]
     L.ka_ens_fam_destroy.argtypes = [vp]
@@ -1165,6 +1171,36 @@ def _cmp_result(counts, scores, sp):
     return d
 
 
+CMP_DETAIL_STATS = ["maps_ms", "walk_ms", "columns_ms", "launches", "syncs"]
+
+
+def _detail_buffers(T, n_tcols, n_rcols):
+    """the seven outputs of ka_cmp_detail / ka_cmp_fam_detail, in the order the entries take them"""
+    return [np.zeros((3, T), np.int32), np.zeros(n_tcols, np.int32), np.zeros(n_tcols, np.int64), np.zeros(n_tcols, np.uint8),
+            np.zeros(n_rcols, np.int32), np.zeros(n_rcols, np.int64), np.zeros(n_rcols, np.uint8)]
+
+
+def _detail_result(bufs, res_first, tcol_first, rcol_first):
+    """the outputs split per family: res [n_residues, 3] (aligned partners in the reference, in the test, in both), and
+    test_columns / ref_columns as dicts of residues (k), common and correct"""
+    planes, tk, tc, tf, rk, rc, rf = bufs
+    out = []
+    for f in range(len(res_first) - 1):
+        t0, t1, r0, r1 = tcol_first[f], tcol_first[f + 1], rcol_first[f], rcol_first[f + 1]
+        out.append(dict(res=np.ascontiguousarray(planes[:, res_first[f]:res_first[f + 1]].T),
+                        test_columns=dict(residues=tk[t0:t1].copy(), common=tc[t0:t1].copy(), correct=tf[t0:t1].copy()),
+                        ref_columns=dict(residues=rk[r0:r1].copy(), common=rc[r0:r1].copy(), correct=rf[r0:r1].copy())))
+    return out
+
+
+def _detail_stats(L, fn, ctx, h):
+    st = np.zeros(5, np.float64)
+    ctx._chk(getattr(L, fn)(h, _ptr(st)))
+    d = dict(zip(CMP_DETAIL_STATS, st.tolist()))
+    d["launches"], d["syncs"] = int(d["launches"]), int(d["syncs"])
+    return d
+
+
 class Comparer(_CtxChild):
     """A reference alignment on the device (ka_cmp) that test alignments of the same sequences are scored against, as
     kalign_msa_compare (sp) and kalign_msa_compare_detailed / _with_mask (recall, precision, f1, tc) score them.  Rows
@@ -1229,6 +1265,24 @@ class Comparer(_CtxChild):
         self.ctx._chk(self.L.ka_cmp_stats(self.h, _ptr(st)))
         return dict(zip(["ref_maps_ms", "maps_ms", "walk_ms", "tc_ms"], st.tolist()))
 
+    def detail(self, test_rows):
+        """where the test alignment agrees with the reference (ka_cmp_detail): dict(res=[n_residues, 3] int32 -- a
+        residue's aligned partners in the reference, in the test and in both, residues numbered sequence by sequence --,
+        test_columns, ref_columns = dicts of residues (k), common and correct per column).  test_columns["correct"] is
+        _column_correctness of the reference's calibration benchmark; the column rule of score() plays no part."""
+        if not self.h:
+            raise KalignAmdError("the comparer is closed")
+        a, w = self._test_array(test_rows)
+        T = int(self.lens.sum())
+        bufs = _detail_buffers(T, w, self.width)
+        self.ctx._chk(self.L.ka_cmp_detail(self.h, _ptr(a), w, w, *[_ptr(b) for b in bufs]))
+        return _detail_result(bufs, [0, T], [0, w], [0, self.width])[0]
+
+    def detail_stats(self):
+        """ka_cmp_detail_stats: device ms of the test maps, the detailed walk and the column pass, then the launches and
+        host synchronisations of the last detail() call"""
+        return _detail_stats(self.L, "ka_cmp_detail_stats", self.ctx, self.h)
+
 
 def _cmp_create(self, ref_rows):
     """ka_cmp_create: a Comparer holding ref_rows (one row per sequence) on this context's device"""
@@ -1285,12 +1339,7 @@ class FamilyComparer(_CtxChild):
         (kalign_msa_compare_with_mask).  Returns one Comparer.score dict per family."""
         if not self.h:
             raise KalignAmdError("the comparer is closed")
-        tests = [list(f) for f in tests]
-        if [len(f) for f in tests] != self.sizes:
-            for f, (t, n) in enumerate(zip(tests, self.sizes)):
-                if len(t) != n:
-                    raise KalignAmdError("family %d: the test alignment has %d rows, the reference %d" % (f, len(t), n))
-            raise KalignAmdError("%d test alignments for %d families" % (len(tests), len(self.sizes)))
+        tests = self._tests(tests)
         self._set_masks(max_gap_frac, column_masks)
         rows, widths = pack_families(tests)
         F = len(self.sizes)
@@ -1305,6 +1354,35 @@ class FamilyComparer(_CtxChild):
         st = np.zeros(4, np.float64)
         self.ctx._chk(self.L.ka_cmp_fam_stats(self.h, _ptr(st)))
         return dict(zip(["ref_maps_ms", "maps_ms", "walk_ms", "tc_ms"], st.tolist()))
+
+    def _tests(self, tests):
+        tests = [list(f) for f in tests]
+        if [len(f) for f in tests] != self.sizes:
+            for f, (t, n) in enumerate(zip(tests, self.sizes)):
+                if len(t) != n:
+                    raise KalignAmdError("family %d: the test alignment has %d rows, the reference %d" % (f, len(t), n))
+            raise KalignAmdError("%d test alignments for %d families" % (len(tests), len(self.sizes)))
+        return tests
+
+    def detail(self, tests, want=None):
+        """one test alignment per family (ka_cmp_fam_detail): per family what Comparer(ref).detail(test) returns for it
+        alone, from launches that do not grow with the batch.  want: None, or the outputs asked of the device, a subset of
+        range(7) in the entry's order (the others stay zero) -- for the tests of the optional pointers."""
+        if not self.h:
+            raise KalignAmdError("the comparer is closed")
+        rows, widths = pack_families(self._tests(tests))
+        seq_first = np.asarray(self.first, np.int64)
+        res_first = np.concatenate([[0], np.cumsum(self.lens, dtype=np.int64)])[seq_first]
+        tcol_first = np.concatenate([[0], np.cumsum(widths, dtype=np.int64)])
+        rcol_first = np.concatenate([[0], np.cumsum(self.widths, dtype=np.int64)])
+        bufs = _detail_buffers(int(res_first[-1]), int(tcol_first[-1]), int(rcol_first[-1]))
+        ptrs = [_ptr(b) if want is None or k in want else None for k, b in enumerate(bufs)]
+        self.ctx._chk(self.L.ka_cmp_fam_detail(self.h, _ptr(rows if len(rows) else np.zeros(1, np.uint8)), _ptr(widths), *ptrs))
+        return _detail_result(bufs, res_first, tcol_first, rcol_first)
+
+    def detail_stats(self):
+        """ka_cmp_fam_detail_stats: as Comparer.detail_stats, over the whole batch"""
+        return _detail_stats(self.L, "ka_cmp_fam_detail_stats", self.ctx, self.h)
 
 
 def _cmp_fam_create(self, refs):

@@ -82,3 +82,91 @@ def compare_files(ctx, ref_path, test_path, max_gap_frac=0.2, column_mask=None):
     rn, rs = read_fasta(ref_path)
     tn, ts = read_fasta(test_path)
     return compare(ctx, list(zip(rn, rs)), list(zip(tn, ts)), max_gap_frac=max_gap_frac, column_mask=column_mask)
+
+
+# ---- where a test alignment is right: column correctness and the calibration of confidences ----
+# (_column_correctness, brier_score, expected_calibration_error, calibration_curve of the reference's
+# benchmarks/downstream/calibration.py; the flags come from the device, the metrics are host arithmetic in the library)
+def _paired_families(refs, tests):
+    refs, tests = list(refs), list(tests)
+    if len(refs) != len(tests):
+        raise KalignAmdError("%d reference alignments, %d test alignments" % (len(refs), len(tests)))
+    r, t = [], []
+    for f, (a, b) in enumerate(zip(refs, tests)):
+        try:
+            ra, tb = pair_rows(a, b)
+        except KalignAmdError as e:
+            raise KalignAmdError("family %d: %s" % (f, e)) from None
+        r.append(ra)
+        t.append(tb)
+    return r, t
+
+
+def column_correctness_families(ctx, refs, tests):
+    """_column_correctness for a batch of families in one device pass (FamilyComparer.detail): per family the uint8 flag
+    of every test column -- 1 when its residues (none or one: 1) all lie in one column of the family's reference.  refs /
+    tests as compare_families() takes them; a column's flag does not depend on the order of the rows."""
+    r, t = _paired_families(refs, tests)
+    cmp = ctx.family_comparer(r)
+    try:
+        return [d["test_columns"]["correct"] for d in cmp.detail(t)]
+    finally:
+        cmp.close()
+
+
+def column_correctness(ctx, ref, test):
+    """_column_correctness of one test alignment against its reference (true) alignment: one uint8 flag per test column"""
+    return column_correctness_families(ctx, [ref], [test])[0]
+
+
+def calibration(predicted, actual, n_bins=10, segments=None):
+    """brier_score, expected_calibration_error and calibration_curve of (predicted confidence, actual 0 / 1) items, with
+    the reference's arithmetic (ka_calibration; host only).  Returns a dict with the reference's keys: brier_score, ece,
+    bin_centers, fraction_correct (NaN for an empty bin), bin_counts.  With segments (the number of items of each segment,
+    in order) returns (one such dict per segment, the dict of the pool of all items in order)."""
+    import ctypes as C
+
+    import numpy as np
+
+    from .api import _ptr, load_library
+    L = load_library()
+    p = np.ascontiguousarray(predicted, np.float64).reshape(-1)
+    a = np.asarray(actual).reshape(-1)
+    if len(a) != len(p):
+        raise KalignAmdError("%d predicted values, %d actual values" % (len(p), len(a)))
+    if len(a) and (a != (a != 0)).any():
+        k = int(np.flatnonzero(a != (a != 0))[0])
+        raise KalignAmdError("ka_calibration: item %d: actual %s is neither 0 nor 1" % (k, a[k]))
+    a = np.ascontiguousarray(a, np.uint8)
+    sizes = [len(p)] if segments is None else [int(n) for n in segments]
+    if any(n < 0 for n in sizes) or sum(sizes) != len(p):
+        raise KalignAmdError("the segments hold %d items, %d are given" % (sum(sizes), len(p)))
+    first = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
+    S = len(sizes) + 1
+    nb = max(int(n_bins), 0)
+    brier, ece = np.zeros(S, np.float64), np.zeros(S, np.float64)
+    frac, counts = np.zeros((S, nb), np.float64), np.zeros((S, nb), np.int64)
+    if L.ka_calibration(len(sizes), _ptr(first), _ptr(p), _ptr(a), C.c_int(int(n_bins)), _ptr(brier), _ptr(ece), _ptr(frac), _ptr(counts)) != 0:
+        raise KalignAmdError(L.ka_last_error().decode())
+    width = 1.0 / n_bins
+    centers = [(b + 0.5) * width for b in range(n_bins)]
+    out = [dict(brier_score=float(brier[s]), ece=float(ece[s]), bin_centers=list(centers), fraction_correct=frac[s].tolist(),
+                bin_counts=[int(x) for x in counts[s]]) for s in range(S)]
+    return out[-1] if segments is None else (out[:-1], out[-1])
+
+
+def calibrate_families(ctx, refs, tests, column_confidences, n_bins=10):
+    """the calibration of per-column confidences (FamilyEnsemble.confidence's column values) against the column
+    correctness of the test alignments: column_confidences[f] one value per test column of family f.  Returns
+    dict(correct=the flags per family, families=calibration() per family, pooled=calibration() of all columns, families in
+    order)."""
+    import numpy as np
+    flags = column_correctness_families(ctx, refs, tests)
+    conf = [np.asarray(c, np.float64).reshape(-1) for c in column_confidences]
+    if len(conf) != len(flags):
+        raise KalignAmdError("%d confidence arrays for %d families" % (len(conf), len(flags)))
+    for f, (c, g) in enumerate(zip(conf, flags)):
+        if len(c) != len(g):
+            raise KalignAmdError("family %d: %d confidences for %d test columns" % (f, len(c), len(g)))
+    per, pooled = calibration(np.concatenate(conf) if conf else [], np.concatenate(flags) if flags else [], n_bins, [len(g) for g in flags])
+    return dict(correct=flags, families=per, pooled=pooled)

@@ -6,7 +6,9 @@
 // once -- and scores a call's jobs (ka_cmp.h: one test alignment against one reference) in one sequence: the rows
 // uploaded, the test maps, the pair walk (one launch per LDS class in use), the TC pass, every job's eight sums back in
 // one copy behind one synchronisation (ka_cmp.hip).  The device returns exact integer counts; the final doubles are
-// computed on the host with the reference's expressions, in its order (ka_cmp_finish, ka_cmp.h).
+// computed on the host with the reference's expressions, in its order (ka_cmp_finish, ka_cmp.h).  A detail call (one
+// job per reference) takes the same first steps -- begin() and walk() are shared -- with the walk in its detailed form,
+// then the column pass, and brings the counts of every residue and the records of every column back in one copy.
 //
 // A handle's front checks its arguments on the host before anything is launched and says how its rows are laid out; a
 // refused call launches nothing and leaves the handle usable.
@@ -14,6 +16,8 @@
 // Unlike the reference, the two alignments must hold the same sequences: numseq rows each, row s with lens[s] letters
 // (the reference reads out of bounds otherwise).  Two sequences at least.
 #include "ka_cmp_core.h"
+
+#include <string.h>
 
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
 
@@ -54,7 +58,7 @@ KaCmpCore::~KaCmpCore()
                 if (e) (void)hipEventDestroy(e);
         dRefs.release(); dJobs.release(); dRefFirst.release(); dJobFirst.release(); dOffs.release(); dLens.release(); dSeqOf.release();
         dColR.release(); dColT.release(); dColCnt.release(); dMasks.release(); dResR.release(); dResT.release(); dRows.release();
-        dScored.release(); dFrac.release(); dMaskOff.release(); dSums.release();
+        dScored.release(); dFrac.release(); dMaskOff.release(); dSums.release(); dDet.release();
 }
 
 int KaCmpCore::attach(ka_ctx* ctx) { return ka_ctx_device_stream(ctx, &device, &stream); }
@@ -147,20 +151,20 @@ int KaCmpCore::set_rule(const char* who, const float* frac, const int* masks, co
         return KA_OK;
 }
 
-int KaCmpCore::score(const char* who, const char* item, int nJob, const int* refOf, const int* widths, int pad, const KaCmpUpload& upload,
-                     long long* counts, double* scores, float* sp)
+int KaCmpCore::begin(const char* who, const char* item, int nJob, const int* refOf, const int* widths, int pad, const KaCmpUpload& upload, Call& c,
+                     int* launches)
 {
         const std::string me(who);
         // every job's test side, tile geometry and LDS class, and the ascending tables of what the call numbers: test
-        // rows, job columns and the tiles of every LDS class
-        enum { ROWS = 0, COLS = 1, TILES = 2, TABLES = TILES + KA_CMP_CLASSES };
-        static const char* const what[3] = { "rows", "columns", "tiles" };
-        std::vector<KaCmpJob> jobs(nJob);
-        std::vector<int> first((size_t)TABLES * (nJob + 1), 0);
-        size_t classLds[KA_CMP_CLASSES] = {};
+        // rows, job columns, test columns and the tiles of every LDS class
+        static const char* const what[4] = { "rows", "columns", "test columns", "tiles" };
+        c.nJob = nJob;
+        c.jobs.assign(nJob, KaCmpJob{});
+        c.first.assign((size_t)TABLES * (nJob + 1), 0);
+        std::vector<int>& first = c.first;
         long long rowOff = 0, resOff = 0, colOff = 0;
         for (int k = 0; k < nJob; k++) {
-                KaCmpJob& d = jobs[k] = refs[refOf ? refOf[k] : k];
+                KaCmpJob& d = c.jobs[k] = refs[refOf ? refOf[k] : k];
                 d.t.W = widths[k]; d.t.Wp = ka_cmp_pad(widths[k]); d.t.stride = widths[k] + pad; d.t.rowOff = rowOff; d.t.resOff = resOff;
                 d.colOff = colOff - d.firstRes;
                 const size_t lds = walk_lds(d.N, d.r.Wp, d.t.Wp, &d.TJ);
@@ -169,54 +173,108 @@ int KaCmpCore::score(const char* who, const char* item, int nJob, const int* ref
                                     " together exceed the LDS of one CU (one row of each is staged)");
                 d.nTJ = (d.N + d.TJ - 1) / d.TJ;
                 const int nTI = (d.N + KA_CMP_TI - 1) / KA_CMP_TI, cls = lds_class(lds);
-                classLds[cls] = std::max(classLds[cls], lds);
-                for (int c = 0; c < TABLES; c++) {
-                        const long long n = c == ROWS ? d.N : c == COLS ? d.r.W : c - TILES == cls ? (long long)nTI * d.nTJ : 0;
-                        const long long next = first[(size_t)c * (nJob + 1) + k] + n;
-                        if (next > INT32_MAX) return fail(me + ": more than 2^31 - 1 " + what[std::min<int>(c, TILES)] + " in the batch");
-                        first[(size_t)c * (nJob + 1) + k + 1] = (int)next;
+                c.classLds[cls] = std::max(c.classLds[cls], lds);
+                for (int t = 0; t < TABLES; t++) {
+                        const long long n = t == ROWS ? d.N : t == COLS ? d.r.W : t == TCOLS ? d.t.W : t - TILES == cls ? (long long)nTI * d.nTJ : 0;
+                        const long long next = first[(size_t)t * (nJob + 1) + k] + n;
+                        if (next > INT32_MAX) return fail(me + ": more than 2^31 - 1 " + what[std::min<int>(t, TILES)] + " in the batch");
+                        first[(size_t)t * (nJob + 1) + k + 1] = (int)next;
                 }
                 rowOff += d.N * d.t.stride;
                 resOff += (long long)d.N * d.t.Wp;
                 colOff += offs[d.firstSeq + d.N] - d.firstRes;
         }
-        std::vector<unsigned long long> sums((size_t)nJob * KA_CMP_SUMS);
         HIPCHK(hipSetDevice(device));
         if (dRows.alloc((size_t)rowOff) || dResT.alloc((size_t)resOff) || dColT.alloc((size_t)std::max<long long>(colOff, 1)) || dJobs.alloc(nJob) ||
-            dJobFirst.alloc(first.size()) || dSums.alloc(sums.size()))
+            dJobFirst.alloc(first.size()) || dSums.alloc((size_t)nJob * KA_CMP_SUMS))
                 return fail(me + ": out of device memory");
-        HIPCHK(hipMemcpyAsync(dJobs.p, jobs.data(), sizeof(KaCmpJob) * nJob, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(dJobs.p, c.jobs.data(), sizeof(KaCmpJob) * nJob, hipMemcpyHostToDevice, stream));
         HIPCHK(hipMemcpyAsync(dJobFirst.p, first.data(), sizeof(int) * first.size(), hipMemcpyHostToDevice, stream));
         if (upload(dRows.p, stream)) return KA_FAIL;
-        HIPCHK(hipMemsetAsync(dSums.p, 0, sizeof(unsigned long long) * sums.size(), stream));
+        HIPCHK(hipMemsetAsync(dSums.p, 0, sizeof(unsigned long long) * (size_t)nJob * KA_CMP_SUMS, stream));
         HIPCHK(hipEventRecord(ev[0], stream));
-        KaCmpTab a = tab();
+        KaCmpTab& a = c.a = tab();
         a.nJob = nJob; a.jobs = dJobs.p;
-        a.jobRow = dJobFirst.p + (size_t)ROWS * (nJob + 1); a.jobRows = first[(size_t)ROWS * (nJob + 1) + nJob];
-        a.jobCol = dJobFirst.p + (size_t)COLS * (nJob + 1); a.jobCols = first[(size_t)COLS * (nJob + 1) + nJob];
+        a.jobRow = dJobFirst.p + (size_t)ROWS * (nJob + 1); a.jobRows = c.last(ROWS);
+        a.jobCol = dJobFirst.p + (size_t)COLS * (nJob + 1); a.jobCols = c.last(COLS);
+        a.tcolFirst = dJobFirst.p + (size_t)TCOLS * (nJob + 1); a.tCols = c.last(TCOLS);
         ka_cmp_run_maps(a, 1, stream);
+        ++*launches;
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev[1], stream));
-        for (int c = 0; c < KA_CMP_CLASSES; c++) {
-                const size_t at0 = (size_t)(TILES + c) * (nJob + 1);
-                if (!first[at0 + nJob]) continue;
-                if (ka_cmp_run_walk(a, dJobFirst.p + at0, first[at0 + nJob], classLds[c], stream))
-                        return fail(me + ": the walk's LDS (" + std::to_string(classLds[c]) + " bytes) was refused");
+        return KA_OK;
+}
+
+int KaCmpCore::walk(const char* who, const Call& c, bool detailed, int* launches)
+{
+        for (int cls = 0; cls < KA_CMP_CLASSES; cls++) {
+                const size_t at0 = (size_t)(TILES + cls) * (c.nJob + 1);
+                if (!c.last(TILES + cls)) continue;
+                if (ka_cmp_run_walk(c.a, dJobFirst.p + at0, c.last(TILES + cls), c.classLds[cls], detailed, stream))
+                        return fail(std::string(who) + ": the walk's LDS (" + std::to_string(c.classLds[cls]) + " bytes) was refused");
+                ++*launches;
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev[2], stream));
-        ka_cmp_run_tc(a, stream);
+        return KA_OK;
+}
+
+int KaCmpCore::score(const char* who, const char* item, int nJob, const int* refOf, const int* widths, int pad, const KaCmpUpload& upload,
+                     long long* counts, double* scores, float* sp)
+{
+        Call c;
+        int launches = 0;
+        if (begin(who, item, nJob, refOf, widths, pad, upload, c, &launches) || walk(who, c, false, &launches)) return KA_FAIL;
+        std::vector<unsigned long long> sums((size_t)nJob * KA_CMP_SUMS);
+        ka_cmp_run_tc(c.a, stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev[3], stream));
         HIPCHK(hipMemcpyAsync(sums.data(), dSums.p, sizeof(unsigned long long) * sums.size(), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         st[1] += ms(0, 1); st[2] += ms(1, 2); st[3] += ms(2, 3);
         for (int k = 0; k < nJob; k++) {
-                const KaCmpJob& d = jobs[k];
+                const KaCmpJob& d = c.jobs[k];
                 const long long* w = (const long long*)&sums[(size_t)k * KA_CMP_SUMS];
                 ka_cmp_finish(w, w[KA_CMP_WALK], w[KA_CMP_WALK + 1], d.N, offs[d.firstSeq + d.N] - d.firstRes,
                               counts ? counts + (size_t)k * 12 : nullptr, scores ? scores + (size_t)k * 5 : nullptr, sp ? sp + k : nullptr);
         }
+        return KA_OK;
+}
+
+// A detail call's outputs are one block on the device and come back in one copy: the column records' 64-bit sums first
+// (8-byte aligned), then the three residue planes (the part the walk adds to: zeroed), the columns' residues and flags
+int KaCmpCore::detail(const char* who, const char* item, const int* widths, int pad, const KaCmpUpload& upload, int* resCounts, int* tcolRes,
+                      long long* tcolCommon, uint8_t* tcolCorrect, int* rcolRes, long long* rcolCommon, uint8_t* rcolCorrect)
+{
+        Call c;
+        int launches = 0;
+        if (begin(who, item, (int)refs.size(), nullptr, widths, pad, upload, c, &launches)) return KA_FAIL;
+        const size_t nCol = (size_t)c.a.tCols + (size_t)cols, nT = (size_t)T;
+        const size_t oPlanes = nCol * sizeof(long long), oRes = oPlanes + 3 * nT * sizeof(int), oFlag = oRes + nCol * sizeof(int), bytes = oFlag + nCol;
+        if (dDet.alloc(bytes)) return fail(std::string(who) + ": out of device memory");
+        HIPCHK(hipMemsetAsync(dDet.p + oPlanes, 0, 3 * nT * sizeof(int), stream));
+        c.a.T = T;
+        c.a.detColCommon = (long long*)dDet.p;
+        c.a.detRes = (int*)(dDet.p + oPlanes);
+        c.a.detColRes = (int*)(dDet.p + oRes);
+        c.a.detColCorrect = dDet.p + oFlag;
+        if (walk(who, c, true, &launches)) return KA_FAIL;
+        ka_cmp_run_cols(c.a, stream);
+        launches += nCol > 0;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev[3], stream));
+        std::vector<uint8_t> out(bytes);
+        HIPCHK(hipMemcpyAsync(out.data(), dDet.p, bytes, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        dst[0] = ms(0, 1); dst[1] = ms(1, 2); dst[2] = ms(2, 3); dst[3] = launches; dst[4] = 1;
+        const size_t nt = (size_t)c.a.tCols, nr = (size_t)cols;
+        if (resCounts) memcpy(resCounts, out.data() + oPlanes, 3 * nT * sizeof(int));
+        if (tcolCommon) memcpy(tcolCommon, out.data(), nt * sizeof(long long));
+        if (rcolCommon) memcpy(rcolCommon, out.data() + nt * sizeof(long long), nr * sizeof(long long));
+        if (tcolRes) memcpy(tcolRes, out.data() + oRes, nt * sizeof(int));
+        if (rcolRes) memcpy(rcolRes, out.data() + oRes + nt * sizeof(int), nr * sizeof(int));
+        if (tcolCorrect) memcpy(tcolCorrect, out.data() + oFlag, nt);
+        if (rcolCorrect) memcpy(rcolCorrect, out.data() + oFlag + nt, nr);
         return KA_OK;
 }
 
@@ -297,5 +355,24 @@ extern "C" int ka_cmp_stats(ka_cmp* h, double* stats_out)
 {
         if (!h) return fail("ka_cmp_stats: bad arguments");
         if (stats_out) std::copy_n(h->core.st, KA_CMP_STATS, stats_out);
+        return KA_OK;
+}
+
+extern "C" int ka_cmp_detail(ka_cmp* h, const uint8_t* test_rows, long long row_stride, int alnlen, int* res_counts, int* tcol_residues,
+                             long long* tcol_common, uint8_t* tcol_correct, int* rcol_residues, long long* rcol_common, uint8_t* rcol_correct)
+{
+        if (!h) return fail("ka_cmp_detail: bad arguments");
+        std::fill_n(h->core.dst, KA_CMP_DETAIL_STATS, 0.0);
+        if (ka_msa_check_rows("ka_cmp_detail", h->q, test_rows, row_stride, alnlen)) return KA_FAIL;
+        const KaSeqSet& q = h->q;
+        return h->core.detail("ka_cmp_detail", nullptr, &alnlen, 0, [&](uint8_t* dst, hipStream_t s) {
+                return ka_msa_upload_rows(q, dst, test_rows, row_stride, alnlen, s);
+        }, res_counts, tcol_residues, tcol_common, tcol_correct, rcol_residues, rcol_common, rcol_correct);
+}
+
+extern "C" int ka_cmp_detail_stats(ka_cmp* h, double* out5)
+{
+        if (!h) return fail("ka_cmp_detail_stats: bad arguments");
+        if (out5) std::copy_n(h->core.dst, KA_CMP_DETAIL_STATS, out5);
         return KA_OK;
 }

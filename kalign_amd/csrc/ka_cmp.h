@@ -8,13 +8,14 @@
 #define KA_CMP_WALK 6              // the walk's counters per job: see the enum below
 #define KA_CMP_SUMS 8              // a job's sums: the walk's six counters, tc_correct, tc_total
 #define KA_CMP_STATS 4             // ka_cmp_stats: see include/kalign_amd.h
+#define KA_CMP_DETAIL_STATS 5      // ka_cmp_detail_stats: see include/kalign_amd.h
 #define KA_CMP_TI 16               // sequences i per tile of the pair walk
 #define KA_CMP_TJ 32               // at most this many sequences j per tile (fewer when their rows do not fit the LDS budget)
 #define KA_CMP_LDS 65536           // LDS budget of a walk workgroup for the staged rows (more only when one j row needs it)
 #define KA_CMP_MAX_LDS 163840      // gfx950: LDS of one CU
 #define KA_CMP_WALK_WGS 2048       // workgroups of a walk launch at most (8 per CU): more tiles are strided over
 #define KA_CMP_CLASSES 4           // walk launches by LDS need: up to 16, 32 and 64 KiB (KA_CMP_LDS), and what is larger
-#define KA_CMP_TCCHUNK 8           // consecutive job columns per wave of the TC pass at most
+#define KA_CMP_TCCHUNK 8           // consecutive job columns per wave of the TC pass and of the column pass at most
 
 // res maps are stored with a row stride padded to 8 entries (16 bytes): a tile's rows copy as whole uint4s
 static inline int ka_cmp_pad(int w) { return (w + 7) & ~7; }
@@ -71,6 +72,14 @@ struct KaCmpTab {
         const float* frac;                     // [nRef] max_gap_frac
         const int* masks; const long long* maskOff;   // reference f's mask at masks + maskOff[f], or maskOff[f] < 0
         unsigned long long* sums;              // [nJob][KA_CMP_SUMS]
+        // ---- a detail call (one job per reference, job k against reference k; unset in a score call) ----
+        int T, tCols;                          // residues of the references; test columns of the call
+        const int* tcolFirst;                  // [nJob + 1] first test column of a job
+        int* detRes;                           // [3][T] per flat residue: the walk's REF_ALIGNED, TEST_ALIGNED, IDENT_ALIGNED
+        // the column records: the call's tCols test columns, then the references' cols columns
+        int* detColRes;                        // residues of the column (k)
+        long long* detColCommon;               // plane 2 of detRes summed over the column's residues
+        uint8_t* detColCorrect;                // k <= 1, or all k residues in one column of the other alignment
 };
 
 // ka_cmp.hip
@@ -78,8 +87,11 @@ void ka_cmp_run_maps(const KaCmpTab& a, int test, hipStream_t s);     // the ref
 void ka_cmp_run_col_count(const KaCmpTab& a, hipStream_t s);
 void ka_cmp_run_mask(const KaCmpTab& a, hipStream_t s);
 // the tiles first[k] .. first[k + 1] - 1 (device, [nJob + 1]) of the jobs of one LDS class
-int ka_cmp_run_walk(const KaCmpTab& a, const int* first, int nTiles, size_t lds, hipStream_t s);
+// detail: every lane also adds its residue's three counts to the planes of a.detRes (zeroed by the caller)
+int ka_cmp_run_walk(const KaCmpTab& a, const int* first, int nTiles, size_t lds, bool detail, hipStream_t s);
 void ka_cmp_run_tc(const KaCmpTab& a, hipStream_t s);
+// the column records of both sides, after the detailed walk
+void ka_cmp_run_cols(const KaCmpTab& a, hipStream_t s);
 
 // the doubles of one scored alignment from its exact counts, with the reference's expressions in its order: w = the walk's
 // six sums, N sequences with T residues in all.  counts[12], scores[5] and sp (each optional) as ka_cmp_score hands them out.

@@ -21,6 +21,10 @@
 //                  job's sums -- when the job changes and at the end
 //   cmp_tc         a wave per chunk of consecutive job columns: a scored reference column with two residues or more -- do
 //                  they all sit in one test column?  Its counts are handed over in the same way
+//   cmp_walk_detail  the walk's body once more (cmp_walk_body<true>): every lane also adds its residue's ra / ta / ia to the
+//                  three planes of detRes -- the counts behind a per-residue ground truth (ka_cmp_fam_detail)
+//   cmp_cols       a wave per chunk of consecutive test columns or reference columns: the residues of the column, the sum
+//                  of their plane-2 counts, and whether they all sit in one column of the other alignment
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <algorithm>
@@ -75,7 +79,9 @@ __global__ void cmp_mask(KaCmpTab a)
         a.scored[c] = (uint8_t)v;
 }
 
-__global__ __launch_bounds__(CMP_THREADS) void cmp_walk(KaCmpTab a, const int* first, int nTiles)
+// the walk's body in its two forms: DETAIL false is the score call's, DETAIL true also hands out every residue's counts
+template <bool DETAIL>
+__device__ __forceinline__ void cmp_walk_body(const KaCmpTab& a, const int* first, int nTiles)
 {
         extern __shared__ uint4 cmp_lds[];
         __shared__ long long wsum[CMP_WAVES][KA_CMP_WALK];
@@ -140,6 +146,13 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_walk(KaCmpTab a, const int* f
                         // both (pR == pT == ri)
                         const int self = (unsigned)(a.seqOf[e] - j0) < (unsigned)nj;
                         ra -= self; ta -= self; ia -= self;
+                        if (DETAIL) {
+                                // the residue's counts of this j-tile: nTJ workgroups add to one entry, a wave's lanes to
+                                // consecutive ones (256 contiguous bytes per plane); integer adds, so no order shows
+                                atomicAdd(a.detRes + e, ra);
+                                atomicAdd(a.detRes + (size_t)a.T + e, ta);
+                                atomicAdd(a.detRes + 2 * (size_t)a.T + e, ia);
+                        }
                         acc[KA_CMP_REF_ALIGNED] += ra;
                         acc[KA_CMP_TEST_ALIGNED] += ta;
                         acc[KA_CMP_IDENT_ALIGNED] += ia;
@@ -151,6 +164,16 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_walk(KaCmpTab a, const int* f
 #pragma unroll
                 for (int q = 0; q < KA_CMP_WALK; q++) carry[q] += acc[q];
         }
+}
+
+__global__ __launch_bounds__(CMP_THREADS) void cmp_walk(KaCmpTab a, const int* first, int nTiles)
+{
+        cmp_walk_body<false>(a, first, nTiles);
+}
+
+__global__ __launch_bounds__(CMP_THREADS) void cmp_walk_detail(KaCmpTab a, const int* first, int nTiles)
+{
+        cmp_walk_body<true>(a, first, nTiles);
 }
 
 // TC (compare_with_mask_helper): a scored reference column with >= 2 residues counts; it is correct when every one of
@@ -205,6 +228,65 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_tc(KaCmpTab a, int chunk)
         }
 }
 
+// The column records of a detail call, both sides in one launch.  Side 0: the call's test columns, each against its
+// reference -- correct when its residues share one reference column (_column_correctness of the reference's calibration
+// benchmark).  Side 1: the references' columns against the tests -- TC's verdict, here for every column.  A wave takes
+// `chunk` consecutive columns of one side (waves 0 .. nW0 - 1 serve side 0) and carries the job across them as cmp_tc
+// does.  `correct` comes from the columns, `common` from the detailed walk's plane 2: two routes to one fact
+// (correct == (common == k (k - 1))).
+__global__ __launch_bounds__(CMP_THREADS) void cmp_cols(KaCmpTab a, int chunk, int nW0)
+{
+        const int lane = threadIdx.x & 63;
+        const long long w = (long long)blockIdx.x * CMP_WAVES + (threadIdx.x >> 6);
+        const int side = w >= nW0;
+        const int* first = side ? a.jobCol : a.tcolFirst;
+        const int n = side ? a.jobCols : a.tCols;
+        const long long c0 = (w - (side ? nW0 : 0)) * chunk;
+        if (c0 >= n) return;
+        const int c1 = (int)min((long long)n, c0 + chunk);
+        const long long out0 = side ? a.tCols : 0;               // the reference columns' records follow the test columns'
+        const int* plane2 = a.detRes + 2 * (size_t)a.T;
+        int f = ka_fam_find(first, a.nJob, (int)c0);
+        KaCmpJob d = a.jobs[f];                                  // (by value: its fields stay in registers over the columns)
+        int cf = first[f], cn = first[f + 1];                    // the job's columns of this side: cf .. cn - 1
+        for (int c = (int)c0; c < c1; c++) {
+                if (c >= cn) {
+                        while (c >= first[f + 1]) f++;           // (c < n = first[nJob]: f stays below nJob)
+                        d = a.jobs[f];
+                        cf = first[f]; cn = first[f + 1];
+                }
+                const KaCmpSide& own = side ? d.r : d.t;
+                const int16_t* res = (side ? a.resR : a.resT) + own.resOff + (c - cf);
+                const int* other = side ? a.colT + d.colOff : a.colR;    // a flat residue's column in the other alignment
+                const int* offs = a.offs + d.firstSeq;
+                int lo = INT_MAX, hi = INT_MIN;
+                long long k = 0, common = 0;
+                for (int s = lane; s < d.N; s += 64) {
+                        const int r = res[(long long)s * own.Wp];
+                        if (r >= 0) {
+                                const int e = offs[s] + r;
+                                const int t = other[e];
+                                lo = min(lo, t);
+                                hi = max(hi, t);
+                                k++;
+                                common += plane2[e];
+                        }
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                        lo = min(lo, __shfl_xor(lo, o, 64));
+                        hi = max(hi, __shfl_xor(hi, o, 64));
+                }
+                k = ka_msa_wave_sum(k);
+                common = ka_msa_wave_sum(common);
+                if (lane == 0) {
+                        a.detColRes[out0 + c] = (int)k;
+                        a.detColCommon[out0 + c] = common;
+                        a.detColCorrect[out0 + c] = (uint8_t)(k <= 1 || lo == hi);
+                }
+        }
+}
+
 void ka_cmp_run_maps(const KaCmpTab& a, int test, hipStream_t s)
 {
         cmp_maps<<<((test ? a.jobRows : a.S) + CMP_WAVES - 1) / CMP_WAVES, CMP_THREADS, 0, s>>>(a, test);
@@ -221,12 +303,14 @@ void ka_cmp_run_mask(const KaCmpTab& a, hipStream_t s)
         cmp_mask<<<(unsigned)(((long long)a.cols + 255) / 256), 256, 0, s>>>(a);
 }
 
-int ka_cmp_run_walk(const KaCmpTab& a, const int* first, int nTiles, size_t lds, hipStream_t s)
+int ka_cmp_run_walk(const KaCmpTab& a, const int* first, int nTiles, size_t lds, bool detail, hipStream_t s)
 {
+        const void* kernel = detail ? (const void*)cmp_walk_detail : (const void*)cmp_walk;
         // (64 KiB without asking, the kernel's static LDS included)
-        if (lds > 65536 - 1024 && hipFuncSetAttribute((const void*)cmp_walk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        if (lds > 65536 - 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
                 return 1;
-        cmp_walk<<<std::min(nTiles, KA_CMP_WALK_WGS), CMP_THREADS, lds, s>>>(a, first, nTiles);
+        if (detail) cmp_walk_detail<<<std::min(nTiles, KA_CMP_WALK_WGS), CMP_THREADS, lds, s>>>(a, first, nTiles);
+        else cmp_walk<<<std::min(nTiles, KA_CMP_WALK_WGS), CMP_THREADS, lds, s>>>(a, first, nTiles);
         return 0;
 }
 
@@ -237,4 +321,14 @@ void ka_cmp_run_tc(const KaCmpTab& a, hipStream_t s)
         const int chunk = std::max(1, std::min(KA_CMP_TCCHUNK, (a.jobCols + 2047) / 2048));
         const int perBlock = CMP_WAVES * chunk;
         cmp_tc<<<(unsigned)(((long long)a.jobCols + perBlock - 1) / perBlock), CMP_THREADS, 0, s>>>(a, chunk);
+}
+
+void ka_cmp_run_cols(const KaCmpTab& a, hipStream_t s)
+{
+        // the TC pass's rule over the columns of both sides: 2048 waves or more, KA_CMP_TCCHUNK columns per wave at most
+        const long long all = (long long)a.tCols + a.jobCols;
+        const int chunk = (int)std::max<long long>(1, std::min<long long>(KA_CMP_TCCHUNK, (all + 2047) / 2048));
+        const long long nW0 = ((long long)a.tCols + chunk - 1) / chunk, nW1 = ((long long)a.jobCols + chunk - 1) / chunk;
+        if (nW0 + nW1 == 0) return;
+        cmp_cols<<<(unsigned)((nW0 + nW1 + CMP_WAVES - 1) / CMP_WAVES), CMP_THREADS, 0, s>>>(a, chunk, (int)nW0);
 }

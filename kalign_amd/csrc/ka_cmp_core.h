@@ -39,8 +39,30 @@ struct KaCmpCore {
         // nJob jobs, job k a test of widths[k] columns against reference refOf[k] (NULL: k); outputs as ka_cmp_score_batch's
         int score(const char* who, const char* item, int nJob, const int* refOf, const int* widths, int pad, const KaCmpUpload& upload,
                   long long* counts, double* scores, float* sp);
+        // one job per reference (job f a test of widths[f] columns against reference f): the counts of every residue and
+        // the records of every test and reference column, as ka_cmp_fam_detail hands them out (each optional).  Fills dst
+        // and leaves st alone.  The front zeroes dst before its checks: a refused call reads as no launch
+        int detail(const char* who, const char* item, const int* widths, int pad, const KaCmpUpload& upload, int* resCounts, int* tcolRes,
+                   long long* tcolCommon, uint8_t* tcolCorrect, int* rcolRes, long long* rcolCommon, uint8_t* rcolCorrect);
+        double dst[KA_CMP_DETAIL_STATS] = {};  // ka_cmp_detail_stats: of the last detail call
 
 private:
+        // what a call numbers flat over its jobs: a first-index table each, [nJob + 1], back to back in `first`
+        enum { ROWS = 0, COLS = 1, TCOLS = 2, TILES = 3, TABLES = TILES + KA_CMP_CLASSES };
+        struct Call {                          // a call's jobs on the device, their test maps launched
+                int nJob = 0;
+                std::vector<KaCmpJob> jobs;
+                std::vector<int> first;        // [TABLES][nJob + 1]
+                size_t classLds[KA_CMP_CLASSES] = {};
+                KaCmpTab a{};
+                int last(int table) const { return first[(size_t)table * (nJob + 1) + nJob]; }
+        };
+        // the steps score() and detail() share: the job table, the upload and the test maps (events 0, 1 around the
+        // maps); then the walk of every LDS class in use (event 2 behind it).  *launches counts the kernels
+        int begin(const char* who, const char* item, int nJob, const int* refOf, const int* widths, int pad, const KaCmpUpload& upload, Call& c,
+                  int* launches);
+        int walk(const char* who, const Call& c, bool detailed, int* launches);
         float ms(int a, int b) { float m = 0.0f; (void)hipEventElapsedTime(&m, ev[a], ev[b]); return m; }
         KaCmpTab tab() const;                  // the handle's side of the table
+        DevBuf<uint8_t> dDet;                  // a detail call's outputs, one block: see detail()
 };

@@ -116,3 +116,21 @@ extern "C" int ka_cmp_fam_stats(ka_cmp_fam* h, double* stats_out)
         if (stats_out) std::copy_n(h->core.st, KA_CMP_STATS, stats_out);
         return KA_OK;
 }
+
+extern "C" int ka_cmp_fam_detail(ka_cmp_fam* h, const uint8_t* test_rows, const int* test_alnlens, int* res_counts, int* tcol_residues,
+                                 long long* tcol_common, uint8_t* tcol_correct, int* rcol_residues, long long* rcol_common, uint8_t* rcol_correct)
+{
+        if (!h) return fail("ka_cmp_fam_detail: bad arguments");
+        std::fill_n(h->core.dst, KA_CMP_DETAIL_STATS, 0.0);
+        const int F = (int)h->core.refs.size();
+        if (cmp_fam_check("ka_cmp_fam_detail", F, h->famFirst.data(), h->core.lens.data(), test_rows, test_alnlens)) return KA_FAIL;
+        return h->core.detail("ka_cmp_fam_detail", "family", test_alnlens, 1, packed(test_rows, h->famFirst.data(), F, test_alnlens), res_counts,
+                              tcol_residues, tcol_common, tcol_correct, rcol_residues, rcol_common, rcol_correct);
+}
+
+extern "C" int ka_cmp_fam_detail_stats(ka_cmp_fam* h, double* out5)
+{
+        if (!h) return fail("ka_cmp_fam_detail_stats: bad arguments");
+        if (out5) std::copy_n(h->core.dst, KA_CMP_DETAIL_STATS, out5);
+        return KA_OK;
+}

@@ -130,3 +130,25 @@ def trim_alignment(ctx, alignment, start=None, end=None):
         return [r.decode("latin-1") for r in s.compact(column_masks=[mask])[0]]
     finally:
         s.close()
+
+
+def mask_by_confidence(ctx, families, column_confidences, threshold):
+    """mask_alignment_by_confidence of the reference's benchmarks/downstream/utils.py for a list of alignments: column j of
+    family f is kept when float(column_confidences[f][j]) >= threshold, compared in double as the reference compares
+    them.  The flags go to the device as column masks (FamilySummary.compact).  Returns (rows, n_retained) per family."""
+    fams = _families(families)
+    conf = list(column_confidences)
+    if len(conf) != len(fams):
+        raise ValueError("%d confidence lists for %d alignments" % (len(conf), len(fams)))
+    t = float(threshold)
+    masks = []
+    for f, (rows, c) in enumerate(zip(fams, conf)):
+        if len(c) != len(rows[0]):
+            raise ValueError("alignment %d: %d confidences for %d columns" % (f, len(c), len(rows[0])))
+        masks.append([1 if float(x) >= t else 0 for x in c])
+    s = _summary(ctx, fams)
+    try:
+        out = s.compact(column_masks=masks)
+    finally:
+        s.close()
+    return [([r.decode("latin-1") for r in rows], len(rows[0]) if rows else 0) for rows in out]
