@@ -274,9 +274,6 @@ int ka_debug_refine_marks(int numseq, int n_tasks, const int* tasks_abc, const f
 /* Debug: 64 breadcrumb words written by workgroup 0 (context created with KA_TRACE=1 in the
    environment); readable while a kernel is still running. */
 int ka_debug_trace(ka_ctx* ctx, int* out64);
-/* Launches of the throughput kernel (round 6: unit 10, ka_task_kernel_tp; opt-in, KA_TP=1 in the environment) since the library was
- * loaded -- tests assert that the path they mean to test is the one that ran. */
-long long ka_debug_tp_launches(void);
 /* Tests only: ONE level of the device 2-means bisection (ka_kmeans.hip), launched by the function the product's level loop
  * calls, with everything it computed handed back candidate by candidate.  dm[numrows][32]: distances to the 32 anchors;
  * samples[n_samples]: the level's sample buffer (row indices); sets_start_n[2 * n_sets]: the sets to split, (start, n)

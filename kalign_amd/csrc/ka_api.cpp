@@ -18,7 +18,7 @@ __attribute__((visibility("hidden"))) int ka_fail_message(const char* m) { retur
 extern "C" const char* ka_last_error(void) { return g_err.c_str(); }
 struct ka_ctx;
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_guide.cpp)
-extern "C" int ka_abi_version(void) { return 24; }
+extern "C" int ka_abi_version(void) { return 25; }
 
 extern "C" int ka_ctx_create(int device, ka_ctx** out)
 {
@@ -229,7 +229,7 @@ KaTreeDev tree_dev(ka_ctx* c)
         D.ho_mode = c->env.ho >= 0 ? c->env.ho : 1;
         D.per_target = c->env.per;
         D.q_order = nullptr; D.q_n = 0; D.q_slots = 0; D.qw = c->env.qw; D.lw = c->env.lw; D.reuse = c->env.reuse; D.carry = c->env.carry;
-        D.tp = c->env.tp; D.reserve = 0;
+        D.reserve = 0; D.layout_pad = 0;
         D.overlap = c->overlap_plan ? 1 : 0;
         D.hw_mode = c->env.hw ? (1 | (c->env.hw_prio << 4)) : 0;
         D.lean4 = c->env.lean4;
@@ -317,7 +317,7 @@ int tree_launch(ka_ctx* c, bool reset)
                         // levels queue_first .. chain_level-1: one launch, two workgroups per CU pulling from the ordered list
                         // (workgroups per CU: two of four waves; of narrower ones as many as the registers (eight waves) and the LDS (160 KB) hold)
                         // (more than fit is harmless: a workgroup that starts late finds the rest of the list, or nothing)
-                        const int per_cu = ka_tp_ok(&D) ? 3 : (c->env.qw == 4 ? 2 : (c->env.qw == 2 ? 4 : 8));
+                        const int per_cu = c->env.qw == 4 ? 2 : (c->env.qw == 2 ? 4 : 8);
                         const int nwg = std::min(c->queue_n, per_cu * c->n_cus);
                         if (ov) {
                                 // (the chain's stream forks here: behind the leaf levels and the counter resets, beside the queue)
@@ -334,7 +334,6 @@ int tree_launch(ka_ctx* c, bool reset)
                         KaTreeDev Dq = D;
                         Dq.reserve = ov ? c->reserve_cus : 0;          // (CUs left to the head of the chain: only when the chain really goes out beside the queue)
                         if (ka_cons_big(&D)) ka_unit7_launch(&Dq, c->d_blocks.p + c->queue_off, nwg, c->queue_n, c->stream);
-                        else if (ka_tp_ok(&D)) ka_unit10_launch(&Dq, c->d_blocks.p + c->queue_off, nwg, c->queue_n, c->stream);
                         else ka_unit2_launch(&Dq, c->d_blocks.p + c->queue_off, nwg, D.cons_K > 0, c->queue_n, c->stream);
                         c->n_launches++; if (mark_launch(c)) return KA_FAIL;
                         L = (size_t)c->chain_level - 1;

@@ -22,7 +22,7 @@
 #include "ka_plan.h"         // KaEnv, KaPlan (the host-only base of the context), fail()
 #include "ka_forest.h"       // the records of the realignment-tree kernels
 
-// the task kernels live in four translation units (ka_kernels.hip, -DKA_UNIT=0..3)
+// the task kernels live in ten translation units (ka_kernels.hip, -DKA_UNIT=0..9); unit 5 is launched through unit 4
 extern "C" void ka_unit0_launch(const KaTreeDev* D, const int2* blocks_dev, int nblocks, int chain, hipStream_t stream);   // 8 waves
 extern "C" void ka_unit1_launch(const KaTreeDev* D, const int2* blocks_dev, int nblocks, int chain, hipStream_t stream);   // 8 waves + consistency
 extern "C" void ka_unit2_launch(const KaTreeDev* D, const int2* blocks_dev, int nblocks, int cons, int nqueue, hipStream_t stream);   // half (4 waves, 2 per CU)
@@ -34,9 +34,6 @@ extern "C" void ka_unit7_launch(const KaTreeDev* D, const int2* blocks_dev, int 
 extern "C" void ka_unit8_launch(const KaTreeDev* D, const int2* blocks_dev, int nblocks, hipStream_t stream);
 extern "C" void ka_unit9_launch(const KaTreeDev* D, const int2* blocks_dev, int nblocks, hipStream_t stream);
 static inline bool ka_cons_big(const KaTreeDev* D) { return D->cons_K > KA_NB - 1; }
-// round 6: the throughput kernel (unit 10; three four-wave workgroups per CU) in place of the half kernel: fast mode, no B / Z / X
-extern "C" void ka_unit10_launch(const KaTreeDev* D, const int2* blocks_dev, int nblocks, int nqueue, hipStream_t stream);
-static inline bool ka_tp_ok(const KaTreeDev* D) { return D->tp != 0 && D->cons_K == 0 && D->nres <= 20; }
 // kind: 0 = 8-wave kernel, 1 = lean (seq-seq only), 2 = half (4 waves, two workgroups per CU)
 static inline void ka_launch_task_level(const KaTreeDev* D, const int2* blocks_dev, int nblocks, int kind, int chain, hipStream_t stream)
 {
@@ -48,7 +45,6 @@ static inline void ka_launch_task_level(const KaTreeDev* D, const int2* blocks_d
                 return;
         }
         if (kind == 1) ka_unit3_launch(D, blocks_dev, nblocks, cons, stream);
-        else if (kind == 2 && ka_tp_ok(D)) ka_unit10_launch(D, blocks_dev, nblocks, 0, stream);
         else if (kind == 2) ka_unit2_launch(D, blocks_dev, nblocks, cons, 0, stream);
         else if (cons) ka_unit1_launch(D, blocks_dev, nblocks, chain, stream);
         else ka_unit0_launch(D, blocks_dev, nblocks, chain, stream);

@@ -116,7 +116,8 @@ struct KaTreeDev {
         const long long* sip_off;      // [2N-1]
         int reserve;                   // round 6, the queued launch of an overlapping run: its workgroups leave the first `reserve` CUs of XCC 0 (shader
                                        // engines 0 .. reserve / 8 - 1) to the head of the chained launch (plan_launches; 0: none)
-        int tp;                        // round 6: launches of the 4-wave kind go to the throughput kernel (unit 10) when the job allows it (host: ka_tp_ok)
+        int layout_pad;                // unused, 0.  It holds the place of a removed switch: without it the structure is eight bytes shorter, and every task kernel
+                                       // then copies its arguments another way (-5 .. +15 instructions, 16 bytes less scratch).  To go with the next change to those kernels
         int merge_batch;               // round 6, ka_update_profile: bit 0 = items in batches when both operands' records are in HBM, bit 1 = also when one is a sequence, bit 2 = also in a cluster of workgroups (KA_MERGE)
 };
 

@@ -35,22 +35,10 @@ typedef float float4v __attribute__((ext_vector_type(4)));
 #define KA_REC_CHUNKS 7                                         // 7 x 16 B = profile fields [32..59]
 #define KA_SLOT_BYTES (KA_REC_CHUNKS * KA_RING_BATCH * 16)      // 3584
 #define KA_RING_BYTES (KA_RING_SLOTS * KA_SLOT_BYTES)           // 14336 B: the column ring of a strip wave
-// KA_TP (round 6, unit 10: the THROUGHPUT kernel -- three four-wave workgroups per CU): profile-profile strips run as ka_lstrip
-// (ka_lstrip.h: an 80-column record-major ring + a 2 KB out ring), so a wave's region shrinks to 11 KB; the seq-profile score table
-// takes 21 floats per row (the kernel only runs jobs without B / Z / X: residues < 20), packed passes stage 64 records per region.
-#ifndef KA_TP
-#define KA_TP 0
-#endif
-#if KA_TP
-#define KA_WAVE_LDS 12288
-#define KA_SP_STRIDE 21
-#define KA_PK_RECS 96
-#else
 #define KA_WAVE_LDS 18432                                       // per-wave LDS region: the ring, or the staging area of a wave-local subtree (ka_subtree.h)
 #define KA_SP_STRIDE 25                                         // floats per row in the seq-profile score table
 #define KA_PK_RECS 128                                          // packed passes: staged column records per region
-#endif
-#define KA_SP_FILL (KA_SP_STRIDE < 23 ? KA_SP_STRIDE : 23)      // scores copied into a row of the seq-profile table
+#define KA_SP_FILL 23                                           // scores copied into a row of the seq-profile table
 #define KA_WAVE_LDS_LEAN 6144                                   // the same in the seq-seq kernels (no ring; residues instead of records)
 #define KA_T_STRIDE 24                                          // floats per row in the seq-seq score table
 
@@ -241,7 +229,7 @@ struct KaBonus {
 #define KA_HO_RING KA_RING_BYTES                                // 256 slots x 16 B behind the column ring: [14336, 18432) of the wave's region
 #define KA_HO_SLOTS 256
 #define KA_LDS_HO_BACK 64                                       // control words, this many bytes below the wave regions: [wave] columns written, [8 + wave] columns read
-static_assert(KA_TP || KA_HO_RING + KA_HO_SLOTS * 16 <= KA_WAVE_LDS, "hand-over ring outgrew the wave's LDS region");
+static_assert(KA_HO_RING + KA_HO_SLOTS * 16 <= KA_WAVE_LDS, "hand-over ring outgrew the wave's LDS region");
 static_assert(128 * KA_SP_STRIDE * 4 <= KA_WAVE_LDS && KA_REC_CHUNKS * KA_PK_RECS * 16 <= KA_WAVE_LDS, "seq-profile table / packed staging outgrew the wave's LDS region");
 
 // SAVE (round 5, Hirschberg prefix reuse, ka_meetup.h): svrows != nullptr -- the pass leaves the row after `sv_rows` of its rows in
@@ -1098,7 +1086,7 @@ __device__ __forceinline__ void ka_packed(const TaskShared& S, const KaSub* qc, 
                         if (sidx < lane / SLOT) lds_base += c;
                         total += c;
                 }
-                staged = total <= nreg * KA_PK_RECS;                      // 128 records per region, 64 in the throughput kernel (wave-uniform)
+                staged = total <= nreg * KA_PK_RECS;                      // 128 records per region (wave-uniform)
                 if (staged) {
                         for (int vv = ls; vv < cnt; vv += SLOT) {
                                 ka_gfloat4c* g = (ka_gfloat4c*)(S.p2 + ((long long)REC(vv) << 6) + 32);

@@ -44,7 +44,7 @@ PLANS = [(1, 3, 1, 5, True), (3, 1, 2, 1, False), (3, 3, 5, 2, True), (1, 1, 1, 
 # KA_MERGE: bit 0 the batched loop for two profiles, bit 1 with a sequence made from its residue, bit 2 on a cluster, bit 3 in
 # the 128-register units; unset = 15.  0 is the one-item loop everywhere.
 MODES = [dict(m, **c) for m in ({}, {"KA_MERGE": "0"}, {"KA_MERGE": "1"}, {"KA_MERGE": "3"}, {"KA_MERGE": "7"}) for c in ({}, {"KA_MAX_CLUSTER": "1"})]
-MODE_KEYS = ["KA_MERGE", "KA_MAX_CLUSTER", "KA_TP"]
+MODE_KEYS = ["KA_MERGE", "KA_MAX_CLUSTER"]
 
 # Codes of a first-pass path (ko_code_path: add_gap_info_to_path_n as executed sets the terminal flag only)
 FIRST_CODES = [0, 1, 2, 33, 34]

@@ -1,4 +1,4 @@
-"""Seeded jobs for the strip passes (ka_strip, ka_wstrip / ka_whelper, ka_lstrip, ka_packed) at their row and column edges: shared
+"""Seeded jobs for the strip passes (ka_strip, ka_wstrip / ka_whelper, ka_packed) at their row and column edges: shared
 by tests/test_gpu_strip_edges.py, which runs them on the device, and tests/test_strip_edge_inputs.py, which checks on the host that
 the oracle's root task of every job really has the rows and columns it is here for.  Host only: nothing here imports the device
 library."""

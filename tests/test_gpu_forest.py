@@ -1,9 +1,7 @@
-"""The throughput kernel (round 6; unit 10 of kalign_amd/csrc/ka_kernels.hip, opt-in: KA_TP=1): launches of the 4-wave kind run
-three workgroups per CU with the lean profile-profile strip of ka_lstrip.h (record-major 88-column ring fed by the strip itself,
-steps in octets, the last row through an LDS out ring) and their passes and meetups as real functions.  A launch takes that kernel
-when a guide-tree level has more tasks than the GPU has CUs: forests of the reference's goldens (every copy must come out as the
-golden does: aln_seqseq.c / aln_seqprofile.c / aln_profileprofile.c through the Hirschberg recursion of aln_controller.c, bit for
-bit) and a synthetic tree against the default kernels."""
+"""Launches of the 4-wave kind (unit 2 of kalign_amd/csrc/ka_kernels.hip: two workgroups per CU).  A launch takes that kernel when
+a guide-tree level has more tasks than the GPU has CUs: forests of the reference's goldens (every copy must come out as the golden
+does: aln_seqseq.c / aln_seqprofile.c / aln_profileprofile.c through the Hirschberg recursion of aln_controller.c, bit for bit).
+And the planner experiments of round 6, which change who runs when and must not change the alignment."""
 import numpy as np
 import pytest
 
@@ -17,13 +15,10 @@ COPIES = 40
 
 
 @pytest.mark.parametrize("name", tree_cases())
-@pytest.mark.parametrize("tp", ["1", "0"])
-def test_forest_of_goldens(name, tp, monkeypatch):
-    """40 copies of a golden tree as one forest: the lower levels hold more tasks than CUs and go to the 4-wave kind of launch --
-    the throughput kernel with KA_TP=1 (alphabets without B / Z / X; the others stay on the 4-wave kernel, same answer)"""
+def test_forest_of_goldens(name):
+    """40 copies of a golden tree as one forest: the lower levels hold more tasks than CUs and go to the 4-wave kind of launch"""
     import kalign_amd
     from kalign_amd import guide
-    monkeypatch.setenv("KA_TP", tp)
     g = Golden(name)
     if len(g.lens) < 8:
         pytest.skip("too few tasks per level even as a forest")
@@ -40,12 +35,8 @@ def test_forest_of_goldens(name, tp, monkeypatch):
     fc, ft, fd, spans = guide.forest([(g.codes, g.tasks, sd)] * copies if sd is not None else [(g.codes, g.tasks)] * copies)
     ctx = kalign_amd.Context(0)
     try:
-        before = ctx.tp_launches()
         recs, paths, gaps = ctx.msa_tree(fc, ft, g.subm, g.scal, fd)
         assert ctx.fallback_runs() == 0
-        nres = int(max(int(c.max()) for c in g.codes)) + 1
-        took_tp = ctx.tp_launches() > before
-        assert took_tp == (tp == "1" and nres <= 20), (nres, took_tp)
         want_gaps = g.gaps_list()
         for (s0, t0, ns, nt) in spans:
             sub = recs[t0:t0 + nt]
@@ -56,37 +47,8 @@ def test_forest_of_goldens(name, tp, monkeypatch):
         ctx.close()
 
 
-@pytest.mark.parametrize("shape", [(1536, 300, False), (2048, 700, False), (2048, 600, True)])
-def test_throughput_kernel_against_the_default_kernels(shape, monkeypatch):
-    """synthetic families (wider windows, several strips per pass, nucleotides): KA_TP=1 against KA_TP=0 on one context"""
-    import os
-    import bench
-    import kalign_amd
-    nseq, length, dna = shape
-    codes, tasks, dist = bench.make_workload(nseq, length, dna, 3)
-    subm, scal = bench.scoring(dna)
-    ctx = kalign_amd.Context(0)
-    try:
-        out = {}
-        for tp in ("0", "1"):
-            monkeypatch.setenv("KA_TP", tp)
-            ctx.reload_env()
-            before = ctx.tp_launches()
-            recs, paths, gaps = ctx.msa_tree(codes, tasks, subm, scal, dist)
-            assert ctx.fallback_runs() == 0
-            assert (ctx.tp_launches() > before) == (tp == "1")
-            out[tp] = ([(r.plen, r.meet, r.transition, r.score) for r in recs], [paths[r.path_off:r.path_off + r.plen + 2].copy() for r in recs], gaps)
-        assert out["0"][0] == out["1"][0]
-        for a, b in zip(out["0"][1], out["1"][1]):
-            assert np.array_equal(a, b)
-        for a, b in zip(out["0"][2], out["1"][2]):
-            assert np.array_equal(a, b)
-    finally:
-        ctx.close()
-
-
 @pytest.mark.parametrize("switches", [{"KA_SPINE": "8", "KA_RESERVE": "16"}, {"KA_SPINE": "3"}, {"KA_RESERVE": "24"}, {"KA_QORDER": "2"},
-                                      {"KA_SPINE": "6", "KA_RESERVE": "8", "KA_TP": "1"}])
+                                      {"KA_SPINE": "6", "KA_RESERVE": "8"}])
 def test_round6_schedule_experiments_give_the_same_alignment(switches, monkeypatch):
     """the planner experiments of round 6 (all off by default): the most critical entries' spines as tasks of the chained
     launch (chain_need 1 + a done flag from the queue), CUs of XCC 0 that the queued launch leaves to the head of the chain, one

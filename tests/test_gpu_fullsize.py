@@ -71,13 +71,6 @@ def test_headline_shape_protein_4096x400_matches_reference():
     run_case(4096, 400, False)
 
 
-def test_headline_shape_through_the_throughput_kernel(monkeypatch):
-    """The same tree with the levels of the queued launch on the opt-in throughput kernel (KA_TP=1, unit 10: ka_lstrip's lean
-    profile-profile strips, three workgroups per CU): the reference's gap arrays bit for bit."""
-    monkeypatch.setenv("KA_TP", "1")
-    run_case(4096, 400, False)
-
-
 def test_config2_shape_dna_256x2000_matches_reference():
     """configs[2] shape (--type dna, ~2000 nt, profile-profile dominated), scaled to 256 sequences
     so the CPU reference finishes in seconds: long anti-diagonals, multi-strip passes, clusters."""

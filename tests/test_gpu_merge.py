@@ -7,8 +7,8 @@ more columns inside either operand, profile operands that arrive with gap column
 either side of a stride and of a batched trip; tests/test_merge_inputs.py proves on the host that they are, and that the recipe
 is the oracle's and the real reference's profile.  Every form of the merge runs: the batched loop in its four instances (which
 operand is a sequence made from its residue) and the one-item loop it replaced (KA_MERGE = 0 / 1 / 3 / 7), on a cluster and on
-one workgroup, elem() under sequence weights, the two-step adjustment of refined paths, and -- as forests -- the 4-wave kernel,
-the 128-register units' lean build and the throughput kernel."""
+one workgroup, elem() under sequence weights, the two-step adjustment of refined paths, and -- as forests -- the 4-wave kernel
+and the 128-register units' lean build."""
 import numpy as np
 import pytest
 
@@ -161,11 +161,11 @@ def _levels(tasks, n):
     return lvl
 
 
-def _forest(ctx, monkeypatch, alphabet, tps, leaf_profiles):
+def _forest(ctx, monkeypatch, alphabet, leaf_profiles):
     """every job of one alphabet and one scoring (the plain tables), copied until the widest level with profile tasks holds more
     than 300 of them -- more than the GPU has CUs, and not only seq-seq tasks: that level goes to the 4-wave kind of launch, the
     seq-seq level below it to the 128-register units (the rule of tests/test_gpu_strip_edges.py's forests).  Every copy's
-    profiles must equal the recipe of its job alone."""
+    profiles must equal the recipe of its job alone, in two runs on one upload."""
     from kalign_amd import guide
     mine = [j for j in JOBS if j[2] == alphabet and j[3] == "plain"]
     per_level = {}
@@ -182,25 +182,22 @@ def _forest(ctx, monkeypatch, alphabet, tps, leaf_profiles):
     subm, scal = mj.scoring(mine[0])
     try:
         ctx.tree_upload(fc, ft, subm, scal, fd, flags=_flags(leaf_profiles))
-        for tp in tps:
-            _set(monkeypatch, {"KA_TP": tp})
+        for run in ("run 1", "run 2"):
+            _set(monkeypatch, {})
             ctx.reload_env()
-            # the seq-seq level: lean (1); the widest profile level: the 4-wave kind (2), which KA_TP=1 sends to the throughput
-            # kernel where that has an instance
-            # kernel where that has an instance; it is a launch of its own, neither queued nor chained.  Above it the levels are
+            # the seq-seq level: lean (1); the widest profile level: the 4-wave kind (2); it is a launch of its own, neither
+            # queued nor chained.  Above it the levels are
             # narrower than the device (the targets of the 1 / 3 and 3 / 2 jobs, the roots): 8-wave tasks, chained into one launch
             plan = ctx.debug_plan()
-            assert widest == 1 and plan["levels"] == 4 and plan["level_lean"].tolist() == [1, 2, 0, 0], (alphabet, tp, plan["level_lean"])
-            assert plan["queue_first"] == -1 and plan["chain_level"] == 2, (alphabet, tp, plan["queue_first"], plan["chain_level"])
-            before = ctx.tp_launches()
+            assert widest == 1 and plan["levels"] == 4 and plan["level_lean"].tolist() == [1, 2, 0, 0], (alphabet, run, plan["level_lean"])
+            assert plan["queue_first"] == -1 and plan["chain_level"] == 2, (alphabet, run, plan["queue_first"], plan["chain_level"])
             ctx.tree_run()
             got = ctx.tree_download()
-            assert ctx.fallback_runs() == 0, (alphabet, tp)
-            assert (ctx.tp_launches() > before) == (tp == "1" and alphabet != "bzx"), (alphabet, tp)
-            assert (len(got[2]), len(got[0])) == (len(fc), len(ft)) == tuple(sum(s[i] for s in spans) for i in (2, 3)), (alphabet, tp)
+            assert ctx.fallback_runs() == 0, (alphabet, run)
+            assert (len(got[2]), len(got[0])) == (len(fc), len(ft)) == tuple(sum(s[i] for s in spans) for i in (2, 3)), (alphabet, run)
             for k, (s0, t0, ns, nt) in enumerate(spans):
                 j = mine[k % len(mine)]
-                tag = (mj.job_id(j), "KA_TP=" + tp, "copy %d" % (k // len(mine)))
+                tag = (mj.job_id(j), run, "copy %d" % (k // len(mine)))
                 nodes, leaves = mj.expected(j)
                 _same_nodes(ctx, got[0], got[1], nodes, tag, t0, lambda t, ns=ns: ns + t)
                 _same(got, mj.want(j), tag, FOREST, t0, s0, (ns, nt))
@@ -213,9 +210,8 @@ def _forest(ctx, monkeypatch, alphabet, tps, leaf_profiles):
 
 @pytest.mark.parametrize("alphabet,leaf_profiles", [("protein", False), ("dna", True), ("bzx", False)])
 def test_forest_of_merge_jobs(ctx, oracle, monkeypatch, alphabet, leaf_profiles):
-    """KA_TP=0: the 4-wave kernel and the lean units' merge (KA_MERGE_LEAN); KA_TP=1: the throughput kernel (no instance for the
-    23 residue classes of B / Z / X: the 4-wave kernel again)"""
-    _forest(ctx, monkeypatch, alphabet, ["0", "1"], leaf_profiles)
+    """the 4-wave kernel and the lean units' merge (KA_MERGE_LEAN)"""
+    _forest(ctx, monkeypatch, alphabet, leaf_profiles)
 
 
 # ---- reading a sequence's records back ---------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """The strip passes at their row and column edges, against the oracle bit for bit: ka_strip (128-row strips and, with KA_Q1, 64-row
 ones; hand-over through the HBM row buffer, through the LDS ring and between the workgroups of a cluster), ka_wstrip / ka_whelper
 (strips with helper waves), ka_packed and ka_strip's small and empty passes (KA_SUBTREE=0), and -- as forests -- the 4-wave kernel's
-strips and ka_lstrip of the throughput kernel.
+strips.
 
 The jobs are tests/strip_jobs.py's: small tasks whose root has exactly the rows and columns that put a pass on an edge -- strips of
 1, 2, 63, 64, 65, 127 and 128 rows as the only, the second and the third strip of a pass, the empty pass, column counts either side of
@@ -47,7 +47,7 @@ def _same(got, want, tag, fields=EXACT, task0=0, seq0=0, span=None):
 
 
 def _set(monkeypatch, mode):
-    for k in sj.MODE_KEYS + ["KA_TP"]:
+    for k in sj.MODE_KEYS:
         monkeypatch.delenv(k, raising=False)
     for k, v in mode.items():
         monkeypatch.setenv(k, v)
@@ -96,10 +96,10 @@ def test_strip_edges_with_anchor_consistency(ctx, oracle, monkeypatch, case):
     _modes(ctx, monkeypatch, case, sj.CONS_MODES, n_anchors=3)
 
 
-def _forest(ctx, monkeypatch, alphabet, tps):
+def _forest(ctx, monkeypatch, alphabet):
     """every profile job of one alphabet, copied until the widest level with profile tasks holds at least 300 of them -- more than
-    the GPU has CUs, and not only seq-seq tasks: the level goes to the 4-wave kind of launch (the rule of tests/test_gpu_tp.py).
-    Every copy of every job must come out as the oracle's answer for that job alone."""
+    the GPU has CUs, and not only seq-seq tasks: the level goes to the 4-wave kind of launch (the rule of tests/test_gpu_forest.py).
+    Every copy of every job must come out as the oracle's answer for that job alone, in two runs on one upload."""
     from kalign_amd import api, guide
     cases = [c for c in sj.cases() if c[0] != "ss" and c[3] == alphabet]
     copies = 300 // len(cases) + 1                                    # (each job's only profile task of the widest level is its root)
@@ -109,23 +109,20 @@ def _forest(ctx, monkeypatch, alphabet, tps):
     subm, scal = sj.scoring(alphabet)
     try:
         ctx.tree_upload(fc, ft, subm, scal, fd, flags=api.FLAG_DEBUG_ROWS | api.FLAG_DEVICE_GAPS)
-        for tp in tps:
-            _set(monkeypatch, {"KA_TP": tp})
+        for run in ("run 1", "run 2"):
+            _set(monkeypatch, {})
             ctx.reload_env()
-            # the roots' level is wider than the device and not all seq-seq: a launch of the 4-wave kind (2), which KA_TP=1 sends to
-            # the throughput kernel where that has an instance
+            # the roots' level is wider than the device and not all seq-seq: a launch of the 4-wave kind (2)
             plan = ctx.debug_plan()
-            assert plan["levels"] == 2 and plan["level_lean"].tolist() == [1, 2], (alphabet, tp, plan["level_lean"])
-            assert plan["chain_level"] == -1 and plan["queue_first"] == -1, (alphabet, tp)
-            before = ctx.tp_launches()
+            assert plan["levels"] == 2 and plan["level_lean"].tolist() == [1, 2], (alphabet, run, plan["level_lean"])
+            assert plan["chain_level"] == -1 and plan["queue_first"] == -1, (alphabet, run)
             ctx.tree_run()
             got = ctx.tree_download()
-            assert ctx.fallback_runs() == 0, (alphabet, tp)
-            assert (ctx.tp_launches() > before) == (tp == "1" and alphabet != "bzx"), (alphabet, tp)
-            assert (len(got[2]), len(got[0])) == (len(fc), len(ft)) == tuple(sum(s[i] for s in spans) for i in (2, 3)), (alphabet, tp)
+            assert ctx.fallback_runs() == 0, (alphabet, run)
+            assert (len(got[2]), len(got[0])) == (len(fc), len(ft)) == tuple(sum(s[i] for s in spans) for i in (2, 3)), (alphabet, run)
             for j, (s0, t0, ns, nt) in enumerate(spans):
                 case = cases[j % len(cases)]
-                _same(got, sj.want(*case), (sj.case_id(case), "KA_TP=" + tp, "copy %d" % (j // len(cases))), FOREST, t0, s0, (ns, nt))
+                _same(got, sj.want(*case), (sj.case_id(case), run, "copy %d" % (j // len(cases))), FOREST, t0, s0, (ns, nt))
     finally:
         _set(monkeypatch, {})
         ctx.reload_env()
@@ -133,10 +130,10 @@ def _forest(ctx, monkeypatch, alphabet, tps):
 
 @pytest.mark.parametrize("alphabet", ["protein", "dna"])
 def test_forest_of_strip_edges(ctx, oracle, monkeypatch, alphabet):
-    """KA_TP=0: the 4-wave kernel's strips; KA_TP=1: the throughput kernel's (ka_lstrip)"""
-    _forest(ctx, monkeypatch, alphabet, ["0", "1"])
+    """the 4-wave kernel's strips"""
+    _forest(ctx, monkeypatch, alphabet)
 
 
 def test_forest_of_strip_edges_with_b_z_x(ctx, oracle, monkeypatch):
-    """23 residue classes: the 4-wave kernel, with KA_TP=1 as well (the throughput kernel has no NRES = 23 instance)"""
-    _forest(ctx, monkeypatch, "bzx", ["0", "1"])
+    """23 residue classes: the 4-wave kernel's NRES = 23 instance"""
+    _forest(ctx, monkeypatch, "bzx")
