@@ -129,7 +129,7 @@ struct ka_ctx : KaPlan {
         int nres = 23;
         DevBuf<uint8_t> d_codes;
         DevBuf<int> d_seq_off, d_node_len, d_level_ids, d_path_arena, d_error;
-        DevBuf<long long> d_node_prof, d_node_vote, d_dbg_off, d_timing;
+        DevBuf<long long> d_node_prof, d_dbg_off, d_timing;
         DevBuf<float> d_prof_arena, d_subm, d_dbg_arena;
         DevBuf<unsigned long long> d_counters;
         DevBuf<char> d_scratch, d_ctl;

@@ -58,7 +58,6 @@ struct KaTreeDev {
         const int* seq_off;
         int* node_len;                 // [2N-1] sequence length / profile length (msa->plen)
         long long* node_prof;          // [2N-1] offset (floats) of the node's profile in prof_arena
-        long long* node_vote;          // [2N-1] offset (floats) of the node's carried vote table in prof_arena (ka_votes_merge), -1: none
         float* prof_arena;
         unsigned long long* counters;  // [0] prof_top, [1] scratch_top, [2] path_top, [3] dbg_top (floats), [4] head of the queued launch, [5] queue tasks taken by workgroups of the chained launch
         long long prof_cap, scratch_cap, path_cap, dbg_cap;
@@ -103,8 +102,6 @@ struct KaTreeDev {
         int q_n, q_slots;              // a chained workgroup that finds more than a round of the queue still to do helps (ka_task_entry); 0: no
         int qw, lw;                    // waves per workgroup of the queued launch (KA_QW: 4, 2 or 1) / of the seq-seq leaf levels (KA_LW)
         int per_target;                // experiments (KA_PER): strips per workgroup a profile-profile task aims for at its top level (0: the built-in table)
-        int carry;                     // round 5: a node's anchor votes are carried up the tree (ka_votes_merge) instead of counted again from every
-                                       // member at every task (KA_CARRY=1; off by default: the sweeps that settle its marked cells cost what the votes cost)
         int cons_K;                    // anchors
         int cons_maxlen;               // longest sequence: bounds every anchor position
         float cons_paw;                // weight / (float)K  (per_anchor_weight, anchor_consistency.c:487)
@@ -116,8 +113,6 @@ struct KaTreeDev {
         const long long* sip_off;      // [2N-1]
         int reserve;                   // round 6, the queued launch of an overlapping run: its workgroups leave the first `reserve` CUs of XCC 0 (shader
                                        // engines 0 .. reserve / 8 - 1) to the head of the chained launch (plan_launches; 0: none)
-        int layout_pad;                // unused, 0.  It holds the place of a removed switch: without it the structure is eight bytes shorter, and every task kernel
-                                       // then copies its arguments another way (-5 .. +15 instructions, 16 bytes less scratch).  To go with the next change to those kernels
         int merge_batch;               // round 6, ka_update_profile: bit 0 = items in batches when both operands' records are in HBM, bit 1 = also when one is a sequence, bit 2 = also in a cluster of workgroups (KA_MERGE)
 };
 

@@ -70,8 +70,9 @@ struct KaCtl {
         long long scratch_off;          // cluster: scratch block allocated by member 0
         long long newp_off;             // merged profile offset in the arena (-1: root / none)
         long long path_off;             // coded path offset in the path arena
-        int vote_conf;                  // carried votes (ka_votes_merge): cells of the merged node that need an operand's members counted ...
-        int vote_types;                 // ... bit 0: some of them b's members, bit 1: a's
+        int regalloc_pad[2];            // unused, never written.  The place of two removed counters: without these eight bytes everything behind ctl_lds in
+                                        // TaskShared moves, and the task kernels allocate registers another way (unit 0: 18 scratch accesses per step instead
+                                        // of 3 in the head form of the helper-wave strip; ka_task_kernel_half: 16 bytes more scratch, 5 more spilled VGPRs)
 };
 
 // Everything the waves of a workgroup share about the task being aligned.
@@ -97,7 +98,6 @@ struct TaskShared {
         // parity (the children read it in level L+1's meetups while that level's own passes fill the other one); sliced by KaSub::roff
         KaState* sfbuf[2];
         KaState* sbbuf[2];
-        int carried;                   // this task's anchor positions come from its operands' carried vote tables (ka_cons_from_tables)
         int reuse_ok;                  // ... enabled for this task (a kernel built with it, one workgroup, no recursion-order records)
         KaSub* q[2];
         int* raw;
