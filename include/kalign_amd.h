@@ -905,6 +905,46 @@ int  ka_debug_ens_fam_consensus_host(int n_fam, const int* fam_first, const int*
  *   ka_sum_fam_identity_stats  out3: device ms of the identity pass [0]; kernel launches [1] and host synchronisations [2] of
  *                        the call that computed the matrices (1 and 1; all 0 before).  Later calls, which only copy, leave the
  *                        three values as they are, and no identity call touches ka_sum_fam_stats' six.
+ *
+ * The gap structure of the rows a handle holds, and the rows without their gaps -- no new upload (ABI 26).  What the
+ * reference's benchmarks/analysis.py: compute_gap_stats measures of an alignment (the gap opens per sequence of
+ * vsm_ensemble_experiment.py: _alignment_stats are gap blocks / N), and what dealign_msa and the strip loop of
+ * kalign_post_realign make of it.  Both come from a walk along rows, a wave per row, with the rule for a byte above and the
+ * handle's gap_char; nothing at or past column W of a row is read.  Rows are numbered flat over the batch, families in order.
+ *   A row's record  int32[4]: characters; leading gap columns (before its first character); trailing gap columns (after its
+ *                   last); gap blocks, a block being a maximal run of gaps.  An all-gap row has leading = trailing = W and
+ *                   one block: it counts its W gaps on both sides, as the reference's lstrip / rstrip arithmetic does.
+ *   ka_sum_fam_gaps      each output optional.  row_recs_out[numseq * 4]: the records.  counts_out[n_fam * 8], per family:
+ *                        rows N [0], columns W [1], characters [2], gaps [3], gap blocks [4], terminal [5]: the sum over rows
+ *                        of leading + trailing (an all-gap row adds 2 W), internal [6]: the sum over rows of
+ *                        max(0, gaps_r - leading_r - trailing_r), gappy columns [7]: those with 2 n_gap > N (the reference's
+ *                        gaps_in_col > n_seqs / 2 in exact integers).  values_out[n_fam * 7]: mean_seq_length = characters /
+ *                        N [0], expansion_factor = W / mean_seq_length when that mean is > 0, else 0.0 [1] (two roundings, as
+ *                        the reference computes it), gap_fraction = gaps / (N W) [2], mean_gap_block_len = gaps / blocks, 0.0
+ *                        without a block [3], mean_terminal_gap = terminal / N [4], mean_internal_gap = internal / N [5],
+ *                        gappy_column_fraction = gappy / W [6], each (double)a / (double)b, computed on the host from the
+ *                        counts and nowhere else.  The first call -- or ka_sum_fam_ungapped before it -- runs the row pass
+ *                        and the gappy-column pass over the whole batch: two launches and one host synchronisation, whatever
+ *                        the number of families; later calls are copies.
+ *   ka_sum_fam_gap_values  host only (no context, no GPU): values_out[n_fam * 7] from counts[n_fam * 8], the expressions
+ *                        above and their zero-denominator cases (N, N W, W, blocks or the mean 0: 0.0).
+ *                        "ka_sum_fam_gap_values: bad arguments" for n_fam < 1 or a NULL.
+ *   ka_sum_fam_ungapped_size  the characters of the batch, the bytes ka_sum_fam_ungapped writes (known from the column
+ *                        table: nothing is launched); -1 with "ka_sum_fam_ungapped_size: bad arguments" for a NULL handle.
+ *   ka_sum_fam_ungapped  out: every row's characters in order, packed, row after row with nothing between them;
+ *                        row_off_out[numseq + 1] (optional): row r lies at out + row_off_out[r], row_off_out[numseq] is the
+ *                        size.  The offsets are the running sum of the records' characters, 64 bits.  The first call runs
+ *                        the row pass if no call has yet (counted as ka_sum_fam_gaps' own), then one launch and one host
+ *                        synchronisation, and leaves the rows on the device; later calls are copies.  A cap below the size
+ *                        is refused before anything is launched: "ka_sum_fam_ungapped: 3 bytes do not hold the ungapped
+ *                        rows (5)".  A batch without a character is valid: size 0, nothing launched or waited for by the
+ *                        ungap pass, out may be NULL.
+ *   ka_sum_fam_gap_stats out6: device ms of the row pass and the gappy pass [0] and of the ungap pass [1]; kernel launches
+ *                        [2] and host synchronisations [3] of the computation of the gaps (2 and 1), and [4], [5] of the
+ *                        ungapped rows (1 and 1; 0 and 0 for a batch without a character).  All 0 before; copies leave them
+ *                        as they are; these calls touch neither ka_sum_fam_stats' six values nor
+ *                        ka_sum_fam_identity_stats' three.
+ * A refused call launches nothing and leaves the handle usable.
  */
 typedef struct ka_sum_fam ka_sum_fam;
 int  ka_sum_fam_check(int n_fam, const int* fam_first, const uint8_t* rows, const int* alnlens);
@@ -921,6 +961,11 @@ int  ka_sum_fam_stats(ka_sum_fam* h, double* stats_out);
 long long ka_sum_fam_identity_entries(int n_fam, const int* fam_first);
 int  ka_sum_fam_identity(ka_sum_fam* h, int* matches_out, int* compared_out, double* identity_out);
 int  ka_sum_fam_identity_stats(ka_sum_fam* h, double* out3);
+int  ka_sum_fam_gaps(ka_sum_fam* h, long long* counts_out, double* values_out, int* row_recs_out);
+int  ka_sum_fam_gap_values(int n_fam, const long long* counts, double* values_out);      /* host only: no context, no GPU */
+long long ka_sum_fam_ungapped_size(ka_sum_fam* h);
+int  ka_sum_fam_ungapped(ka_sum_fam* h, uint8_t* out, long long cap, long long* row_off_out);
+int  ka_sum_fam_gap_stats(ka_sum_fam* h, double* out6);
 
 #ifdef __cplusplus
 }

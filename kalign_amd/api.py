@@ -68,6 +68,7 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_sum_fam_check", "ka_sum_fam_create", "ka_sum_fam_destroy", "ka_sum_fam_columns", "ka_sum_fam_summary", "ka_sum_fam_consensus",
            "ka_sum_fam_keep", "ka_sum_fam_compact", "ka_sum_fam_rows_size", "ka_sum_fam_rows", "ka_sum_fam_stats",
            "ka_sum_fam_identity_entries", "ka_sum_fam_identity", "ka_sum_fam_identity_stats",
+           "ka_sum_fam_gaps", "ka_sum_fam_gap_values", "ka_sum_fam_ungapped_size", "ka_sum_fam_ungapped", "ka_sum_fam_gap_stats",
            "ka_guide_forest_from", "ka_guide_forest", "ka_aln_guide_forest", "ka_run_encoded_batch", "ka_batch_rows_size", "ka_batch_rows",
            "ka_batch_stats", "ka_batch_refine_stats"]
 
@@ -275,6 +276,12 @@ def load_library():
     L.ka_sum_fam_identity_entries.restype = C.c_longlong
     L.ka_sum_fam_identity.argtypes = [vp, vp, vp, vp]
     L.ka_sum_fam_identity_stats.argtypes = [vp, vp]
+    L.ka_sum_fam_gaps.argtypes = [vp, vp, vp, vp]
+    L.ka_sum_fam_gap_values.argtypes = [C.c_int, vp, vp]
+    L.ka_sum_fam_ungapped_size.argtypes = [vp]
+    L.ka_sum_fam_ungapped_size.restype = C.c_longlong
+    L.ka_sum_fam_ungapped.argtypes = [vp, vp, C.c_longlong, vp]
+    L.ka_sum_fam_gap_stats.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -1512,6 +1519,10 @@ Context.family_ensemble = _ens_fam_create
 SUM_COUNTS = ["gaps", "cells", "conserved_columns", "columns", "matching_pairs", "compared_pairs"]
 SUM_STATS = ["table_ms", "consensus_ms", "keep_ms", "compact_ms", "launches", "syncs"]
 IDENTITY_STATS = ["identity_ms", "launches", "syncs"]
+GAP_COUNTS = ["n_seqs", "alignment_length", "characters", "total_gaps", "n_gap_blocks", "terminal_gaps", "internal_gaps", "n_gappy_columns"]
+GAP_VALUES = ["mean_seq_length", "expansion_factor", "gap_fraction", "mean_gap_block_len", "mean_terminal_gap", "mean_internal_gap",
+              "gappy_column_fraction"]
+GAP_STATS = ["gaps_ms", "ungap_ms", "gaps_launches", "gaps_syncs", "ungap_launches", "ungap_syncs"]
 
 
 def identity_entries(sizes):
@@ -1679,6 +1690,62 @@ class FamilySummary(_CtxChild):
         st = np.zeros(len(IDENTITY_STATS), np.float64)
         self.ctx._chk(self.L.ka_sum_fam_identity_stats(self.h, _ptr(st)))
         return {k: (float(v) if k.endswith("_ms") else int(v)) for k, v in zip(IDENTITY_STATS, st)}
+
+    def gaps(self, want_rows=False):
+        """the gap structure of every family, one dict each with GapStats' names (benchmarks/analysis.py:
+        compute_gap_stats) -- n_seqs, alignment_length, mean_seq_length, expansion_factor, total_gaps, gap_fraction,
+        n_gap_blocks, mean_gap_block_len, mean_terminal_gap, mean_internal_gap, n_gappy_columns, gappy_column_fraction --
+        and gap_opens_per_seq (blocks / n), characters, terminal_gaps and internal_gaps (the sums behind the two means).
+        want_rows: also rows, int32 [n, 4]: a row's characters, leading and trailing gap columns and gap blocks (an
+        all-gap row: leading = trailing = width, one block).  The first call walks the rows of the whole batch on the
+        device; later calls copy."""
+        F = self._open()
+        counts, values = np.zeros((F, len(GAP_COUNTS)), np.int64), np.zeros((F, len(GAP_VALUES)), np.float64)
+        recs = np.zeros((int(self.first[-1]), 4), np.int32) if want_rows else None
+        self.ctx._chk(self.L.ka_sum_fam_gaps(self.h, _ptr(counts), _ptr(values), _ptr(recs)))
+        out = []
+        for f in range(F):
+            d = {k: int(v) for k, v in zip(GAP_COUNTS, counts[f])}
+            d.update({k: float(v) for k, v in zip(GAP_VALUES, values[f])})
+            d["gap_opens_per_seq"] = float(d["n_gap_blocks"]) / float(d["n_seqs"])
+            if want_rows:
+                d["rows"] = recs[self.first[f]:self.first[f + 1]]
+            out.append(d)
+        return out
+
+    def ungapped(self, want_offsets=False):
+        """the rows of every family without their gaps (dealign_msa): one list of bytes per family.  want_offsets: also
+        the int64 [rows + 1] offsets of the rows in the packed buffer, flat over the batch (their running lengths).  The
+        first call packs the rows on the device and leaves them there; later calls copy."""
+        self._open()
+        n = int(self.L.ka_sum_fam_ungapped_size(self.h))
+        if n < 0:
+            raise KalignAmdError(self.L.ka_last_error().decode())
+        buf = np.zeros(max(n, 1), np.uint8)
+        off = np.zeros(int(self.first[-1]) + 1, np.int64)
+        self.ctx._chk(self.L.ka_sum_fam_ungapped(self.h, _ptr(buf), n, _ptr(off)))
+        data = buf[:n].tobytes()
+        rows = [[data[off[r]:off[r + 1]] for r in range(self.first[f], self.first[f + 1])] for f in range(len(self.sizes))]
+        return (rows, off) if want_offsets else rows
+
+    def gap_stats(self):
+        """ka_sum_fam_gap_stats: device ms of the row and gappy passes and of the ungap pass; kernel launches and host
+        synchronisations of the computation of the gaps and of the ungapped rows (zeros before; unchanged by copies)"""
+        self._open()
+        st = np.zeros(len(GAP_STATS), np.float64)
+        self.ctx._chk(self.L.ka_sum_fam_gap_stats(self.h, _ptr(st)))
+        return {k: (float(v) if k.endswith("_ms") else int(v)) for k, v in zip(GAP_STATS, st)}
+
+
+def gap_values(counts):
+    """ka_sum_fam_gap_values: the seven doubles of each family from its eight exact counts (int64 [n, 8], GAP_COUNTS) -- on
+    the host alone.  float64 [n, 7] (GAP_VALUES)."""
+    L = load_library()
+    counts = np.ascontiguousarray(counts, np.int64).reshape(-1, len(GAP_COUNTS))
+    values = np.zeros((len(counts), len(GAP_VALUES)), np.float64)
+    if L.ka_sum_fam_gap_values(len(counts), _ptr(counts), _ptr(values)) != 0:
+        raise KalignAmdError(L.ka_last_error().decode())
+    return values
 
 
 def _sum_fam_create(self, families_rows, gap=b"-"):

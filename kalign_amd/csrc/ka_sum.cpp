@@ -7,6 +7,10 @@
 // device returns exact integers; the doubles are computed here, each the one division of two of those integers
 // (ka_sum_finish), and the two threshold comparisons on the device are the same divisions of the same integers.
 //
+// The gap structure (the reference's benchmarks/analysis.py: compute_gap_stats) and the rows without their gaps (dealign_msa)
+// come from a walk along rows: ka_sum_fam_gaps, ka_sum_fam_ungapped.  The row records and the families' exact sums come
+// back once and stay on the host; the doubles are computed here alone (gap_finish, which ka_sum_fam_gap_values hands out).
+//
 // Every check runs on the host before anything is launched (sum_fam_check; ka_sum_fam_check is its public form; the rule
 // of a consensus, keep or compact call: thresholds, rule): a refused call launches nothing and leaves the handle usable.
 #include <memory>
@@ -72,6 +76,21 @@ void ka_sum_finish(const long long* counts, double* values)
         values[2] = counts[5] > 0 ? (double)counts[4] / (double)counts[5] : 0.0;
 }
 
+// the seven doubles of one family's gap structure from its eight exact counts (ka_sum_fam_gaps' layout), each as the
+// reference's compute_gap_stats divides: the expansion factor is the width over the ROUNDED mean length, two roundings; a
+// zero denominator gives 0.0.  The one place these expressions live.
+void gap_finish(const long long* c, double* v)
+{
+        const double N = (double)c[0], W = (double)c[1];
+        v[0] = c[0] > 0 ? (double)c[2] / N : 0.0;
+        v[1] = v[0] > 0.0 ? W / v[0] : 0.0;
+        v[2] = c[0] * c[1] > 0 ? (double)c[3] / (double)(c[0] * c[1]) : 0.0;
+        v[3] = c[4] > 0 ? (double)c[3] / (double)c[4] : 0.0;
+        v[4] = c[0] > 0 ? (double)c[5] / N : 0.0;
+        v[5] = c[0] > 0 ? (double)c[6] / N : 0.0;
+        v[6] = c[1] > 0 ? (double)c[7] / W : 0.0;
+}
+
 // 'N' when every character of the family, upper-cased, lies in ATCGUN, else 'X' (consensus_sequence's heuristic)
 uint8_t ambiguous_of(const unsigned* present)
 {
@@ -115,6 +134,18 @@ struct ka_sum_fam {
         DevBuf<unsigned> dIdmTiles;
         DevBuf<double> dIdentity;
         double idmSt[KA_SUM_IDM_STATS] = {};   // device ms, launches and waits of the call that computed them
+        // the gap structure: the row records and the families' sums are computed by the first ka_sum_fam_gaps or
+        // ka_sum_fam_ungapped and kept on the host, the ungapped rows by the first ka_sum_fam_ungapped and kept on the device
+        bool haveGaps = false, haveUngap = false;
+        int numseq = 0;
+        std::vector<int> rowFirst, gapRecs;                      // [nFam + 1]; [numseq][KA_SUM_ROWREC]
+        std::vector<unsigned long long> gapSums;                 // [nFam][KA_SUM_GAPSUMS]
+        std::vector<long long> ungapOff;                         // [numseq + 1]: where a row's characters start
+        DevBuf<int> dRowFirst, dGapRecs;
+        DevBuf<unsigned long long> dGapSums;
+        DevBuf<long long> dUngapOff;
+        DevBuf<uint8_t> dUngap;
+        double gapSt[KA_SUM_GAP_STATS] = {};   // ka_sum_fam_gap_stats
 
         ~ka_sum_fam()
         {
@@ -124,6 +155,7 @@ struct ka_sum_fam {
                 dNewW.release(); dMasks.release(); dRows.release(); dTopChar.release(); dAmbiguous.release(); dCons.release(); dOut.release(); dSame.release();
                 dMaskOff.release(); dOutOff.release(); dFamSums.release(); dPresent.release(); dThr.release();
                 dIdmFirst.release(); dMatches.release(); dCompared.release(); dIdmTiles.release(); dIdentity.release();
+                dRowFirst.release(); dGapRecs.release(); dGapSums.release(); dUngapOff.release(); dUngap.release();
         }
         float ms() { float m = 0.0f; (void)hipEventElapsedTime(&m, ev[0], ev[1]); return m; }
         // a call that launches (create, consensus, keep, compact): nothing launched, nothing waited for yet.  The hand-outs
@@ -154,6 +186,17 @@ struct ka_sum_fam {
         // the column rule of keep and compact, checked and uploaded; *masked: the table carries masks
         int rule(const char* who, const double* gapThr, const int* masks, const long long* maskOff, bool* masked);
         int identity(const char* who, int* matchesOut, int* comparedOut, double* identityOut);
+        KaGapTab gapTab() const
+        {
+                KaGapTab a{};
+                a.nFam = nFam; a.nRows = numseq; a.cols = cols; a.gap = gap;
+                a.fams = dFams.p; a.rowFirst = dRowFirst.p; a.colFirst = dFirst.p + nFam + 1; a.rows = dRows.p; a.nGap = dNGap.p;
+                a.recs = dGapRecs.p; a.sums = dGapSums.p; a.off = dUngapOff.p; a.out = dUngap.p;
+                return a;
+        }
+        long long characters() const;          // of the batch, from the column table's sums: nothing is launched
+        int gaps(const char* who);             // the row pass and the gappy pass, once
+        int ungapped(const char* who, uint8_t* out, long long cap, long long* rowOffOut);
 };
 
 int ka_sum_fam::create(const char* who, int n_fam, const int* fam_first, const uint8_t* rows, const int* alnlens)
@@ -171,6 +214,7 @@ int ka_sum_fam::create(const char* who, int n_fam, const int* fam_first, const u
                 cols += d.W;
                 nItems += d.N * d.chunks;
                 bytes += (long long)d.N * (d.W + 1);
+                numseq += d.N;
         }
         first[nFam] = nTiles; first[2 * nFam + 1] = cols; first[3 * nFam + 2] = nItems;
         famSums.assign((size_t)nFam * KA_SUM_FAMSUMS, 0);
@@ -439,6 +483,121 @@ extern "C" int ka_sum_fam_identity_stats(ka_sum_fam* h, double* out3)
 {
         if (!h) return fail("ka_sum_fam_identity_stats: bad arguments");
         if (out3) std::copy_n(h->idmSt, KA_SUM_IDM_STATS, out3);
+        return KA_OK;
+}
+
+long long ka_sum_fam::characters() const
+{
+        long long n = 0;
+        for (int f = 0; f < nFam; f++) n += (long long)fams[f].N * fams[f].W - (long long)famSums[(size_t)f * KA_SUM_FAMSUMS + KA_SUM_GAPS];
+        return n;
+}
+
+// The first-row table up, the row pass and the gappy pass over the whole batch, the records and the sums down, one wait.
+// They stay on the host: every later call is a copy from there.
+int ka_sum_fam::gaps(const char* who)
+{
+        if (haveGaps) return KA_OK;
+        const std::string me(who);
+        int launches = 0;
+        HIPCHK(hipSetDevice(device));
+        rowFirst.assign((size_t)nFam + 1, 0);
+        for (int f = 0; f < nFam; f++) rowFirst[f + 1] = rowFirst[f] + fams[f].N;
+        gapRecs.assign((size_t)numseq * KA_SUM_ROWREC, 0);
+        gapSums.assign((size_t)nFam * KA_SUM_GAPSUMS, 0);
+        if (dRowFirst.alloc(rowFirst.size()) || dGapRecs.alloc(gapRecs.size()) || dGapSums.alloc(gapSums.size())) return fail(me + ": out of device memory");
+        HIPCHK(hipMemcpyAsync(dRowFirst.p, rowFirst.data(), sizeof(int) * rowFirst.size(), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemsetAsync(dGapSums.p, 0, sizeof(unsigned long long) * gapSums.size(), stream));
+        HIPCHK(hipEventRecord(ev[0], stream));
+        ka_sum_run_gaps(gapTab(), stream, &launches);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev[1], stream));
+        HIPCHK(hipMemcpyAsync(gapRecs.data(), dGapRecs.p, sizeof(int) * gapRecs.size(), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(gapSums.data(), dGapSums.p, sizeof(unsigned long long) * gapSums.size(), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        gapSt[0] = ms(); gapSt[2] = launches; gapSt[3] = 1;
+        haveGaps = true;
+        return KA_OK;
+}
+
+// Where every row's characters start, a running sum of the records' characters on the host, goes up in one copy; one launch
+// packs the rows.  A batch without a character launches nothing.  The rows stay on the device: later calls copy.
+int ka_sum_fam::ungapped(const char* who, uint8_t* out, long long cap, long long* rowOffOut)
+{
+        const std::string me(who);
+        const long long size = characters();
+        if (cap < size) return fail(me + ": " + std::to_string(cap) + " bytes do not hold the ungapped rows (" + std::to_string(size) + ")");
+        if (!out && size > 0) return fail(me + ": bad arguments");
+        if (gaps(who)) return KA_FAIL;
+        HIPCHK(hipSetDevice(device));
+        const bool compute = !haveUngap;
+        int launches = 0;
+        if (compute) {
+                ungapOff.assign((size_t)numseq + 1, 0);
+                for (int r = 0; r < numseq; r++) ungapOff[r + 1] = ungapOff[r] + gapRecs[(size_t)r * KA_SUM_ROWREC + KA_ROW_CHARS];
+                if (ungapOff[numseq] != size)
+                        return fail(me + ": the rows hold " + std::to_string(ungapOff[numseq]) + " characters, the column table " + std::to_string(size));
+                if (size > 0) {
+                        if (dUngapOff.alloc(ungapOff.size()) || dUngap.alloc((size_t)size)) return fail(me + ": out of device memory");
+                        HIPCHK(hipMemcpyAsync(dUngapOff.p, ungapOff.data(), sizeof(long long) * ungapOff.size(), hipMemcpyHostToDevice, stream));
+                        HIPCHK(hipEventRecord(ev[0], stream));
+                        ka_sum_run_ungap(gapTab(), stream, &launches);
+                        HIPCHK(hipGetLastError());
+                        HIPCHK(hipEventRecord(ev[1], stream));
+                }
+        }
+        if (size > 0) {
+                HIPCHK(hipMemcpyAsync(out, dUngap.p, (size_t)size, hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+        }
+        if (compute) {
+                if (size > 0) { gapSt[1] = ms(); gapSt[4] = launches; gapSt[5] = 1; }
+                haveUngap = true;
+        }
+        if (rowOffOut) std::copy(ungapOff.begin(), ungapOff.end(), rowOffOut);
+        return KA_OK;
+}
+
+extern "C" int ka_sum_fam_gap_values(int n_fam, const long long* counts, double* values_out)
+{
+        if (n_fam < 1 || !counts || !values_out) return fail("ka_sum_fam_gap_values: bad arguments");
+        for (int f = 0; f < n_fam; f++) gap_finish(counts + (size_t)f * KA_SUM_GAP_COUNTS, values_out + (size_t)f * KA_SUM_GAP_VALUES);
+        return KA_OK;
+}
+
+extern "C" int ka_sum_fam_gaps(ka_sum_fam* h, long long* counts_out, double* values_out, int* row_recs_out)
+{
+        if (!h) return fail("ka_sum_fam_gaps: bad arguments");
+        if (h->gaps("ka_sum_fam_gaps")) return KA_FAIL;
+        for (int f = 0; f < h->nFam; f++) {
+                const unsigned long long* s = &h->gapSums[(size_t)f * KA_SUM_GAPSUMS];
+                const KaSumFam& d = h->fams[f];
+                const long long cells = (long long)d.N * d.W;
+                const long long counts[KA_SUM_GAP_COUNTS] = { d.N, d.W, (long long)s[KA_GAP_CHARS], cells - (long long)s[KA_GAP_CHARS], (long long)s[KA_GAP_BLOCKS],
+                                                              (long long)s[KA_GAP_TERMINAL], (long long)s[KA_GAP_INTERNAL], (long long)s[KA_GAP_GAPPY] };
+                if (counts_out) std::copy_n(counts, KA_SUM_GAP_COUNTS, counts_out + (size_t)f * KA_SUM_GAP_COUNTS);
+                if (values_out) gap_finish(counts, values_out + (size_t)f * KA_SUM_GAP_VALUES);
+        }
+        if (row_recs_out) std::copy(h->gapRecs.begin(), h->gapRecs.end(), row_recs_out);
+        return KA_OK;
+}
+
+extern "C" long long ka_sum_fam_ungapped_size(ka_sum_fam* h)
+{
+        if (!h) return fail("ka_sum_fam_ungapped_size: bad arguments"), -1;
+        return h->characters();
+}
+
+extern "C" int ka_sum_fam_ungapped(ka_sum_fam* h, uint8_t* out, long long cap, long long* row_off_out)
+{
+        if (!h) return fail("ka_sum_fam_ungapped: bad arguments");
+        return h->ungapped("ka_sum_fam_ungapped", out, cap, row_off_out);
+}
+
+extern "C" int ka_sum_fam_gap_stats(ka_sum_fam* h, double* out6)
+{
+        if (!h) return fail("ka_sum_fam_gap_stats: bad arguments");
+        if (out6) std::copy_n(h->gapSt, KA_SUM_GAP_STATS, out6);
         return KA_OK;
 }
 

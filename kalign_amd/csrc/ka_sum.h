@@ -28,6 +28,30 @@
 #define KA_SUM_IDM_THREADS 256
 #define KA_SUM_IDM_STATS 3         // ka_sum_fam_identity_stats: see include/kalign_amd.h
 
+// the walk along rows (sum_gap_rows, sum_ungap): a wave per row, KA_SUM_CHUNK columns a step as four ballots of 64
+#define KA_SUM_GAP_THREADS 1024    // sum_gap_rows: sixteen waves, sixteen consecutive rows, per workgroup
+#define KA_SUM_ROW_THREADS 256     // sum_ungap: four waves, four rows, per workgroup
+#define KA_SUM_ROWREC 4            // a row's record: see the enum below
+#define KA_SUM_GAPSUMS 5           // a family's sums of the gap structure: see the enum below
+#define KA_SUM_GAP_COUNTS 8        // ka_sum_fam_gaps' counts per family, KA_SUM_GAP_VALUES its doubles: see include/kalign_amd.h
+#define KA_SUM_GAP_VALUES 7
+#define KA_SUM_GAP_STATS 6         // ka_sum_fam_gap_stats: see include/kalign_amd.h
+
+enum {
+        KA_ROW_CHARS = 0,          // characters of the row
+        KA_ROW_LEADING = 1,        // gap columns before its first character (W in an all-gap row)
+        KA_ROW_TRAILING = 2,       // gap columns after its last character (W in an all-gap row)
+        KA_ROW_BLOCKS = 3,         // maximal runs of gaps
+};
+
+enum {
+        KA_GAP_CHARS = 0,          // sum over the family's rows of the characters
+        KA_GAP_BLOCKS = 1,         // ... of the gap blocks
+        KA_GAP_TERMINAL = 2,       // ... of leading + trailing (an all-gap row adds 2 W)
+        KA_GAP_INTERNAL = 3,       // ... of max(0, gaps - leading - trailing)
+        KA_GAP_GAPPY = 4,          // columns with 2 nGap > N
+};
+
 enum {
         KA_SUM_GAPS = 0,           // gap bytes
         KA_SUM_CONSERVED = 1,      // columns with a character and one distinct character
@@ -83,9 +107,28 @@ struct KaIdmTab {
         double* identity;                      // [entries]
 };
 
+// the walk along the rows of the batch: rows are numbered flat over the families, family f's are rowFirst[f] ..
+// rowFirst[f + 1] - 1
+struct KaGapTab {
+        int nFam, nRows, cols;
+        uint8_t gap;
+        const KaSumFam* fams;                  // [nFam]
+        const int* rowFirst;                   // [nFam + 1]
+        const int* colFirst;                   // [nFam + 1]
+        const uint8_t* rows;
+        const int* nGap;                       // [cols] of the column table
+        int* recs;                             // [nRows][KA_SUM_ROWREC]
+        unsigned long long* sums;              // [nFam][KA_SUM_GAPSUMS] (zeroed first by the caller)
+        // the ungapped rows: row r's characters, in order, from out + off[r]; off[nRows] bytes in all
+        const long long* off;                  // [nRows + 1]
+        uint8_t* out;
+};
+
 // ka_sum.hip: every launcher adds the kernels it launches to *launches
 int ka_sum_run_columns(const KaSumTab& a, hipStream_t s, int* launches);     // the column table, the family sums and the presence masks (zeroed first by the caller); 1: the LDS was refused
 void ka_sum_run_consensus(const KaSumTab& a, hipStream_t s, int* launches);
 void ka_sum_run_keep(const KaSumTab& a, hipStream_t s, int* launches);       // keep flags, then the per-family scan: src, newW
 void ka_sum_run_gather(const KaSumTab& a, hipStream_t s, int* launches);     // outOff over the families, then the rows
 int ka_sum_run_identity(const KaIdmTab& a, hipStream_t s, int* launches);     // the three matrices, both triangles; 1: the LDS was refused
+void ka_sum_run_gaps(const KaGapTab& a, hipStream_t s, int* launches);       // the row records and the families' five sums: the row pass, then the gappy columns
+void ka_sum_run_ungap(const KaGapTab& a, hipStream_t s, int* launches);      // the characters of every row, packed at a.off

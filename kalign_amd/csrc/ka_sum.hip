@@ -20,6 +20,13 @@
 //                  columns staged in LDS with per-row character marks; a lane holds 2 x 2 pairs and takes four columns per
 //                  32-bit operation: XOR, an exact zero-byte test, population counts.  Exact counts, the doubles one
 //                  division each, both triangles written by the tile of the upper one.
+//   sum_gap_rows   the walk along rows: a wave per row of the batch (the family by ka_fam_find over the first-row table), 256
+//                  columns a step as four ballots of 64.  Per row its characters, leading and trailing gap columns and gap
+//                  blocks from population counts, count-leading / count-trailing zeros and one carried bit; the record to
+//                  memory, the family's four sums by 64-bit atomics, once per family that a workgroup of 16 rows meets.
+//   sum_gappy      flat over the columns: the columns with 2 nGap > N of every family, from the column table
+//   sum_ungap      a wave per row: its characters packed in order at the row's 64-bit offset, a lane's place the
+//                  population count of the character mask below it
 #include <algorithm>
 #include "ka_sum.h"
 #include "ka_msa.h"
@@ -372,6 +379,147 @@ __global__ __launch_bounds__(KA_SUM_IDM_THREADS) void sum_identity(KaIdmTab a)
                 }
 }
 
+// ---- the walk along rows ------------------------------------------------------------------------------------------------
+// A wave per row, rows numbered flat over the batch (the family by ka_fam_find over the first-row table).  A step takes
+// KA_SUM_CHUNK columns as four ballots of 64, lane l of ballot q the column c0 + 64 q + l: a byte per lane, so that a row may
+// start at any byte, and the loads of all four go out before the first ballot.  A lane at or past column W loads nothing
+// and is neither a gap nor a character: the byte after a row, the next row and the end of the upload are never read.
+// Everything after the ballots is wave-uniform arithmetic on 64-bit masks.
+struct RowWalk {
+        const uint8_t* row;
+        int f, W;
+};
+
+__device__ __forceinline__ RowWalk row_walk(const KaGapTab& a, int r)
+{
+        RowWalk w;
+        w.f = ka_fam_find(a.rowFirst, a.nFam, r);
+        const KaSumFam fam = a.fams[w.f];
+        w.W = fam.W;
+        w.row = a.rows + fam.rowOff + (long long)(r - a.rowFirst[w.f]) * ((long long)fam.W + 1);
+        return w;
+}
+
+// the bytes of one step, -1 at and past column W
+__device__ __forceinline__ void row_step(const RowWalk& w, int c0, int lane, int* b)
+{
+#pragma unroll
+        for (int q = 0; q < KA_SUM_CHUNK / 64; q++) {
+                const int c = c0 + 64 * q + lane;
+                b[q] = c < w.W ? (int)w.row[c] : -1;
+        }
+}
+
+// A row's record and its share of the family's sums.  Gap blocks: a block starts at a gap whose left neighbour is no gap --
+// inside a ballot the mask shifted by one, at its first column the carried bit, which says whether the last column of the
+// ballot before was a gap (so a block that crosses an edge is counted once, and one that ends at an edge is counted).  The
+// first and the last character of the row give leading and trailing; a row without a character has leading = trailing = W.
+// A workgroup's rows are consecutive, so those of one family are neighbours: their four sums are added up in LDS and go to
+// the family's by one 64-bit atomic each per family the workgroup meets (a family of thousands of rows would otherwise
+// queue one atomic per row on the same four addresses).
+__global__ __launch_bounds__(KA_SUM_GAP_THREADS) void sum_gap_rows(KaGapTab a)
+{
+        constexpr int kWaves = KA_SUM_GAP_THREADS / 64;
+        __shared__ long long part[kWaves][KA_SUM_ROWREC];
+        __shared__ int famOf[kWaves];                            // -1: no row
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const long long r = (long long)blockIdx.x * kWaves + wave;
+        int f = -1;
+        long long sum = 0;
+        if (r < a.nRows) {                                       // (the whole wave)
+                const RowWalk w = row_walk(a, (int)r);
+                const int gap = a.gap;
+                int gaps = 0, blocks = 0, first = w.W, last = -1;        // first, last: the columns of the first and last character
+                unsigned long long carry = 0;
+                for (int c0 = 0; c0 < w.W; c0 += KA_SUM_CHUNK) {
+                        int b[KA_SUM_CHUNK / 64];
+                        row_step(w, c0, lane, b);
+#pragma unroll
+                        for (int q = 0; q < KA_SUM_CHUNK / 64; q++) {
+                                const unsigned long long m = __ballot(b[q] == gap), k = __ballot(b[q] >= 0 && b[q] != gap);
+                                gaps += __popcll(m);
+                                blocks += __popcll(m & ~(m << 1 | carry));
+                                carry = m >> 63;                 // (read again only when this ballot was full)
+                                if (k) {
+                                        if (first == w.W) first = c0 + 64 * q + __ffsll((long long)k) - 1;
+                                        last = c0 + 64 * q + 63 - __clzll((long long)k);
+                                }
+                        }
+                }
+                const int chars = w.W - gaps, leading = first, trailing = last < 0 ? w.W : w.W - 1 - last;
+                const long long terminal = (long long)leading + trailing;
+                const int rec = lane == KA_ROW_CHARS ? chars : lane == KA_ROW_LEADING ? leading : lane == KA_ROW_TRAILING ? trailing : blocks;
+                sum = lane == KA_GAP_CHARS ? chars : lane == KA_GAP_BLOCKS ? blocks : lane == KA_GAP_TERMINAL ? terminal : max(0ll, gaps - terminal);
+                static_assert(KA_SUM_ROWREC == 4 && KA_GAP_INTERNAL == 3, "four lanes write the record and hold the four row sums");
+                if (lane < KA_SUM_ROWREC) a.recs[r * KA_SUM_ROWREC + lane] = rec;
+                f = w.f;
+        }
+        if (lane < KA_SUM_ROWREC) part[wave][lane] = sum;
+        if (lane == 0) famOf[wave] = f;
+        __syncthreads();
+        if (threadIdx.x >= KA_SUM_ROWREC) return;
+        long long acc = 0;
+        for (int w = 0; w < kWaves && famOf[w] >= 0; w++) {
+                acc += part[w][threadIdx.x];
+                if (w + 1 < kWaves && famOf[w + 1] == famOf[w]) continue;
+                if (acc) atomicAdd(&a.sums[(long long)famOf[w] * KA_SUM_GAPSUMS + threadIdx.x], (unsigned long long)acc);
+                acc = 0;
+        }
+}
+
+// flat over the columns of the batch: a column is gappy when more than half of its family's rows hold a gap, 2 nGap > N.
+// A wave whose columns lie in one family adds their number once; where a family ends inside it, each gappy column adds for
+// itself.
+__global__ __launch_bounds__(256) void sum_gappy(KaGapTab a)
+{
+        const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+        const int lane = threadIdx.x & 63;
+        int f = -1;
+        bool gappy = false;
+        if (g < a.cols) {
+                f = ka_fam_find(a.colFirst, a.nFam, (int)g);
+                gappy = 2ll * a.nGap[g] > a.fams[f].N;
+        }
+        const int f0 = __shfl(f, 0, 64);
+        if (f0 < 0) return;                                      // (the whole wave is past the last column)
+        unsigned long long* sums = a.sums + KA_GAP_GAPPY;
+        if (__all(f == f0 || f < 0)) {
+                const unsigned long long m = __ballot(gappy);
+                if (lane == 0 && m) atomicAdd(&sums[(long long)f0 * KA_SUM_GAPSUMS], (unsigned long long)__popcll(m));
+        } else if (gappy)
+                atomicAdd(&sums[(long long)f * KA_SUM_GAPSUMS], 1ull);
+}
+
+// the characters of a row in order from out + off[r]: within a ballot a lane's place is the population count of the
+// character mask below it, after the characters of the ballots before.  A wave reads and writes consecutive bytes.  The
+// offsets come from the row records of sum_gap_rows, which applies the same rule to the same bytes; a write is held inside
+// the row's own range regardless.
+__global__ __launch_bounds__(KA_SUM_ROW_THREADS) void sum_ungap(KaGapTab a)
+{
+        const int lane = threadIdx.x & 63;
+        const long long r = (long long)blockIdx.x * (KA_SUM_ROW_THREADS / 64) + (threadIdx.x >> 6);
+        if (r >= a.nRows) return;
+        const long long n = a.off[r + 1] - a.off[r];
+        if (n <= 0) return;                                      // (an all-gap row)
+        const RowWalk w = row_walk(a, (int)r);
+        const int gap = a.gap;
+        const unsigned long long below = (1ull << lane) - 1ull;
+        uint8_t* o = a.out + a.off[r];
+        long long run = 0;
+        for (int c0 = 0; c0 < w.W && run < n; c0 += KA_SUM_CHUNK) {
+                int b[KA_SUM_CHUNK / 64];
+                row_step(w, c0, lane, b);
+#pragma unroll
+                for (int q = 0; q < KA_SUM_CHUNK / 64; q++) {
+                        const bool ch = b[q] >= 0 && b[q] != gap;
+                        const unsigned long long k = __ballot(ch);
+                        const long long j = run + __popcll(k & below);
+                        if (ch && j < n) o[j] = (uint8_t)b[q];
+                        run += __popcll(k);
+                }
+        }
+}
+
 } // namespace
 
 // Each launcher counts its launches where it makes them (*launches is the caller's counter of the call).
@@ -404,6 +552,22 @@ void ka_sum_run_gather(const KaSumTab& a, hipStream_t s, int* launches)
         sum_offsets<<<1, 256, 0, s>>>(a);
         ++*launches;
         sum_gather<<<(unsigned)(((long long)a.nItems + 3) / 4), 256, 0, s>>>(a);
+        ++*launches;
+}
+
+void ka_sum_run_gaps(const KaGapTab& a, hipStream_t s, int* launches)
+{
+        constexpr int kRows = KA_SUM_GAP_THREADS / 64;
+        sum_gap_rows<<<(unsigned)(((long long)a.nRows + kRows - 1) / kRows), KA_SUM_GAP_THREADS, 0, s>>>(a);
+        ++*launches;
+        sum_gappy<<<(unsigned)(((long long)a.cols + 255) / 256), 256, 0, s>>>(a);
+        ++*launches;
+}
+
+void ka_sum_run_ungap(const KaGapTab& a, hipStream_t s, int* launches)
+{
+        constexpr int kRows = KA_SUM_ROW_THREADS / 64;
+        sum_ungap<<<(unsigned)(((long long)a.nRows + kRows - 1) / kRows), KA_SUM_ROW_THREADS, 0, s>>>(a);
         ++*launches;
 }
 

@@ -2,6 +2,9 @@
 pairwise_identity_matrix with the reference's names, arguments and return shapes, for one alignment (a list of str) and -- in one device pass, the
 number of launches independent of the batch -- for a list of families (Context.family_summary = ka_sum_fam).
 
+gap_stats is compute_gap_stats of the reference's benchmarks/analysis.py (expansion factor, gap blocks, terminal against
+internal gaps, gappy columns), dealign its dealign_msa: the sequences without their gaps.
+
 A gap is '-'; every other character counts and is compared as it stands (upper and lower case differ), as in kalign.utils.
 Results equal the reference's bit for bit.  There is no CPU fallback: every function takes a Context."""
 from .api import KalignAmdError
@@ -83,6 +86,40 @@ def pairwise_identity_matrices(ctx, families):
         return s.identity()
     finally:
         s.close()
+
+
+def gap_stats_families(ctx, families):
+    """compute_gap_stats of the reference's benchmarks/analysis.py for every alignment of the list (rows as str or bytes):
+    dicts with GapStats' field names, and with gap_opens_per_seq, characters, terminal_gaps and internal_gaps"""
+    s = _summary(ctx, _families(families))
+    try:
+        return s.gaps()
+    finally:
+        s.close()
+
+
+def dealign_families(ctx, families):
+    """every alignment of the list without its gaps (the reference's dealign_msa): per alignment the list of its sequences,
+    str where its rows were str and bytes where they were bytes; a row of gaps alone gives an empty sequence"""
+    families = [list(f) for f in families]
+    text = [bool(f) and isinstance(f[0], str) for f in families]
+    s = _summary(ctx, _families(families))
+    try:
+        out = s.ungapped()
+    finally:
+        s.close()
+    return [[r.decode("latin-1") for r in rows] if t else rows for rows, t in zip(out, text)]
+
+
+def gap_stats(ctx, alignment):
+    """benchmarks/analysis.py: compute_gap_stats of one alignment: expansion factor, gap blocks and their mean length,
+    terminal against internal gaps per sequence, gappy columns"""
+    return gap_stats_families(ctx, [alignment])[0]
+
+
+def dealign(ctx, alignment):
+    """one alignment's sequences without their gaps, in the type they were given"""
+    return dealign_families(ctx, [alignment])[0]
 
 
 def alignment_stats(ctx, alignment):
