@@ -251,10 +251,10 @@ int ka_debug_reload_env(ka_ctx* ctx);
  * plans it.  The KA_* switches are read from the environment on every call.  The plan comes back flattened:
  *   scalars[16]            0 levels, 1 entries of the block table, 2 workgroups one task may use, 3 trees, 4 first level of the chained
  *                          launch (-1: none), 5 first level of the queued launch (-1: none), 6 / 7 the queue's list in the block table
- *                          (first entry, entries), 8 overlapping launches, 9 CUs kept for the head of the chain, 10 / 11 the chained
- *                          launch's table in the block table (first entry, entries; 0, 0 without one), 12 .. 15 zero
- *   per_task[7 * n_tasks]  parent, chain_need, is_root, wait_mult, qa, qb of every task, then whether it is a spine task
- *   blocks[2 * entries]    the block table, (task, member | cluster size << 8 | flags) per workgroup: one table per level, the queue's
+ *                          (first entry, entries), 8 overlapping launches, 9 / 10 the chained launch's table in the block table
+ *                          (first entry, entries; 0, 0 without one), 11 .. 15 zero
+ *   per_task[6 * n_tasks]  parent, chain_need, is_root, wait_mult, qa, qb of every task
+ *   blocks[2 * entries]    the block table, (task, member | cluster size << 8) per workgroup: one table per level, the queue's
  *                          list, the chained launch's table
  *   blocks_off[levels + 1] first entry of every level's table;  level_lean[levels]: its launch kind (0 eight waves, 1 lean, 2 half)
  * blocks_off and level_lean must hold n_tasks + 1 and n_tasks values.  With more than blocks_cap entries the call fails after it has

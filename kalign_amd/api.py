@@ -1881,14 +1881,14 @@ def dist_plan_subtrees(lens, tasks, world):
 
 
 PLAN_SCALARS = ("levels", "n_blocks", "max_cluster", "n_trees", "chain_level", "queue_first", "queue_off", "queue_n", "overlap_plan",
-                "reserve_cus", "chain_blocks_off", "chain_blocks_n")
-PLAN_TASK_FIELDS = ("parent", "chain_need", "is_root", "wait_mult", "qa", "qb", "spine")
+                "chain_blocks_off", "chain_blocks_n")
+PLAN_TASK_FIELDS = ("parent", "chain_need", "is_root", "wait_mult", "qa", "qb")
 
 
 def _flat_plan(L, n_tasks, n_cus, call):
     """one flattened launch plan (ka_debug_plan / ka_debug_ctx_plan) as a dict: the PLAN_SCALARS as ints, the PLAN_TASK_FIELDS
     as int32[n_tasks], blocks int32[n, 2], blocks_off, level_lean"""
-    scalars, per_task = np.zeros(16, np.int32), np.zeros((7, n_tasks), np.int32)
+    scalars, per_task = np.zeros(16, np.int32), np.zeros((len(PLAN_TASK_FIELDS), n_tasks), np.int32)
     blocks_off, level_lean = np.zeros(n_tasks + 1, np.int32), np.zeros(n_tasks, np.int32)
     cap = 4 * n_tasks + 8 * n_cus + 4096
     for _ in range(2):

@@ -18,7 +18,7 @@ __attribute__((visibility("hidden"))) int ka_fail_message(const char* m) { retur
 extern "C" const char* ka_last_error(void) { return g_err.c_str(); }
 struct ka_ctx;
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_guide.cpp)
-extern "C" int ka_abi_version(void) { return 26; }
+extern "C" int ka_abi_version(void) { return 27; }
 
 extern "C" int ka_ctx_create(int device, ka_ctx** out)
 {
@@ -228,7 +228,6 @@ KaTreeDev tree_dev(ka_ctx* c)
         D.ho_mode = c->env.ho >= 0 ? c->env.ho : 1;
         D.per_target = c->env.per;
         D.q_order = nullptr; D.q_n = 0; D.q_slots = 0; D.qw = c->env.qw; D.lw = c->env.lw; D.reuse = c->env.reuse;
-        D.reserve = 0;
         D.overlap = c->overlap_plan ? 1 : 0;
         D.hw_mode = c->env.hw ? (1 | (c->env.hw_prio << 4)) : 0;
         D.lean4 = c->env.lean4;
@@ -330,10 +329,8 @@ int tree_launch(ka_ctx* c, bool reset)
                                 // queue would still be dispatched first.  Hold it back until the chain's workgroups have the CUs.
                                 std::this_thread::sleep_for(std::chrono::milliseconds(20));
                         }
-                        KaTreeDev Dq = D;
-                        Dq.reserve = ov ? c->reserve_cus : 0;          // (CUs left to the head of the chain: only when the chain really goes out beside the queue)
-                        if (ka_cons_big(&D)) ka_unit7_launch(&Dq, c->d_blocks.p + c->queue_off, nwg, c->queue_n, c->stream);
-                        else ka_unit2_launch(&Dq, c->d_blocks.p + c->queue_off, nwg, D.cons_K > 0, c->queue_n, c->stream);
+                        if (ka_cons_big(&D)) ka_unit7_launch(&D, c->d_blocks.p + c->queue_off, nwg, c->queue_n, c->stream);
+                        else ka_unit2_launch(&D, c->d_blocks.p + c->queue_off, nwg, D.cons_K > 0, c->queue_n, c->stream);
                         c->n_launches++; if (mark_launch(c)) return KA_FAIL;
                         L = (size_t)c->chain_level - 1;
                         if (chain_first) { HIPCHK(hipStreamWaitEvent(c->stream, c->e_chain, 0)); break; }

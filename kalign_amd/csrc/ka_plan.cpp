@@ -42,8 +42,8 @@ void build_blocks(const KaPlan* c, const std::vector<int>& L, std::vector<int2>&
 // The tasks a plan covers: all of them, or the subset of ka_tree_plan_tasks (a rank's subtrees of a sharded tree: closed under
 // descendants).  A task outside the plan is neither a parent nor a producer in it.
 static inline bool act(const KaPlan* p, int t) { return p->plan_active.empty() || p->plan_active[t] != 0; }
-// a task of the chained launch: at or above its first level, or on a spine that reaches down from it
-static inline bool in_chain(const KaPlan* p, int t) { return t >= 0 && act(p, t) && (p->task_level[t] >= p->chain_level || p->spine[t]); }
+// a task of the chained launch: a task of the plan at or above the chain's first level
+static inline bool in_chain(const KaPlan* p, int t) { return t >= 0 && act(p, t) && p->task_level[t] >= p->chain_level; }
 static bool all_seq_seq(const KaPlan* p, const std::vector<int>& L)
 {
         return std::all_of(L.begin(), L.end(), [&](int t) { return p->descs[t].nsip_a == 1 && p->descs[t].nsip_b == 1; });
@@ -61,7 +61,7 @@ struct PlanWork {
         std::vector<double> way_sqrt, way_11;
         int L0 = 0;                                  // the first level that is not all seq-seq (at most chain_level; 0 without a chain)
         std::vector<int> order, extra;               // the chain's entries in layout order; spare workgroups of each, beyond G0
-        int m = 0, G0 = 1, spare = 0, front_n = 0;   // entries per XCD column; workgroups every entry starts with; CUs still free; entries at the kept head
+        int m = 0, G0 = 1, spare = 0;                // entries per XCD column; workgroups every entry starts with; CUs still free
 };
 
 // parents (of the plan), roots (of the tree), trees
@@ -83,8 +83,8 @@ static void link_tasks(KaPlan* p, PlanWork& w)
         p->n_trees = numseq - n_tasks;
 }
 
-// The one estimator: lengths per node, ways to the root per task, both models, once per plan (the spine, queue-order, spare and
-// reserve steps read them), and with the lengths the tasks' wait_mult.  Every sum keeps its operand order -- the steps sort on these
+// The one estimator: lengths per node, ways to the root per task, both models, once per plan (the queue-order and spare
+// steps read them), and with the lengths the tasks' wait_mult.  Every sum keeps its operand order -- the steps sort on these
 // doubles, and the plans are pinned bit for bit (tests/test_plan_host.py).
 static void estimate(KaPlan* p, PlanWork& w)
 {
@@ -117,7 +117,7 @@ static void estimate(KaPlan* p, PlanWork& w)
 
 // The level from which the rest of the tree runs as ONE chained launch: the first non-leaf level with at most one task per CU (all
 // its workgroups resident at once; levels only get narrower above it).  KA_NO_CHAIN=1 keeps one launch per level.  And w.L0, the
-// first level below it that is not all seq-seq: where a queued launch would start, and how far down a spine reaches.
+// first level below it that is not all seq-seq: where a queued launch would start.
 static void place_chain(KaPlan* p, PlanWork& w)
 {
         p->chain_level = -1;
@@ -146,52 +146,6 @@ static void place_queue(KaPlan* p, const PlanWork& w)
         if ((int)p->plan_levels[w.L0].size() <= p->n_cus) return;               // (the queue's first level must fill the GPU; later ones need not)
         p->queue_first = w.L0;
         p->overlap_plan = (p->env.overlap > 0 && p->plan_active.empty() && !p->env.no_lean && !p->shared_gpu) ? p->env.overlap : 0;
-}
-
-// SPINES IN THE CHAIN (round 6; KA_SPINE = how many; built, bit-identical, measured, OFF: DESIGN 4j).  What the single tree waits for is not
-// a CU or an operand but the LATENCY of the tasks on its longest dependency chains (13.3 of 14.7 ms are the run times of 17
-// tasks, tools/levels_real.py) -- and the first four or five of those run in the queued launch: one four-wave workgroup,
-// ka_strip with its event steps, 0.54-0.72 ms for a 430 x 420 task that takes 0.33-0.45 ms in the chained launch (helper
-// strips, two workgroups).  So the chain reaches DOWN along the most critical entries: from each of the KA_SPINE entries of
-// the chain's first level with the longest estimated path through them (leaves .. entry .. root), the child with the later
-// estimated finish, and its child, ... down to the queue's first level are tasks of the chained launch too (p->spine):
-// the lowest one is an entry of its own (both children come from the leaf levels / the queue: done flags), the others
-// have ONE child inside the launch (chain_need 1) and one from the queue (qa / qb).  Nothing in the queue consumes a spine
-// task (its parent is the spine task above it), so the queue's order stays topological.
-// (the spines only exist beside an overlapping queued launch)
-static void mark_spines(KaPlan* p, const PlanWork& w)
-{
-        const int numseq = p->numseq, n_tasks = p->n_tasks;
-        const int* abc = p->abc.data();
-        p->spine.assign(n_tasks, 0);
-        const int K = p->env.spine;                       // (measured: 1 % at best with KA_RESERVE -- DESIGN 4j; off)
-        if (K <= 0 || p->queue_first < 0 || !p->overlap_plan || p->env.no_crit) return;
-        // (fin: when a node is ready if every task below it took its own wavefront steps, one after the other along the longest path --
-        // not the finish times of the greedy pass's simulated schedule, which knows about workgroups)
-        std::vector<double> fin(2 * numseq - 1, 0.0);
-        for (int t = 0; t < n_tasks; t++) {
-                const int a = abc[3 * t], b = abc[3 * t + 1], cc = abc[3 * t + 2];
-                const double dur = 2.0 * std::max(w.len_sqrt[a], w.len_sqrt[b]) + std::min(w.len_sqrt[a], w.len_sqrt[b]);
-                fin[cc] = std::max(fin[a], fin[b]) + dur;
-        }
-        std::vector<int> ent(p->plan_levels[p->chain_level].begin(), p->plan_levels[p->chain_level].end());
-        std::stable_sort(ent.begin(), ent.end(), [&](int x, int y) { return fin[abc[3 * x + 2]] + w.way_sqrt[x] > fin[abc[3 * y + 2]] + w.way_sqrt[y]; });
-        for (int e = 0; e < (int)ent.size() && e < K; e++) {
-                int cur = ent[e];
-                while (true) {
-                        int best = -1;
-                        for (int k = 0; k < 2; k++) {
-                                const int ch = abc[3 * cur + k];
-                                if (ch < numseq) continue;
-                                const int tc = w.task_of[ch];
-                                if (!act(p, tc) || p->task_level[tc] < w.L0 || p->task_level[tc] >= p->chain_level) continue;
-                                if (best < 0 || fin[ch] > fin[abc[3 * best + 2]]) best = tc;
-                        }
-                        if (best < 0) break;
-                        p->spine[best] = 1;
-                        cur = best;
-                }
-        }
 }
 
 // join counts of the chained launch: the children of a task that run inside it
@@ -271,21 +225,12 @@ static void order_queue(KaPlan* p, const PlanWork& w)
 {
         p->queue_off = (int)p->blocks_flat.size(); p->queue_n = 0;
         if (p->queue_first < 0) return;
-        const bool by_way = p->env.qorder != 0;
+        const bool by_way = p->env.qorder;
         auto longer_way = [&](int x, int y) { return by_way && w.way_sqrt[x] > w.way_sqrt[y]; };
-        // KA_QORDER=2, an experiment (round 6; measured and not kept): ONE order over all the queue's levels, by the way to the root alone.  A
-        // child's way is longer than its parent's, so the order is still topological (a producer is pulled before its consumer: no
-        // deadlock) -- the subtrees under the spine go first whatever their level, at the price of consumers pulled right behind
-        // their producers, whose workgroups then hold a slot and wait: the chain gains 0.3 ms, the queue loses 1.2 (headline
-        // 14.70 -> 15.45 ms, C3 70.0 -> 77.6, 16384 x 500 41.4 -> 45.7, sixteen trees unchanged; profiles/r06_queue_order.log).
-        const bool one_order = p->env.qorder == 2;
-        std::vector<int> run;
         for (int L = p->queue_first; L < p->chain_level; L++) {
-                for (int t : p->plan_levels[L]) if (!p->spine[t]) run.push_back(t);       // (the spines' tasks run in the chained launch)
-                if (one_order && L + 1 < p->chain_level) continue;
+                std::vector<int> run(p->plan_levels[L]);
                 std::stable_sort(run.begin(), run.end(), longer_way);
                 for (int t : run) { p->blocks_flat.push_back(make_int2(t, 1 << 8)); p->queue_n++; }
-                run.clear();
         }
 }
 
@@ -299,8 +244,8 @@ static void enter_chain(const KaPlan* p, PlanWork& w)
         for (int t = p->n_tasks - 1; t >= 0; t--) if (act(p, t) && p->descs[t].parent < 0 && p->task_level[t] >= p->chain_level) stack.push_back(t);   // every root above the cut
         while (!stack.empty()) {
                 const int t = stack.back(); stack.pop_back();
-                // an entry of the chain: no child of it runs inside the launch (the chain's first level -- unless a spine hangs below
-                // it --, the lowest task of a spine; in a plan over a subset also a task whose children were all run before)
+                // an entry of the chain: no child of it runs inside the launch (the chain's first level; in a plan over a subset also
+                // a task whose children were all run before)
                 if (p->descs[t].chain_need == 0) { w.order.push_back(t); continue; }
                 for (int k = 1; k >= 0; k--) {
                         const int ch = p->abc[3 * t + k];
@@ -338,7 +283,7 @@ static void spare_by_simulation(const KaPlan* p, PlanWork& w, const std::vector<
         for (size_t r = 0; r < w.order.size(); r++) entry_of[w.order[r]] = (int)r;
         std::vector<double> fin(n_tasks, 0.0);
         std::vector<int> Gt(n_tasks, 0), crit_child(n_tasks, -1);
-        const double ba = 1e-3 * (double)p->env.crit_ba;   // (b / a of the model, per mille; 10 from a sweep over five job shapes, profiles/r04_crit_ba.log)
+        const double ba = 0.01;                              // (b / a of the model: from a sweep over five job shapes, profiles/r04_crit_ba.log)
         auto simulate = [&]() -> int {
                 int last = -1;
                 for (int t = 0; t < n_tasks; t++) {                  // children come before their parents
@@ -432,46 +377,6 @@ static void give_spare_workgroups(const KaPlan* p, PlanWork& w)
         spare_by_ranking(p, w, len, up);
 }
 
-// CUs KEPT FOR THE HEAD OF THE CHAIN (round 6; KA_RESERVE = 8 / 16 / 24; built, measured, OFF: the spine then starts 1 ms earlier and the run is as long -- other chains of the same length take over).  The chained launch goes out beside the
-// queued one, but a workgroup of it wants a CU's whole LDS and the queue's 512 persistent workgroups hold two to a CU until
-// their list is empty: the chain only ever started when the queue was over (the spine's first chained task of the headline
-// tree waited 1.0 ms for a CU for its cluster's second workgroup; tools/levels_real.py, `prep`).  Now the queue's workgroups
-// that find themselves on the first R CUs of XCC 0 (shader engines 0 .. R/8 - 1; ka_task_queue_entry reads HW_ID / XCC_ID)
-// leave at once, and the chain's most critical entries -- by their estimated way to the root, all their workgroups, as
-// many as fit R -- sit at the head of column 0 of the block table: block b goes to XCC b % 8 (tools/microbench/cu_map.hip:
-// 0 exceptions in 512), XCC 0 dispatches its share of the chain in order onto the CUs the queue left, and those
-// workgroups wait for their operands' done flags instead of for a CU (they do not help the queue: KA_BLK_NOHELP).
-// This step picks the front entries and moves them to the head of the order (it also trims the spare workgroups of spine entries,
-// so it runs before the layout); lay_out_chain puts their workgroups at the head of column 0.
-static void reserve_front(KaPlan* p, PlanWork& w)
-{
-        p->reserve_cus = 0;
-        w.front_n = 0;
-        const int R = p->env.reserve;                     // (measured: no gain -- DESIGN 4j; off)
-        if (R <= 0 || !p->overlap_plan || p->queue_first < 0 || p->n_trees > 1 || !p->plan_active.empty() || (int)w.order.size() <= 8 || p->env.no_crit) return;
-        std::vector<double> crit(w.way_sqrt);
-        std::vector<int> idx(w.order.size());
-        for (size_t r = 0; r < w.order.size(); r++) idx[r] = (int)r;
-        // (the lowest tasks of the spines first: they are what the kept CUs are for; a 430-row task uses two workgroups)
-        for (size_t r = 0; r < w.order.size(); r++) if (p->task_level[w.order[r]] < p->chain_level) { crit[w.order[r]] += 1e12; w.extra[r] = std::min(w.extra[r], 1); }
-        std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return crit[w.order[x]] > crit[w.order[y]]; });
-        std::vector<char> is_front(w.order.size(), 0);
-        std::vector<int> front;
-        int used = 0;
-        for (int r : idx) {
-                const int Gr = w.G0 + w.extra[r];
-                if (used + Gr > R || (int)front.size() + 1 > w.m) break;
-                front.push_back(r); is_front[r] = 1; used += Gr;
-        }
-        if (front.empty()) return;
-        std::vector<int> o2, e2;
-        for (int r : front) { o2.push_back(w.order[r]); e2.push_back(w.extra[r]); }
-        for (size_t r = 0; r < w.order.size(); r++) if (!is_front[r]) { o2.push_back(w.order[r]); e2.push_back(w.extra[r]); }
-        w.order.swap(o2); w.extra.swap(e2);
-        w.front_n = (int)front.size();
-        p->reserve_cus = R;
-}
-
 // the chained launch's block table: 8 XCD columns of m entries with G0 workgroups each, the spare workgroups behind them
 static void lay_out_chain(KaPlan* p, PlanWork& w)
 {
@@ -494,27 +399,6 @@ static void lay_out_chain(KaPlan* p, PlanWork& w)
                         p->chain_blocks[pos] = make_int2(w.order[r], g | (Gr << 8));
                 }
         }
-        if (w.front_n > 0) {
-                // The front entries' workgroups -- ALL of them: their extra members sit behind the regular table, in whatever column --
-                // trade places with what the head of column 0 holds (a swap: every column keeps its number of workgroups, and with it
-                // the guarantee that the whole launch is resident at once).
-                std::vector<size_t> col0;
-                for (size_t q = 0; q < p->chain_blocks.size(); q += 8) if (p->chain_blocks[q].x >= 0) col0.push_back(q);
-                size_t i = 0;
-                bool ok = true;
-                for (int r = 0; r < w.front_n && ok; r++)
-                        for (int g = 0; g < G0 + w.extra[r] && ok; g++, i++) {
-                                size_t src = p->chain_blocks.size();
-                                for (size_t q = 0; q < p->chain_blocks.size(); q++)
-                                        if (p->chain_blocks[q].x == w.order[r] && (p->chain_blocks[q].y & 0xff) == g) { src = q; break; }
-                                if (src == p->chain_blocks.size() || i >= col0.size()) { ok = false; break; }
-                                std::swap(p->chain_blocks[col0[i]], p->chain_blocks[src]);
-                                p->chain_blocks[col0[i]].y |= KA_BLK_NOHELP;
-                        }
-                if (!ok) { p->reserve_cus = 0; for (auto& bb : p->chain_blocks) if (bb.x >= 0) bb.y &= ~KA_BLK_NOHELP; }
-        }
-        if (p->env.plan_verbose) fprintf(stderr, "chain plan: %d CUs kept for the head of the chain, %d front entries, m %d, G0 %d, by_column %d, overlap %d, queue_first %d\n",
-                                         p->reserve_cus, w.front_n, m, G0, (int)by_column, p->overlap_plan, p->queue_first);
         p->chain_blocks_off = (int)p->blocks_flat.size();
         p->blocks_flat.insert(p->blocks_flat.end(), p->chain_blocks.begin(), p->chain_blocks.end());
 }
@@ -531,7 +415,6 @@ int plan_launches(KaPlan* p)
         // which launches there are
         place_chain(p, w);
         place_queue(p, w);
-        mark_spines(p, w);
         set_chain_need(p, w);
         set_queue_deps(p, w);
         // their workgroup tables: one per level, the queue's list, the chain's table
@@ -541,7 +424,6 @@ int plan_launches(KaPlan* p)
         if (p->chain_level >= 0) {
                 enter_chain(p, w);
                 give_spare_workgroups(p, w);
-                reserve_front(p, w);                      // (trims the spare workgroups of spine entries: before the layout)
                 lay_out_chain(p, w);
         }
         return KA_OK;
@@ -761,13 +643,13 @@ static int export_plan(const KaPlan* p, int* scalars, int* per_task, int* blocks
         const int n = p->n_tasks, levels = (int)p->plan_levels.size(), n_blocks = (int)p->blocks_flat.size();
         const bool chain = p->chain_level >= 0;
         const int sc[16] = { levels, n_blocks, p->max_cluster, p->n_trees, p->chain_level, p->queue_first, p->queue_off, p->queue_n, p->overlap_plan,
-                             p->reserve_cus, chain ? p->chain_blocks_off : 0, chain ? (int)p->chain_blocks.size() : 0, 0, 0, 0, 0 };
+                             chain ? p->chain_blocks_off : 0, chain ? (int)p->chain_blocks.size() : 0, 0, 0, 0, 0, 0 };
         memcpy(scalars, sc, sizeof(sc));
         if (n_blocks > blocks_cap) return fail("ka_debug_plan: the block table needs more room (scalars[1] entries)");
         for (int t = 0; t < n; t++) {
                 const KaTaskDesc& d = p->descs[t];
-                const int v[7] = { d.parent, d.chain_need, d.is_root, d.wait_mult, d.qa, d.qb, (int)p->spine[t] };
-                for (int k = 0; k < 7; k++) per_task[(size_t)k * n + t] = v[k];
+                const int v[6] = { d.parent, d.chain_need, d.is_root, d.wait_mult, d.qa, d.qb };
+                for (int k = 0; k < 6; k++) per_task[(size_t)k * n + t] = v[k];
         }
         for (int i = 0; i < n_blocks; i++) { blocks[2 * i] = p->blocks_flat[i].x; blocks[2 * i + 1] = p->blocks_flat[i].y; }
         for (int L = 0; L <= levels; L++) blocks_off[L] = p->blocks_off[L];

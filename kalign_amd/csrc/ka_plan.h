@@ -39,11 +39,7 @@ struct KaEnv {
         int qw = 4, lw = 4, pw = 2;    // KA_QW / KA_LW / KA_PW: waves per workgroup of the queued launch, the seq-seq leaf levels, the pair batch (4, 2, 1)
         bool launch_ev = false;        // KA_LAUNCH_EV: an event behind every launch of a run (ka_tree_launch_ms)
         bool upgma_launches = false;   // KA_UPGMA_LAUNCHES: ka_aln_guide_tree's UPGMA as one launch per merge (the path for > 6144 sequences) at any size
-        // the planner's round-6 experiments (all measured, all off: DESIGN 4j)
-        int spine = 0;                 // KA_SPINE: how many of the chain's most critical entries reach down into the queue's levels (0: none)
-        int reserve = 0;               // KA_RESERVE: CUs of XCC 0 the queued launch leaves to the head of the chain (0 / 8 / 16 / 24)
-        int qorder = 1;                // KA_QORDER: the queue's order -- 0 list order, 1 per level by the way to the root, 2 one order over all its levels
-        int crit_ba = 10;              // KA_CRIT_BA: b / a of the greedy pass's task model, per mille
+        bool qorder = true;            // KA_QORDER: the queue's order -- 0 list order, anything else per level by the way to the root
         bool plan_verbose = false;     // KA_PLAN_VERBOSE: the chained launch's plan on stderr
 };
 static inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
@@ -70,10 +66,7 @@ static inline void read_env(KaEnv& v)
         v.hw = env_int("KA_HW", 1);
         v.hw_prio = std::max(0, std::min(3, env_int("KA_HW_PRIO", 3)));
         v.upgma_launches = getenv("KA_UPGMA_LAUNCHES") != nullptr;
-        v.spine = env_int("KA_SPINE", 0);
-        v.reserve = std::max(0, std::min(24, env_int("KA_RESERVE", 0) / 8 * 8));
-        v.qorder = env_int("KA_QORDER", 1);
-        v.crit_ba = env_int("KA_CRIT_BA", 10);
+        v.qorder = env_int("KA_QORDER", 1) != 0;
         v.plan_verbose = getenv("KA_PLAN_VERBOSE") != nullptr;
 }
 
@@ -105,8 +98,6 @@ struct KaPlan {
         int queue_first = -1;          // queued launch: levels queue_first .. chain_level-1 run as ONE launch of the half kernel (-1: none)
         int queue_off = 0, queue_n = 0; // its task list in blocks_flat
         int overlap_plan = 0;          // the plan carries the dependencies for overlapping launches (KA_OVERLAP)
-        std::vector<char> spine;       // round 6: tasks below the chain's first level that run in the chained launch all the same (plan_launches)
-        int reserve_cus = 0;           // round 6: CUs of XCC 0 the queued launch leaves to the head of the chained launch (plan_launches; 0: none)
         std::vector<int2> chain_blocks;
         int chain_blocks_off = 0;
 };

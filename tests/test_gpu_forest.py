@@ -1,7 +1,6 @@
 """Launches of the 4-wave kind (unit 2 of kalign_amd/csrc/ka_kernels.hip: two workgroups per CU).  A launch takes that kernel when
 a guide-tree level has more tasks than the GPU has CUs: forests of the reference's goldens (every copy must come out as the golden
-does: aln_seqseq.c / aln_seqprofile.c / aln_profileprofile.c through the Hirschberg recursion of aln_controller.c, bit for bit).
-And the planner experiments of round 6, which change who runs when and must not change the alignment."""
+does: aln_seqseq.c / aln_seqprofile.c / aln_profileprofile.c through the Hirschberg recursion of aln_controller.c, bit for bit)."""
 import numpy as np
 import pytest
 
@@ -46,29 +45,3 @@ def test_forest_of_goldens(name):
     finally:
         ctx.close()
 
-
-@pytest.mark.parametrize("switches", [{"KA_SPINE": "8", "KA_RESERVE": "16"}, {"KA_SPINE": "3"}, {"KA_RESERVE": "24"}, {"KA_QORDER": "2"},
-                                      {"KA_SPINE": "6", "KA_RESERVE": "8"}])
-def test_round6_schedule_experiments_give_the_same_alignment(switches, monkeypatch):
-    """the planner experiments of round 6 (all off by default): the most critical entries' spines as tasks of the chained
-    launch (chain_need 1 + a done flag from the queue), CUs of XCC 0 that the queued launch leaves to the head of the chain, one
-    order over all the queue's levels -- WHO runs WHEN changes, the alignment must not, and no run may fall back"""
-    import bench
-    import kalign_amd
-    codes, tasks, dist = bench.make_workload(2560, 300, False, 5)
-    subm, scal = bench.scoring(False)
-    ctx = kalign_amd.Context(0)
-    try:
-        want = ctx.msa_tree(codes, tasks, subm, scal, dist)
-        for k, v in switches.items():
-            monkeypatch.setenv(k, v)
-        ctx.reload_env()
-        for _ in range(2):
-            got = ctx.msa_tree(codes, tasks, subm, scal, dist)
-            assert ctx.fallback_runs() == 0
-            assert [(r.plen, r.meet, r.transition, r.score) for r in got[0]] == [(r.plen, r.meet, r.transition, r.score) for r in want[0]]
-            assert np.array_equal(got[1], want[1])
-            for a, b in zip(got[2], want[2]):
-                assert np.array_equal(a, b)
-    finally:
-        ctx.close()

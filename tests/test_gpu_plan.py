@@ -34,13 +34,17 @@ def test_context_holds_the_plan_the_host_makes(monkeypatch):
             job = mp.case_inputs(name)
             lens, tasks = job["lens"], job["tasks"]
             codes = [np.zeros(n, np.uint8) for n in lens]
-            monkeypatch.delenv("KA_SPINE", raising=False)
+            monkeypatch.delenv("KA_NO_QUEUE", raising=False)
             ctx.reload_env()
             ctx.tree_upload(codes, tasks, subm, scal, None)
-            assert same(ctx.debug_plan(n_cus), api.debug_plan(lens, tasks, n_cus)), name
-            monkeypatch.setenv("KA_SPINE", "3")
+            default = ctx.debug_plan(n_cus)
+            assert same(default, api.debug_plan(lens, tasks, n_cus)), name
+            monkeypatch.setenv("KA_NO_QUEUE", "1")
             ctx.reload_env()
-            assert same(ctx.debug_plan(n_cus), api.debug_plan(lens, tasks, n_cus)), name
+            flipped = ctx.debug_plan(n_cus)
+            assert same(flipped, api.debug_plan(lens, tasks, n_cus)), name
+            if name == "c":                                  # (the switch takes the queued launch out of the plan)
+                assert default["queue_first"] >= 0 and flipped["queue_first"] == -1
             ids = mp.case_inputs("i")["task_ids"] if name == "c" else np.flatnonzero(tasks[:, 2] < tasks[len(tasks) // 2, 2])
             ctx.tree_plan_tasks(ids)
             assert same(ctx.debug_plan(n_cus), api.debug_plan(lens, tasks, n_cus, task_ids=ids)), name

@@ -33,7 +33,7 @@ def file_of(name):
 def test_names_and_abi_version():
     from kalign_amd import api
     L = api.load_library()
-    assert L.ka_abi_version() >= 15
+    assert L.ka_abi_version() >= 27
     for name in ("ka_debug_plan", "ka_debug_ctx_plan"):
         assert name in api.EXPORTS and hasattr(L, name), name
 
@@ -61,7 +61,8 @@ def check_invariants(job, plan):
     if job["task_ids"] is not None:
         active[:] = False
         active[job["task_ids"]] = True
-    in_chain = active & ((levels_of(job) >= plan["chain_level"]) | (plan["spine"] != 0))
+    level = levels_of(job)
+    in_chain = active & (level >= plan["chain_level"])
     task_of = {int(c): t for t, (_, _, c) in enumerate(tasks)}
     # join counts: the children that run inside the launch (plus the one that never comes, under the starve hook)
     need = np.zeros(n_tasks, np.int64)
@@ -87,9 +88,15 @@ def check_invariants(job, plan):
             assert t < 0 or in_chain[t]
     assert np.array_equal(reached, in_chain)
     assert len(t_blk) <= job["n_cus"]                                         # resident at once
-    # the queued launch: no spine task, producers before consumers
+    # no flag bits in the block table: a workgroup's second word is member | cluster size << 8
+    assert (plan["blocks"][plan["blocks"][:, 0] >= 0, 1] < (1 << 16)).all()
+    # the queued launch: exactly the plan's tasks of levels queue_first .. chain_level - 1, each once, producers before consumers
     q = plan["blocks"][plan["queue_off"]:plan["queue_off"] + plan["queue_n"], 0]
-    assert len(set(q.tolist())) == len(q) and not plan["spine"][q].any()
+    if plan["queue_first"] >= 0:
+        queued = np.flatnonzero(active & (level >= plan["queue_first"]) & (level < plan["chain_level"]))
+        assert sorted(q.tolist()) == queued.tolist()
+    else:
+        assert len(q) == 0
     pos = {int(t): i for i, t in enumerate(q)}
     for i, t in enumerate(q):
         for p in (int(plan["qa"][t]), int(plan["qb"][t])):
