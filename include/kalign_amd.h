@@ -967,6 +967,103 @@ long long ka_sum_fam_ungapped_size(ka_sum_fam* h);
 int  ka_sum_fam_ungapped(ka_sum_fam* h, uint8_t* out, long long cap, long long* row_off_out);
 int  ka_sum_fam_gap_stats(ka_sum_fam* h, double* out6);
 
+/*
+ * The input stage (ABI 28): a batch of families from raw text to the three encodings ka_run_encoded_batch takes, and from
+ * there to rows in the caller's order.  What the reference does at its front door, per family:
+ *   msa_io.c:454-468          "msa->letter_freq[(int)line[i]]++; if(isalpha((int)line[i])){ ... seq_ptr->seq[seq_ptr->len] =
+ *                             line[i]; seq_ptr->len++; ... }else if(ispunct((int)line[i])){ seq_ptr->gaps[seq_ptr->len]++; }"
+ *   msa_op.c:142-213          detect_alphabet: "DNA[i] = log(0.0001 * 1.0 / 116.0); protein[i] = log(0.0001 * 1.0 / 88.0);",
+ *                             "acgtunACGTUN" at log(0.9999 * 1.0 / 12.0), "acdefghiklmnpqrstvwyACDEFGHIKLMNPQRSTVWY" at
+ *                             log(0.9999 * 1.0 / 40.0); "if(msa->letter_freq[i]){ dna_prob += DNA[i] * (double)
+ *                             msa->letter_freq[i]; prot_prob += protein[i]* (double) msa->letter_freq[i]; }"
+ *   msa_op.c:215-271          detect_aligned: "if(gaps){ if(min_len == max_len){ msa->aligned = ALN_STATUS_ALIGNED; }else{ ...
+ *                             ALN_STATUS_UNKNOWN; } }else{ if(min_len == max_len){ ... ALN_STATUS_UNKNOWN; }else{ ...
+ *                             ALN_STATUS_UNALIGNED; } }" (msa_struct.h:14-17: UNALIGNED 1, ALIGNED 2, UNKNOWN 3)
+ *   aln_wrap.c:146-149        "if(msa->aligned != ALN_STATUS_UNALIGNED){ RUN(dealign_msa(msa)); }"
+ *   msa_sort.c:62-80          sort_by_len_name: "if((*one)->len > (*two)->len){ return -1; }else if((*one)->len ==
+ *                             (*two)->len){ int c = strncmp((*one)->name, (*two)->name, MSA_NAME_LEN); if(c < 0){ return -1;
+ *                             }else{ return 1; } }else{ return 1; }"
+ *   msa_op.c:358-364          convert_msa_to_internal: "if(t[(int) seq->seq[j]] == -1){ WARNING_MSG(...); seq->s[j] = 0; }"
+ *   msa_check.c:301-310       GCGchecksum: "chk = (chk + (i % 57 + 1) * (toupper((int) seq[i]))) % 10000;"
+ *   alphabet.c:179-302, 399-430  create_protein_BZX, create_default_DNA, create_reduced_protein, clean_and_set_to_extern
+ *   A byte     b < 128 is a residue when it is a letter (A-Z, a-z; kept as given, case included), a gap character when it
+ *              is punctuation (33-47, 58-64, 91-96, 123-126), and is dropped otherwise (white space, digits, control bytes).
+ *              A byte >= 128 is an error: the reference indexes letter_freq with it, which is undefined.  Gap characters
+ *              are always discarded -- an input with one is never UNALIGNED, and everything else is dealigned -- but they
+ *              are counted, for the aligned status and the histogram.
+ *   Text       text holds the sequences' raw bytes; sequence i of the batch is text[seq_off[i] .. seq_off[i + 1]), seq_off
+ *              [numseq + 1] ascends from 0, a sequence holds fewer than 2^31 bytes.  fam_first[n_fam + 1] as everywhere; a
+ *              family has one sequence at least.  names / name_off[numseq + 1] the same way, or both NULL: no names.
+ *   Histogram  freq[128] per family counts every byte handed in, punctuation and dropped bytes included.
+ *   Biotype    per family, 0 protein, 1 DNA: biotype_in[f] when that is 0 or 1 (biotype_in NULL or -1: detect).  Detection
+ *              is detect_alphabet on the host from the device's integer histogram: two sums in double over i = 0..127 in
+ *              ascending order, zero counts skipped; > gives DNA, < protein, equality is an error for that family.
+ *   Status     per family 1 unaligned, 2 aligned, 3 unknown, from residues + gap characters per sequence.  Reported only.
+ *   Order      per family: more residues first; ties by strncmp of the names over 256 bytes; without names, and for equal
+ *              names, by input index (the reference's comparator is inconsistent for equal names; this defines what it
+ *              leaves open, and is what its library entry gets from the "s%07d" names it makes up).
+ *   Codes      three tables of 128 entries: nucleotides (both planes of a DNA family), the reduced protein alphabet (tree
+ *              plane of a protein family), the protein alphabet with B Z X (its alignment plane); lower case = upper case;
+ *              -1 = no code.  A letter with no code becomes code 0 and is counted per family.  The two protein tables give
+ *              a code to the same letters.
+ *   Checksum   per sequence, GCGchecksum over the residues as kept.
+ *   A sequence with no residue is an error naming family and sequence.  The reference drops such sequences
+ *   (msa_check.c:82-133); a batch whose rows silently go missing is worse than a refusal.
+ *
+ * Host only (no context, no GPU):
+ *   ka_in_tables     out3x128: nucleotides, reduced protein, protein, in this order.
+ *   ka_in_detect     biotype_out from freq128, or "ka_in_detect: could not determine the alphabet".
+ *   ka_in_order      order_out[numseq]: sorted position -> input index, batch-wide (family f's positions are fam_first[f] ..
+ *                    fam_first[f + 1] - 1); names / name_off may be NULL.
+ *   ka_in_fam_check  "ka_in_fam_check: fam_first does not ascend from 0 to numseq", "ka_in_fam_check: empty family",
+ *                    "ka_in_fam_check: seq_off does not ascend from 0 to n_bytes", "ka_in_fam_check: family 0, sequence 1:
+ *                    2147483648 bytes; a sequence holds fewer than 2^31".
+ * The stage:
+ *   ka_in_fam_create runs the check, uploads the text in one copy and launches twice: the scan (counts, checksums, first
+ *                    byte >= 128, histograms), then -- after detection, status, order and offsets on the host -- the encode
+ *                    (three planes in sorted order).  Two launches and two host synchronisations (the host needs the counts,
+ *                    then the planes), whatever the batch.  Fails naming the cause: the check's messages, "ka_in_fam_create:
+ *                    family 1, sequence 0: byte 0xc3 at offset 5" (the first offender in batch order; sequence numbers are
+ *                    within the family, offsets within the sequence's raw bytes), "ka_in_fam_create: family 1, sequence 2
+ *                    has no residue", "ka_in_fam_create: family 0: could not determine the alphabet".  Runs on ctx's device
+ *                    and stream: destroy it before ctx.
+ *   ka_in_fam_sequences  recs_out[numseq * 4] in input order: residues, gap characters, dropped bytes, checksum.
+ *   ka_in_fam_families   recs_out[n_fam * 5]: biotype, aligned status, min and max residues, letters without a code;
+ *                    freq_out[n_fam * 128] (may be NULL).
+ *   ka_in_fam_order  order_out[numseq] as ka_in_order.
+ *   ka_in_fam_size   residues of the batch (the bytes of each plane).
+ *   ka_in_fam_encoded  the three planes, off[numseq] and lens[numseq] in sorted order, as ka_run_encoded_batch takes them
+ *                    (each optional; refused when the batch holds 2^31 residues or more).
+ *   ka_in_fam_run    aligns the families whose biotype is `biotype` with that biotype's subm / scal: their planes go to the
+ *                    path ka_run_encoded_batch runs (no noisy trees), so each family comes out as ka_run_encoded_refine
+ *                    aligns it alone, and their rows are kept in the handle in INPUT order.  A second call with the other
+ *                    biotype adds the remaining families; a call for a biotype no family has does nothing.  The context's
+ *                    own batch rows (ka_batch_rows) are replaced, as by any ka_run_encoded_batch.
+ *   ka_in_fam_rows_size / ka_in_fam_rows  packed as ka_batch_rows packs them, rows in input order; alnlens_out[n_fam]
+ *                    (optional).  While a family is missing: -1 / "ka_in_fam_rows: family 2 has not been run
+ *                    (ka_in_fam_run with biotype 1)".
+ *   ka_in_fam_stats  out[6]: device ms of the scan [0] and of the encode [1]; kernel launches [2] and host synchronisations
+ *                    [3] of create (2 and 2); raw bytes of the batch [4]; wall ms of the ka_in_fam_run calls so far [5].
+ */
+typedef struct ka_in_fam ka_in_fam;
+int  ka_in_tables(int8_t* out3x128);
+int  ka_in_detect(const long long* freq128, int* biotype_out);
+int  ka_in_order(int n_fam, const int* fam_first, const int* residues, const uint8_t* names, const long long* name_off, int* order_out);
+int  ka_in_fam_check(int n_fam, const int* fam_first, const long long* seq_off, long long n_bytes);
+int  ka_in_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, const uint8_t* text, const long long* seq_off,
+                      const uint8_t* names, const long long* name_off, const int* biotype_in, ka_in_fam** out);
+void ka_in_fam_destroy(ka_in_fam* h);
+int  ka_in_fam_sequences(ka_in_fam* h, int* recs_out);
+int  ka_in_fam_families(ka_in_fam* h, int* recs_out, long long* freq_out);
+int  ka_in_fam_order(ka_in_fam* h, int* order_out);
+long long ka_in_fam_size(ka_in_fam* h);
+int  ka_in_fam_encoded(ka_in_fam* h, uint8_t* tree_codes, uint8_t* codes, uint8_t* letters, int* off, int* lens);
+int  ka_in_fam_run(ka_in_fam* h, int biotype, const float* subm, const float* scal, int n_anchors, float weight,
+                   int realign_iterations, int n_threads, int refine_mode, uint8_t gap_char);
+long long ka_in_fam_rows_size(ka_in_fam* h);
+int  ka_in_fam_rows(ka_in_fam* h, uint8_t* out, long long cap, int* alnlens_out);
+int  ka_in_fam_stats(ka_in_fam* h, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,7 +70,10 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_sum_fam_identity_entries", "ka_sum_fam_identity", "ka_sum_fam_identity_stats",
            "ka_sum_fam_gaps", "ka_sum_fam_gap_values", "ka_sum_fam_ungapped_size", "ka_sum_fam_ungapped", "ka_sum_fam_gap_stats",
            "ka_guide_forest_from", "ka_guide_forest", "ka_aln_guide_forest", "ka_run_encoded_batch", "ka_batch_rows_size", "ka_batch_rows",
-           "ka_batch_stats", "ka_batch_refine_stats"]
+           "ka_batch_stats", "ka_batch_refine_stats",
+           "ka_in_tables", "ka_in_detect", "ka_in_order", "ka_in_fam_check", "ka_in_fam_create", "ka_in_fam_destroy", "ka_in_fam_sequences",
+           "ka_in_fam_families", "ka_in_fam_order", "ka_in_fam_size", "ka_in_fam_encoded", "ka_in_fam_run", "ka_in_fam_rows_size",
+           "ka_in_fam_rows", "ka_in_fam_stats"]
 
 
 def lib_path():
@@ -282,6 +285,24 @@ def load_library():
     L.ka_sum_fam_ungapped_size.restype = C.c_longlong
     L.ka_sum_fam_ungapped.argtypes = [vp, vp, C.c_longlong, vp]
     L.ka_sum_fam_gap_stats.argtypes = [vp, vp]
+    L.ka_in_tables.argtypes = [vp]
+    L.ka_in_detect.argtypes = [vp, C.POINTER(C.c_int)]
+    L.ka_in_order.argtypes = [C.c_int, vp, vp, vp, vp, vp]
+    L.ka_in_fam_check.argtypes = [C.c_int, vp, vp, C.c_longlong]
+    L.ka_in_fam_create.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
+    L.ka_in_fam_destroy.argtypes = [vp]
+    L.ka_in_fam_destroy.restype = None
+    L.ka_in_fam_sequences.argtypes = [vp, vp]
+    L.ka_in_fam_families.argtypes = [vp, vp, vp]
+    L.ka_in_fam_order.argtypes = [vp, vp]
+    L.ka_in_fam_size.argtypes = [vp]
+    L.ka_in_fam_size.restype = C.c_longlong
+    L.ka_in_fam_encoded.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ka_in_fam_run.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_ubyte]
+    L.ka_in_fam_rows_size.argtypes = [vp]
+    L.ka_in_fam_rows_size.restype = C.c_longlong
+    L.ka_in_fam_rows.argtypes = [vp, vp, C.c_longlong, vp]
+    L.ka_in_fam_stats.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -1754,6 +1775,178 @@ def _sum_fam_create(self, families_rows, gap=b"-"):
 
 
 Context.family_summary = _sum_fam_create
+
+
+IN_SEQ = ("residues", "gap_characters", "dropped", "checksum")
+IN_FAM = ("biotype", "aligned", "min_len", "max_len", "no_code")
+IN_STATS = ("scan_ms", "encode_ms", "launches", "syncs", "bytes", "run_wall_ms")
+IN_TABLES = ("nucleotide", "reduced_protein", "protein")
+
+
+def _pack_text(seqs):
+    """a flat list of bytes -> (uint8 text, int64 offsets [n + 1])"""
+    off = np.zeros(len(seqs) + 1, np.int64)
+    off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.int64)
+    text = np.frombuffer(b"".join(seqs), np.uint8)
+    return (np.ascontiguousarray(text) if len(text) else np.zeros(1, np.uint8)), off
+
+
+def _raw(s):
+    """a sequence or a name as bytes: a str is its latin-1 bytes, one per character (a character past 255 is refused)"""
+    try:
+        return s.encode("latin-1") if isinstance(s, str) else bytes(s)
+    except UnicodeEncodeError as e:
+        raise KalignAmdError("a sequence holds a character that is no byte: %s" % e)
+
+
+def input_tables():
+    """ka_in_tables (no GPU): int8 [3, 128] -- nucleotides, reduced protein, protein (IN_TABLES); -1: no code"""
+    L = load_library()
+    t = np.zeros((3, 128), np.int8)
+    if L.ka_in_tables(_ptr(t)) != 0:
+        raise KalignAmdError(L.ka_last_error().decode())
+    return t
+
+
+def input_detect(freq):
+    """ka_in_detect (no GPU): the biotype (0 protein, 1 DNA) of a 128-bin byte histogram"""
+    L = load_library()
+    f = np.ascontiguousarray(freq, np.int64)
+    if f.shape != (128,):
+        raise KalignAmdError("input_detect: a histogram has 128 bins")
+    out = C.c_int(-1)
+    if L.ka_in_detect(_ptr(f), C.byref(out)) != 0:
+        raise KalignAmdError(L.ka_last_error().decode())
+    return out.value
+
+
+def input_order(sizes, residues, names=None):
+    """ka_in_order (no GPU): sorted position -> input index, batch-wide, for families of `sizes` sequences with `residues`
+    letters each; names: a flat list (bytes / str), one per sequence, or None"""
+    L = load_library()
+    first = _fam_first(sizes)
+    res = np.ascontiguousarray(residues, np.int32)
+    if len(res) != int(first[-1]) or (names is not None and len(names) != len(res)):
+        raise KalignAmdError("input_order: one residue count (and one name) per sequence")
+    nm, noff = _pack_text([_raw(x) for x in names]) if names is not None else (None, None)
+    out = np.zeros(max(len(res), 1), np.int32)
+    if L.ka_in_order(len(sizes), _ptr(first), _ptr(res), _ptr(nm), _ptr(noff), _ptr(out)) != 0:
+        raise KalignAmdError(L.ka_last_error().decode())
+    return out[:len(res)]
+
+
+class FamilyInput(_CtxChild):
+    """A batch of families from raw text (ka_in_fam): families is a list of lists of sequences (bytes / str) as a user has
+    them -- mixed case, ambiguity codes, possibly aligned already.  Letters are residues, punctuation is gap characters (counted,
+    then discarded), everything else below 128 is dropped; a byte >= 128 or a sequence without a letter is refused.  names: a
+    list of lists like families, or None; biotype: None (detect every family), one value or one per family (-1: detect)."""
+    _destroy = "ka_in_fam_destroy"
+
+    def __init__(self, ctx, families, names=None, biotype=None):
+        self.ctx, self.L = ctx, ctx.L
+        if not ctx.h:
+            raise KalignAmdError("the context is closed")
+        fams = [[_raw(s) for s in f] for f in families]
+        if not fams:
+            raise KalignAmdError("a family input needs a family")
+        self.sizes = [len(f) for f in fams]
+        self.first = _fam_first(self.sizes)
+        text, off = _pack_text([s for f in fams for s in f])
+        nm = noff = None
+        if names is not None:
+            if [len(f) for f in names] != self.sizes:
+                raise KalignAmdError("one name per sequence")
+            nm, noff = _pack_text([_raw(x) for f in names for x in f])
+        bt = None
+        if biotype is not None:
+            bt = np.ascontiguousarray(np.broadcast_to(np.asarray(biotype, np.int32), (len(fams),)))
+        h = C.c_void_p()
+        ctx._chk(self.L.ka_in_fam_create(ctx.h, len(fams), _ptr(self.first), _ptr(text), _ptr(off), _ptr(nm), _ptr(noff), _ptr(bt), C.byref(h)))
+        self._adopt(ctx, h)
+        self.n = int(self.first[-1])
+
+    def _open(self):
+        if not self.h:
+            raise KalignAmdError("the family input is closed")
+        return len(self.sizes)
+
+    def _per_family(self, a):
+        return [a[self.first[f]:self.first[f + 1]] for f in range(len(self.sizes))]
+
+    def sequences(self):
+        """per family an int32 array [n_f, 4] in input order: residues, gap characters, dropped bytes, checksum (IN_SEQ)"""
+        self._open()
+        recs = np.zeros((max(self.n, 1), len(IN_SEQ)), np.int32)
+        self.ctx._chk(self.L.ka_in_fam_sequences(self.h, _ptr(recs)))
+        return self._per_family(recs[:self.n])
+
+    def families(self, want_freq=False):
+        """per family a dict of IN_FAM: biotype (0 protein, 1 DNA), aligned (1 unaligned, 2 aligned, 3 unknown), min_len,
+        max_len, no_code (letters without a code); want_freq: also freq, the int64 histogram of its 128 byte values"""
+        F = self._open()
+        recs, freq = np.zeros((F, len(IN_FAM)), np.int32), np.zeros((F, 128), np.int64)
+        self.ctx._chk(self.L.ka_in_fam_families(self.h, _ptr(recs), _ptr(freq) if want_freq else None))
+        out = [{k: int(v) for k, v in zip(IN_FAM, r)} for r in recs]
+        if want_freq:
+            for d, f in zip(out, freq):
+                d["freq"] = f
+        return out
+
+    def order(self):
+        """per family: sorted position -> index of the sequence in the family as given"""
+        self._open()
+        o = np.zeros(max(self.n, 1), np.int32)
+        self.ctx._chk(self.L.ka_in_fam_order(self.h, _ptr(o)))
+        return [x - self.first[f] for f, x in enumerate(self._per_family(o[:self.n]))]
+
+    def encoded(self):
+        """one (tree_codes, codes, letters) per family, each a list of uint8 arrays in sorted order: what
+        Context.run_families takes as it stands"""
+        self._open()
+        size = int(self.L.ka_in_fam_size(self.h))
+        t, c, l = (np.zeros(max(size, 1), np.uint8) for _ in range(3))
+        off, lens = np.zeros(max(self.n, 1), np.int32), np.zeros(max(self.n, 1), np.int32)
+        self.ctx._chk(self.L.ka_in_fam_encoded(self.h, _ptr(t), _ptr(c), _ptr(l), _ptr(off), _ptr(lens)))
+        out = []
+        for f in range(len(self.sizes)):
+            rng = range(int(self.first[f]), int(self.first[f + 1]))
+            out.append(tuple([p[off[i]:off[i] + lens[i]].copy() for i in rng] for p in (t, c, l)))
+        return out
+
+    def run(self, biotype, subm, scal, n_anchors=0, weight=2.0, realign=0, refine=0, n_threads=4, gap=b"-"):
+        """ka_in_fam_run: aligns the families of this biotype with its subm / scal, as run_families aligns them; their rows
+        stay in the handle in input order"""
+        self._open()
+        sub = np.ascontiguousarray(subm, np.float32).reshape(-1)
+        sc = np.ascontiguousarray(scal, np.float32)
+        self.ctx._chk(self.L.ka_in_fam_run(self.h, int(biotype), _ptr(sub), _ptr(sc), int(n_anchors), float(weight), int(realign),
+                                           int(n_threads), int(refine), gap[0]))
+
+    def rows(self):
+        """one list of rows (bytes) per family, in the caller's order; fails while a family has not been run"""
+        F = self._open()
+        need = int(self.L.ka_in_fam_rows_size(self.h))
+        if need < 0:
+            raise KalignAmdError(self.L.ka_last_error().decode())
+        buf, widths = np.zeros(max(need, 1), np.uint8), np.zeros(F, np.int32)
+        self.ctx._chk(self.L.ka_in_fam_rows(self.h, _ptr(buf), need, _ptr(widths)))
+        return _unpack_families(buf, self.sizes, widths)
+
+    def stats(self):
+        """ka_in_fam_stats: device ms of the scan and of the encode, kernel launches and host synchronisations of the
+        construction, the raw bytes, the wall ms of the run() calls so far (IN_STATS)"""
+        self._open()
+        st = np.zeros(len(IN_STATS), np.float64)
+        self.ctx._chk(self.L.ka_in_fam_stats(self.h, _ptr(st)))
+        return {k: (float(v) if k.endswith("_ms") else int(v)) for k, v in zip(IN_STATS, st)}
+
+
+def _in_fam_create(self, families, names=None, biotype=None):
+    """ka_in_fam_create: a FamilyInput over raw sequences on this context's device"""
+    return FamilyInput(self, families, names, biotype)
+
+
+Context.family_input = _in_fam_create
 
 
 def ens_fam_consensus_host(fam_lens, cands, families_letters, n_threads=1):
