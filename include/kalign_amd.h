@@ -1064,6 +1064,89 @@ long long ka_in_fam_rows_size(ka_in_fam* h);
 int  ka_in_fam_rows(ka_in_fam* h, uint8_t* out, long long cap, int* alnlens_out);
 int  ka_in_fam_stats(ka_in_fam* h, double* out);
 
+/*
+ * The codon stage (ABI 29): coding DNA of a batch of families, aligned in frame -- translate, align the proteins,
+ * backtranslate.  A nucleotide alignment of coding sequences puts one- and two-base gaps where they score well and breaks
+ * the reading frame; the reference's positive-selection pipeline works around it, one family at a time on the host:
+ *   benchmarks/downstream/positive_selection.py:456-459  "Translate-align-backtranslate to preserve codon reading frame
+ *                             Standard DNA alignment can insert 1- or 2-nt gaps that break the codon frame"
+ *   :49-66   _translate_dna   "dna_seq = dna_seq.upper()", "if len(dna_seq) % 3 != 0: raise ValueError(...)", "codon =
+ *                             dna_seq[i : i + 3]; aa = _CODON_TABLE.get(codon, "X"); if aa != "*": protein.append(aa)"
+ *   :69-123  _backtranslate   "original_dna = original_dna.upper()", the same walk keeping the codons whose aa != "*", then
+ *                             "if ch == "-": result.append("---") else: ... result.append(codons[codon_idx]); codon_idx += 1"
+ *                             and "if codon_idx != len(codons): raise ValueError(...)"
+ *   :462-507 the case flow    proteins aligned with seq_type="protein"; "codon_confidence = [c for c in
+ *                             aln_result.column_confidence for _ in range(3)]"
+ * This stage restates that rule, equal to the reference on letter-only input:
+ *   Residues   a sequence's raw bytes pass the input stage's byte rule: letters are residues, punctuation is gap characters
+ *              (counted and discarded), other bytes below 128 are dropped, a byte >= 128 is an error.  Residues are
+ *              upper-cased.
+ *   Codons     residues 3c .. 3c + 2 are codon c.  A residue count that is no multiple of 3 is an error for that sequence.
+ *   Code       the standard code over exactly A C G T: index 16a + 4b + c with A 0, C 1, G 2, T 3 into
+ *              "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF".  A codon holding any other letter -- N, U
+ *              and every ambiguity code included -- translates to X.  U is not T: the reference does not map it, so a codon
+ *              with a U is X here too.
+ *   Stops      TAA, TAG and TGA are omitted wherever they stand, not only at the end.  A sequence whose every codon is a
+ *              stop (or that has no residue) has no protein and is refused, naming family and sequence.
+ *   Proteins   the translated proteins are one family each, in the same order, under the caller's names; they go through the
+ *              input stage with the biotype forced to protein and from there through ka_in_fam_run, unchanged.
+ *   Back       in a protein row of width W a gap byte becomes three gap bytes and the k-th non-gap byte becomes the k-th
+ *              non-stop codon of that sequence, upper-cased: a codon row has width 3W.  A row whose non-gap count differs
+ *              from the sequence's non-stop codon count is an error, reported before any row is handed out.
+ *   A family of one: its protein row is its protein, its codon row its DNA without stop codons.
+ *
+ * Host only (no context, no GPU):
+ *   ka_cod_table     out64: the 64 letters above, '*' for a stop.
+ *   ka_cod_fam_check ka_in_fam_check's rules and messages under this stage's name ("ka_cod_fam_check: empty family", ...).
+ * The stage:
+ *   ka_cod_fam_create  runs the check, uploads the text in one copy and launches twice, back to back: the pack (counts,
+ *                    first byte >= 128, the upper-cased residues compacted at seq_off[i] in a plane the size of the text),
+ *                    then the translate (the protein plane and the stop-free codon plane, compacted at the same offsets).
+ *                    Two launches and one host synchronisation, whatever the batch; then the proteins go to an input stage
+ *                    of their own (ka_in_fam_create, biotype 0: its two launches and two synchronisations are its own).
+ *                    Fails naming the cause: the check's messages, "ka_cod_fam_create: family 1, sequence 0: byte 0xc3 at
+ *                    offset 5", "ka_cod_fam_create: family 1, sequence 2: 301 residues, not a multiple of 3" (the first
+ *                    offender in batch order; sequence numbers are within the family), "ka_cod_fam_create: family 0,
+ *                    sequence 1 has no protein".  Runs on ctx's device and stream: destroy it before ctx.
+ *   ka_cod_fam_sequences  recs_out[numseq * 6] in input order: residues, gap characters, dropped bytes, codons, stop codons,
+ *                    X codons.
+ *   ka_cod_fam_protein_size / ka_cod_fam_protein  the proteins one after the other in input order (size bytes), and
+ *                    off_out[numseq + 1].
+ *   ka_cod_fam_run   aligns the proteins (ka_in_fam_run with biotype 0: subm / scal are the protein's) and backtranslates
+ *                    the rows.
+ *   ka_cod_fam_back  backtranslates rows the caller brings -- a consensus of an ensemble over the same proteins, rows of
+ *                    another aligner: protein_rows packed as ka_batch_rows packs them (alnlens[f] + 1 bytes a row, rows in
+ *                    input order, n_bytes in all), gap_char their gap byte.  "ka_cod_fam_back: family 0, sequence 1: the row
+ *                    holds 6 residues, the sequence 7 codons without stops".  One launch and one synchronisation.
+ *                    Both leave protein rows and codon rows in the handle; a later call replaces them, a failed one leaves
+ *                    none.
+ *   ka_cod_fam_rows_size / ka_cod_fam_rows  the codon rows, packed as ka_batch_rows packs them (3 * alnlen + 1 bytes a
+ *                    row, a 0 byte after each), in input order; alnlens_out[n_fam] (optional) the codon widths.  -1 /
+ *                    "ka_cod_fam_rows: nothing has been backtranslated" before; a cap too small is refused before anything
+ *                    is copied.
+ *   ka_cod_fam_protein_rows_size / ka_cod_fam_protein_rows  the protein rows the codon rows were made from, the same way.
+ *   ka_cod_fam_stats  out[9]: device ms of the pack [0], the translate [1] and the last backtranslation [2]; kernel launches
+ *                    [3] and host synchronisations [4] of create (2 and 1); launches [5] and synchronisations [6] of the
+ *                    last backtranslation (1 and 1); raw bytes [7]; wall ms of the ka_cod_fam_run calls so far [8].
+ */
+typedef struct ka_cod_fam ka_cod_fam;
+int  ka_cod_table(uint8_t* out64);
+int  ka_cod_fam_check(int n_fam, const int* fam_first, const long long* seq_off, long long n_bytes);
+int  ka_cod_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, const uint8_t* text, const long long* seq_off,
+                       const uint8_t* names, const long long* name_off, ka_cod_fam** out);
+void ka_cod_fam_destroy(ka_cod_fam* h);
+int  ka_cod_fam_sequences(ka_cod_fam* h, int* recs_out);
+long long ka_cod_fam_protein_size(ka_cod_fam* h);
+int  ka_cod_fam_protein(ka_cod_fam* h, uint8_t* out, long long* off_out);
+int  ka_cod_fam_run(ka_cod_fam* h, const float* subm, const float* scal, int n_anchors, float weight,
+                    int realign_iterations, int n_threads, int refine_mode, uint8_t gap_char);
+int  ka_cod_fam_back(ka_cod_fam* h, const uint8_t* protein_rows, long long n_bytes, const int* alnlens, uint8_t gap_char);
+long long ka_cod_fam_rows_size(ka_cod_fam* h);
+int  ka_cod_fam_rows(ka_cod_fam* h, uint8_t* out, long long cap, int* alnlens_out);
+long long ka_cod_fam_protein_rows_size(ka_cod_fam* h);
+int  ka_cod_fam_protein_rows(ka_cod_fam* h, uint8_t* out, long long cap, int* alnlens_out);
+int  ka_cod_fam_stats(ka_cod_fam* h, double* out);
+
 #ifdef __cplusplus
 }
 #endif

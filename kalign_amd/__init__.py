@@ -8,3 +8,4 @@ CPU implementation: without the HIP library (or without a GPU) calls raise.
 from .api import (Context, KalignAmdError, TaskRec, lib_path, load_library, msa_tree,  # noqa: F401
                   pairwise_batch)
 from . import prepare  # noqa: F401  (from raw sequences to rows: prepare.align_families, prepare.align)
+from . import codon  # noqa: F401  (coding DNA in frame: codon.align_codon_families, codon.align_codons)

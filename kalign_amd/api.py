@@ -73,7 +73,10 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_batch_stats", "ka_batch_refine_stats",
            "ka_in_tables", "ka_in_detect", "ka_in_order", "ka_in_fam_check", "ka_in_fam_create", "ka_in_fam_destroy", "ka_in_fam_sequences",
            "ka_in_fam_families", "ka_in_fam_order", "ka_in_fam_size", "ka_in_fam_encoded", "ka_in_fam_run", "ka_in_fam_rows_size",
-           "ka_in_fam_rows", "ka_in_fam_stats"]
+           "ka_in_fam_rows", "ka_in_fam_stats",
+           "ka_cod_table", "ka_cod_fam_check", "ka_cod_fam_create", "ka_cod_fam_destroy", "ka_cod_fam_sequences", "ka_cod_fam_protein_size",
+           "ka_cod_fam_protein", "ka_cod_fam_run", "ka_cod_fam_back", "ka_cod_fam_rows_size", "ka_cod_fam_rows",
+           "ka_cod_fam_protein_rows_size", "ka_cod_fam_protein_rows", "ka_cod_fam_stats"]
 
 
 def lib_path():
@@ -303,6 +306,22 @@ def load_library():
     L.ka_in_fam_rows_size.restype = C.c_longlong
     L.ka_in_fam_rows.argtypes = [vp, vp, C.c_longlong, vp]
     L.ka_in_fam_stats.argtypes = [vp, vp]
+    L.ka_cod_table.argtypes = [vp]
+    L.ka_cod_fam_check.argtypes = [C.c_int, vp, vp, C.c_longlong]
+    L.ka_cod_fam_create.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(vp)]
+    L.ka_cod_fam_destroy.argtypes = [vp]
+    L.ka_cod_fam_destroy.restype = None
+    L.ka_cod_fam_sequences.argtypes = [vp, vp]
+    L.ka_cod_fam_protein_size.argtypes = [vp]
+    L.ka_cod_fam_protein_size.restype = C.c_longlong
+    L.ka_cod_fam_protein.argtypes = [vp, vp, vp]
+    L.ka_cod_fam_run.argtypes = [vp, vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_ubyte]
+    L.ka_cod_fam_back.argtypes = [vp, vp, C.c_longlong, vp, C.c_ubyte]
+    for name in ("ka_cod_fam_rows", "ka_cod_fam_protein_rows"):
+        getattr(L, name + "_size").argtypes = [vp]
+        getattr(L, name + "_size").restype = C.c_longlong
+        getattr(L, name).argtypes = [vp, vp, C.c_longlong, vp]
+    L.ka_cod_fam_stats.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -1947,6 +1966,121 @@ def _in_fam_create(self, families, names=None, biotype=None):
 
 
 Context.family_input = _in_fam_create
+
+
+COD_SEQ = ("residues", "gap_characters", "dropped", "codons", "stops", "x_codons")
+COD_STATS = ("pack_ms", "translate_ms", "back_ms", "launches", "syncs", "back_launches", "back_syncs", "bytes", "run_wall_ms")
+
+
+def codon_table():
+    """ka_cod_table (no GPU): the 64 letters of the standard code as bytes, index 16a + 4b + c with A 0, C 1, G 2, T 3; b"*": a stop"""
+    L = load_library()
+    t = np.zeros(64, np.uint8)
+    if L.ka_cod_table(_ptr(t)) != 0:
+        raise KalignAmdError(L.ka_last_error().decode())
+    return t.tobytes()
+
+
+class FamilyCodons(_CtxChild):
+    """Coding DNA of a batch of families, aligned in frame (ka_cod_fam): families is a list of lists of sequences (bytes / str)
+    under the input stage's byte rule, upper-cased; three residues a codon, the standard code over exactly A C G T (any other
+    letter makes the codon X; U is not T), stop codons omitted wherever they stand.  A residue count that is no multiple of 3,
+    a byte >= 128 and a sequence without a protein are refused.  run() aligns the proteins and backtranslates; back() takes
+    protein rows the caller brings.  names: a list of lists like families, or None."""
+    _destroy = "ka_cod_fam_destroy"
+
+    def __init__(self, ctx, families, names=None):
+        self.ctx, self.L = ctx, ctx.L
+        if not ctx.h:
+            raise KalignAmdError("the context is closed")
+        fams = [[_raw(s) for s in f] for f in families]
+        if not fams:
+            raise KalignAmdError("a codon stage needs a family")
+        self.sizes = [len(f) for f in fams]
+        self.first = _fam_first(self.sizes)
+        text, off = _pack_text([s for f in fams for s in f])
+        nm = noff = None
+        if names is not None:
+            if [len(f) for f in names] != self.sizes:
+                raise KalignAmdError("one name per sequence")
+            nm, noff = _pack_text([_raw(x) for f in names for x in f])
+        h = C.c_void_p()
+        ctx._chk(self.L.ka_cod_fam_create(ctx.h, len(fams), _ptr(self.first), _ptr(text), _ptr(off), _ptr(nm), _ptr(noff), C.byref(h)))
+        self._adopt(ctx, h)
+        self.n = int(self.first[-1])
+
+    def _open(self):
+        if not self.h:
+            raise KalignAmdError("the codon stage is closed")
+        return len(self.sizes)
+
+    def sequences(self):
+        """per family an int32 array [n_f, 6] in input order: residues, gap characters, dropped bytes, codons, stop codons, X
+        codons (COD_SEQ)"""
+        self._open()
+        recs = np.zeros((max(self.n, 1), len(COD_SEQ)), np.int32)
+        self.ctx._chk(self.L.ka_cod_fam_sequences(self.h, _ptr(recs)))
+        return [recs[self.first[f]:self.first[f + 1]] for f in range(len(self.sizes))]
+
+    def proteins(self):
+        """per family its translated proteins (bytes) in input order"""
+        self._open()
+        size = int(self.L.ka_cod_fam_protein_size(self.h))
+        buf, off = np.zeros(max(size, 1), np.uint8), np.zeros(self.n + 1, np.int64)
+        self.ctx._chk(self.L.ka_cod_fam_protein(self.h, _ptr(buf), _ptr(off)))
+        return [[buf[off[i]:off[i + 1]].tobytes() for i in range(int(self.first[f]), int(self.first[f + 1]))] for f in range(len(self.sizes))]
+
+    def run(self, subm, scal, n_anchors=0, weight=2.0, realign=0, refine=0, n_threads=4, gap=b"-"):
+        """ka_cod_fam_run: aligns the proteins with the protein's subm / scal, as FamilyInput.run aligns them, and
+        backtranslates their rows; protein rows and codon rows stay in the handle in input order"""
+        self._open()
+        sub = np.ascontiguousarray(subm, np.float32).reshape(-1)
+        sc = np.ascontiguousarray(scal, np.float32)
+        self.ctx._chk(self.L.ka_cod_fam_run(self.h, _ptr(sub), _ptr(sc), int(n_anchors), float(weight), int(realign), int(n_threads),
+                                            int(refine), gap[0]))
+
+    def back(self, protein_rows, gap=b"-"):
+        """ka_cod_fam_back: backtranslates one list of protein rows per family (rows in input order); a row whose residues
+        are not as many as its sequence's non-stop codons is refused"""
+        F = self._open()
+        if len(protein_rows) != F or [len(f) for f in protein_rows] != self.sizes:
+            raise KalignAmdError("one protein row per sequence")
+        packed, widths = pack_families(protein_rows)
+        self.ctx._chk(self.L.ka_cod_fam_back(self.h, _ptr(np.ascontiguousarray(packed)), len(packed), _ptr(widths), gap[0]))
+
+    def _rows(self, name):
+        F = self._open()
+        need = int(getattr(self.L, name + "_size")(self.h))
+        if need < 0:
+            raise KalignAmdError(self.L.ka_last_error().decode())
+        buf, widths = np.zeros(max(need, 1), np.uint8), np.zeros(F, np.int32)
+        self.ctx._chk(getattr(self.L, name)(self.h, _ptr(buf), need, _ptr(widths)))
+        return _unpack_families(buf, self.sizes, widths)
+
+    def rows(self):
+        """one list of codon rows (bytes) per family, in the caller's order; fails before a run() or a back()"""
+        return self._rows("ka_cod_fam_rows")
+
+    def protein_rows(self):
+        """the protein rows the codon rows were made from, the same way"""
+        return self._rows("ka_cod_fam_protein_rows")
+
+    def stats(self):
+        """ka_cod_fam_stats: device ms of the pack, the translate and the last backtranslation; kernel launches and host
+        synchronisations of the construction and of the last backtranslation; the raw bytes; the wall ms of the run() calls
+        so far (COD_STATS)"""
+        self._open()
+        st = np.zeros(len(COD_STATS), np.float64)
+        self.ctx._chk(self.L.ka_cod_fam_stats(self.h, _ptr(st)))
+        return {k: (float(v) if k.endswith("_ms") else int(v)) for k, v in zip(COD_STATS, st)}
+
+
+def _cod_fam_create(self, families, names=None):
+    """ka_cod_fam_create: a FamilyCodons over raw coding sequences on this context's device"""
+    return FamilyCodons(self, families, names)
+
+
+Context.family_codons = _cod_fam_create
 
 
 def ens_fam_consensus_host(fam_lens, cands, families_letters, n_threads=1):

@@ -173,6 +173,13 @@ extern "C" int ka_in_fam_check(int n_fam, const int* fam_first, const long long*
         return in_check("ka_in_fam_check", n_fam, fam_first, seq_off, n_bytes);
 }
 
+// the check's two halves under another stage's name (library-internal: ka_cod.cpp)
+int ka_in_check_first_named(const std::string& me, int n_fam, const int* fam_first) { return check_fam_first(me, n_fam, fam_first); }
+int ka_in_check_named(const std::string& me, int n_fam, const int* fam_first, const long long* seq_off, long long n_bytes)
+{
+        return in_check(me, n_fam, fam_first, seq_off, n_bytes);
+}
+
 #ifndef KA_IN_HOST_ONLY
 
 struct ka_in_fam {
