@@ -230,6 +230,7 @@ KaTreeDev tree_dev(ka_ctx* c)
         D.q_order = nullptr; D.q_n = 0; D.q_slots = 0; D.qw = c->env.qw; D.lw = c->env.lw; D.reuse = c->env.reuse;
         D.overlap = c->overlap_plan ? 1 : 0;
         D.hw_mode = c->env.hw ? (1 | (c->env.hw_prio << 4)) : 0;
+        D.sparse_mode = c->env.sparse ? 1 : 0;
         D.lean4 = c->env.lean4;
         D.sub_mode = c->env.subtree;
         D.mw_mode = c->env.mw;

@@ -112,6 +112,7 @@ struct KaTreeDev {
         const int* sip;                // member lists of every node in the reference's order (aln_run.c:428-436)
         const long long* sip_off;      // [2N-1]
         int merge_batch;               // round 6, ka_update_profile: bit 0 = items in batches when both operands' records are in HBM, bit 1 = also when one is a sequence, bit 2 = also in a cluster of workgroups (KA_MERGE)
+        int sparse_mode;               // round 8: strips with few non-zero counts per row run the gathered dot product (KA_SPARSE_NT, ka_pass.h); 0: off (KA_SPARSE=0 in the environment)
 };
 
 #define KA_NB 6                        // bonus entries a DP row carries: <= 5 anchors + the wrap-around entry

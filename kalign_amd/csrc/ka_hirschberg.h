@@ -28,8 +28,7 @@ __device__ void ka_cluster_sync(TaskShared& S)
         __syncthreads();
 }
 
-// debug breadcrumbs into a host-pinned buffer (KA_TRACE=1): survives a hung kernel
-#define KA_CRUMB(D_trace, slot, val) do { if (D_trace) { ((volatile int*)(D_trace))[slot] = (val); __threadfence_system(); } } while (0)
+// (KA_CRUMB and the slots of the breadcrumb buffer: ka_shared.h)
 
 
 // The passes of one recursion level: its work items (strips, packed jobs) dealt to / pulled by the waves of the team.

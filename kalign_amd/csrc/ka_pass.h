@@ -59,6 +59,31 @@ typedef float float4v __attribute__((ext_vector_type(4)));
 #endif
 #define KA_WAIT_VM0 0x0F70                                      // s_waitcnt vmcnt(0) only (gfx9 encoding)
 
+// THE GATHERED DOT PRODUCT (round 8).  A profile-profile cell adds NRES products count x score, and the reference adds only those
+// whose count is not zero (aln_profileprofile.c:70-77, 99-107): the rows of a profile of few sequences have two, three, four of them.
+// The dense form pays 2 x NRES VALU instructions per step for them all.  A strip whose lanes all have at most KA_SPARSE_NT residues
+// with a non-zero count (two rows per lane: in row A or row B) runs the gathered form instead: per lane a list of (LDS offset of the
+// residue's score inside a column record, count A, count B) in the dense loop's order, built once per strip; per step and term one
+// ds_read_b32 at the lane's own offset, one multiply, one dependent add -- the same products in the same order, and what the dense
+// form adds besides is +-0 (zero count x finite score), as are the pads of a lane whose list is shorter.  Wave-uniform and per
+// strip (TaskShared::sparse_ok, KA_SPARSE=0: every strip dense); nothing a strip hands over changes.
+// Built for the two-row strip of the 4-wave fast-mode kernels (unit 2: the queued launch), protein alphabets.
+// The bound, 4, by measurement (profiles/r08_sparse_bench_ab.txt: this source built at 4, 6 and 8 and run in turns, sixteen trees
+// as one forest): 192.2 / 191.9 / 188.2 GCUPS against 186.6 without the form -- 4 and 6 cannot be told apart, 8 loses most of the
+// gain.  A gathered step is 62-66 instructions against 88 dense at 4; a term costs three VALU instructions and an LDS read where a
+// dense one costs two, so every strip of two to four terms pays for a longer list, and the strips a wider bound adds gain little.
+// 4 is what a lane needs for two rows of a profile of two sequences, and the longest list of a 128-row strip at the levels that
+// hold most profile-profile cells (2 / 2.6 / 3.3 / 4 at levels 2 - 5, tools/row_sparsity.py).  The kernel spills 115 VGPRs at 4
+// (112 without the form), 101 / 100 at 6 / 8.
+#ifndef KA_SPARSE_NT
+#define KA_SPARSE_NT 4
+#endif
+#if defined(KA_UNIT) && KA_UNIT == 2
+#define KA_SPARSE_BUILT 1
+#else
+#define KA_SPARSE_BUILT 0
+#endif
+
 typedef __attribute__((address_space(3))) void* ka_lds_ptr;
 typedef const __attribute__((address_space(1))) void* ka_glb_ptr;
 typedef __attribute__((address_space(1))) float ka_gfloat;
@@ -350,6 +375,14 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
         constexpr int NPAIR = NRES / 2;
         float2v p1p[Q == 1 ? (NPAIR > 0 ? NPAIR : 1) : 1];            // Q = 1: the counts of residues (2i, 2i+1) in row A
         float p1last = 0.0f;                                          // Q = 1, odd alphabets: the count of residue NRES-1
+        // the gathered form (see KA_SPARSE_NT): the strip's choice (0: dense, else KA_SPARSE_NT -- wave-uniform), then per term
+        // the counts of rows (A, B) and the LDS address of the residue's score in column 0 of the ring
+        constexpr bool SPB = KA_SPARSE_BUILT && KIND == KA_PP && NRES >= 20 && NB == 0 && Q == 2;
+        constexpr int SP_NTMAX = SPB ? KA_SPARSE_NT : 1;
+        static_assert(!SPB || !KA_UNTRACKED_READS, "the gathered form reads the ring with tracked loads only");
+        int sp_nt = 0;
+        float2v spc[SP_NTMAX];
+        unsigned spo[SP_NTMAX];
         int res1A = 0, res1B = 0;
         if (KIND == KA_SS) {
                 oA = oB = -S.gpo; eA = eB = -S.gpe; tA = tB = -S.tgpe; orpA = orpB = -S.gpo;
@@ -369,10 +402,40 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
                                 float4v va[NV], vb[NV];
 #pragma unroll
                                 for (int i = 0; i < NV; ++i) { va[i] = ((const float4v*)pA)[i]; vb[i] = ((const float4v*)pB)[i]; }
+                                if constexpr (SPB) {
+                                        // The strip's form: the residues with a non-zero count in row A or row B, this lane's term list; the
+                                        // longest list of the wave against the bounds.  (Lanes below the strip's last row hold a copy of it.)
+                                        unsigned nz = 0;
 #pragma unroll
-                                for (int c = 0; c < NRES; ++c) {
-                                        p1v[c].x = va[c >> 2][c & 3];
-                                        p1v[c].y = actB ? vb[c >> 2][c & 3] : 0.0f;
+                                        for (int c = 0; c < NRES; ++c)
+                                                if (va[c >> 2][c & 3] != 0.0f || (actB && vb[c >> 2][c & 3] != 0.0f)) nz |= 1u << c;
+                                        const int nterms = __popc(nz);
+                                        if (__builtin_amdgcn_readfirstlane(S.sparse_ok) != 0 && __ballot(nterms > KA_SPARSE_NT) == 0ull) sp_nt = KA_SPARSE_NT;
+                                        // (KA_TRACE=1, tests: a gathered / a dense strip of a kernel built with the form has run)
+                                        if (S.trace && lane == 0) ((volatile int*)S.trace)[sp_nt ? KA_TRACE_GATHERED : KA_TRACE_DENSE] = 1;
+                                        if (sp_nt) {
+                                                // Compaction: the list in the order the dense loop adds (residue NRES-1 first), as (LDS offset of
+                                                // the residue's score inside a column record of the ring, count A, count B).  The counts come from
+                                                // the row's record once more (a dynamic index into va / vb would put them into scratch memory);
+                                                // a list that ends early is padded with zero counts at offset 0.
+#pragma unroll
+                                                for (int i = 0; i < SP_NTMAX; ++i) {
+                                                        const bool has = nz != 0u;
+                                                        const int c = has ? 31 - __clz(nz) : 0;
+                                                        nz &= ~(1u << c);
+                                                        const float xa = pA[c], xb = pB[c];
+                                                        spc[i].x = has ? xa : 0.0f;
+                                                        spc[i].y = (has && actB) ? xb : 0.0f;
+                                                        spo[i] = wlds_u + (unsigned)((c >> 2) * 2048 + (c & 3) * 4);
+                                                }
+                                        }
+                                }
+                                if (!SPB || sp_nt == 0) {
+#pragma unroll
+                                        for (int c = 0; c < NRES; ++c) {
+                                                p1v[c].x = va[c >> 2][c & 3];
+                                                p1v[c].y = actB ? vb[c >> 2][c & 3] : 0.0f;
+                                        }
                                 }
                         } else {
                                 float4v va[NV];
@@ -483,6 +546,27 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
                              : "memory");
         };
 
+        // The gathered form's reads: the N scores of the lane's own terms and the two chunks that hold the gap fields (as the dense
+        // form reads them), of column vcol; plain loads the compiler tracks.  sp_wait: see ring_wait.
+        float sq[2][SP_NTMAX];                                        // the scores of the lane's terms: current / next step
+        auto sp_read = [&](float4v* dstq, float* dsts, int vcol, auto& dep, auto n_tag) {
+                constexpr int N = decltype(n_tag)::value;
+                typedef const __attribute__((address_space(3))) float4v ka_l4;
+                typedef const __attribute__((address_space(3))) float ka_l1;
+                const unsigned cb = ((unsigned)vcol & 127u) << 4;
+                ka_l4* const cr = (ka_l4*)(unsigned long)(wlds_u | cb);
+                asm volatile("" : "+v"(dep) : : "memory");
+#pragma unroll
+                for (int i = 0; i < N; ++i) dsts[i] = *(ka_l1*)(unsigned long)(spo[i] | cb);
+                dstq[5] = cr[5 * 128]; dstq[6] = cr[6 * 128];
+        };
+        auto sp_wait = [&](float4v* qq, float* ss, auto n_tag) {
+                constexpr int N = decltype(n_tag)::value;
+#pragma unroll
+                for (int i = 0; i < N; ++i) asm volatile("" : "+v"(ss[i]) : : "memory");
+                asm volatile("" : "+v"(qq[5]), "+v"(qq[6]) : : "memory");
+        };
+
         // ---- HO: batches through LDS (see the head of ka_strip) ----
         const unsigned ho_out_u = wlds_u + KA_HO_RING;                // my ring (I produce)
         const unsigned ho_in_u = wlds_u - KA_WAVE_LDS + KA_HO_RING;   // the ring of the wave before me (I consume)
@@ -502,7 +586,11 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
 
         if (KIND == KA_PP) {
                 __builtin_amdgcn_s_waitcnt(KA_WAIT_VM0);              // the two ring batches issued at the top have landed
-                { float2v nodep = {0.0f, 0.0f}; ring_read(q[0], min(max(-lane, 0), ncols), nodep); }
+                float2v nodep = {0.0f, 0.0f};
+                bool gathered = false;
+                if constexpr (SPB) gathered = sp_nt != 0;
+                if (gathered) sp_read(q[0], sq[0], min(max(-lane, 0), ncols), nodep, std::integral_constant<int, SP_NTMAX>());
+                else ring_read(q[0], min(max(-lane, 0), ncols), nodep);
         } else {
                 // Sequence columns run one step ahead: at step t the residue and the two score look-ups of
                 // step t+1 are prepared (the LDS latency of the look-up and, every 64 steps, the L2 latency
@@ -522,7 +610,8 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
         //   P    : which half of q[] holds this step's column record (the other half receives the next)
         //   EV   : this step may carry a periodic event (ring batch hand-over, boundary / residue batch
         //          reload, flush of the output batch); EV = false steps are branch-free
-        auto step = [&](const int t, auto st_tag, auto full_tag, auto par_tag, auto ev_tag, auto first_tag, auto lb_tag) {
+        auto step = [&](const int t, auto st_tag, auto full_tag, auto par_tag, auto ev_tag, auto first_tag, auto lb_tag, auto nt_tag) {
+                constexpr int NTV = decltype(nt_tag)::value;                   // terms of the gathered dot product (0: the dense one)
                 constexpr bool LASTB = decltype(lb_tag)::value;                // partial strips: the last row is its lane's row B (always so in full strips)
                 constexpr bool FIRST = decltype(first_tag)::value;             // strip 0 of its pass: the row above is the pass's generated row -1
                 constexpr bool ST = decltype(st_tag)::value;
@@ -537,7 +626,8 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
                 // ---- column data for column v ----
                 float copen, cext, ctext;
                 if (KIND == KA_PP) {
-                        ring_wait(q[P]);                       // this step's column record (issued one step ago)
+                        // this step's column record (issued one step ago)
+                        if constexpr (NTV > 0) sp_wait(q[P], sq[P], nt_tag); else ring_wait(q[P]);
 #ifdef KA_PROF
                         if (EV && ST && pslot && lane == 0) pslot[256 + 0] += __builtin_amdgcn_s_memtime() - tq0;      // (head slot reused: top-of-step wait)
 #endif
@@ -644,6 +734,23 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
                                 acc.x += scA_cur;
                                 acc.y += scB_cur;
                                 if (NB) { const int jb = (dir == KA_FWD) ? (startb + v) : (endb - v); acc.x += bonA.template at<!ST>(jb); acc.y += bonB.template at<!ST>(jb); }
+                        } else if constexpr (NTV > 0) {
+                                // the gathered form: the lane's own terms in list order (the dense loop's), products one term ahead of the sums
+                                float2v prod;
+                                { float2v w; w.x = sq[P][0]; w.y = sq[P][0]; prod = spc[0] * w; }
+#pragma unroll
+                                for (int i = 1; i < NTV; ++i) {
+                                        float2v w; w.x = sq[P][i]; w.y = sq[P][i];
+                                        const float2v nprod = spc[i] * w;
+                                        acc = acc + prod;
+                                        prod = nprod;
+                                }
+                                acc = acc + prod;
+                                // the next step's scores and gap fields: after the sums, as the dense form's record
+                                __builtin_amdgcn_sched_barrier(0);
+                                if (EV && ((t + 1) & (KA_RING_BATCH - 1)) == 0) __builtin_amdgcn_s_waitcnt(KA_WAIT_VM0);
+                                sp_read(q[1 - P], sq[1 - P], ST ? (v + 1) : min(max(v + 1, 0), ncols), acc, nt_tag);
+                                __builtin_amdgcn_sched_barrier(0);
                         } else {
                                 // products one term ahead of the (dependent) sums: keeps a v_pk_mul between two
                                 // v_pk_add of the chain instead of an s_nop
@@ -863,7 +970,7 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
         // steps as in the steady phase, plus the strip's last step (the final flush) -- everything else runs WITHOUT the event
         // tests (round 2 ran all 128 edge steps of a strip as event steps, ~900 cycles each; the head of a strip is what its
         // consumer's start waits for, at every hand-over of every pass).
-        auto run = [&](int& t, const int tend, auto st_tag, auto full_tag, auto first_tag, auto lb_tag) {
+        auto run = [&](int& t, const int tend, auto st_tag, auto full_tag, auto first_tag, auto lb_tag, auto nt_tag) {
                 constexpr bool FIRST = decltype(first_tag)::value;
                 const int e4 = ncols + lastl;                                 // the last step: vL == ncols
                 while (t < tend) {
@@ -874,20 +981,20 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
                         const int ev = min(min(e1, e2), min(e3, e5));
                         const int fend = min(ev, tend);
                         if ((t & 1) && t < fend) {
-                                step(t, st_tag, full_tag, std::integral_constant<int, 1>(), std::false_type(), first_tag, lb_tag);
+                                step(t, st_tag, full_tag, std::integral_constant<int, 1>(), std::false_type(), first_tag, lb_tag, nt_tag);
                                 ++t;
                         }
                         for (; t + 1 < fend; t += 2) {
-                                step(t, st_tag, full_tag, std::integral_constant<int, 0>(), std::false_type(), first_tag, lb_tag);
-                                step(t + 1, st_tag, full_tag, std::integral_constant<int, 1>(), std::false_type(), first_tag, lb_tag);
+                                step(t, st_tag, full_tag, std::integral_constant<int, 0>(), std::false_type(), first_tag, lb_tag, nt_tag);
+                                step(t + 1, st_tag, full_tag, std::integral_constant<int, 1>(), std::false_type(), first_tag, lb_tag, nt_tag);
                         }
                         if (t < fend) {
-                                step(t, st_tag, full_tag, std::integral_constant<int, 0>(), std::false_type(), first_tag, lb_tag);
+                                step(t, st_tag, full_tag, std::integral_constant<int, 0>(), std::false_type(), first_tag, lb_tag, nt_tag);
                                 ++t;
                         }
                         if (t < tend && t == ev) {
-                                if (t & 1) step(t, st_tag, full_tag, std::integral_constant<int, 1>(), std::true_type(), first_tag, lb_tag);
-                                else step(t, st_tag, full_tag, std::integral_constant<int, 0>(), std::true_type(), first_tag, lb_tag);
+                                if (t & 1) step(t, st_tag, full_tag, std::integral_constant<int, 1>(), std::true_type(), first_tag, lb_tag, nt_tag);
+                                else step(t, st_tag, full_tag, std::integral_constant<int, 0>(), std::true_type(), first_tag, lb_tag, nt_tag);
                                 ++t;
                         }
                 }
@@ -895,7 +1002,7 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
         // steady state: the periodic events fall on known steps (ring hand-over at t = 31 mod 32 -- in full strips also the
         // output flush, at t = lastl mod 64 --, batch reloads at t = 0 mod 64); everything between two event steps runs
         // as branch-free step pairs.  (HO changes what a reload and a flush DO -- LDS instead of HBM -- not when they happen.)
-        auto run_steady = [&](int& t, const int tend, auto full_tag, auto first_tag, auto lb_tag) {
+        auto run_steady = [&](int& t, const int tend, auto full_tag, auto first_tag, auto lb_tag, auto nt_tag) {
                 constexpr bool FIRST = decltype(first_tag)::value;
                 while (t < tend) {
                         const int e1 = t | 31;
@@ -905,7 +1012,7 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
                         const int ev = min(e1, min(e2, e3));
                         const int fend = min(ev, tend);
                         if ((t & 1) && t < fend) {
-                                step(t, std::true_type(), full_tag, std::integral_constant<int, 1>(), std::false_type(), first_tag, lb_tag);
+                                step(t, std::true_type(), full_tag, std::integral_constant<int, 1>(), std::false_type(), first_tag, lb_tag, nt_tag);
                                 ++t;
                         }
 #ifdef KA_PROF
@@ -913,15 +1020,15 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
                         const int t_in = t;
 #endif
                         for (; t + 1 < fend; t += 2) {
-                                step(t, std::true_type(), full_tag, std::integral_constant<int, 0>(), std::false_type(), first_tag, lb_tag);
-                                step(t + 1, std::true_type(), full_tag, std::integral_constant<int, 1>(), std::false_type(), first_tag, lb_tag);
+                                step(t, std::true_type(), full_tag, std::integral_constant<int, 0>(), std::false_type(), first_tag, lb_tag, nt_tag);
+                                step(t + 1, std::true_type(), full_tag, std::integral_constant<int, 1>(), std::false_type(), first_tag, lb_tag, nt_tag);
                         }
 #ifdef KA_PROF
                         // cycles inside the branch-free step pairs / steps taken there (the rest of the strip: events, single steps, edges)
                         if (pslot && lane == 0) { pslot[6] += __builtin_amdgcn_s_memtime() - tpair0; pslot[7] += t - t_in; }
 #endif
                         if (t < fend) {
-                                step(t, std::true_type(), full_tag, std::integral_constant<int, 0>(), std::false_type(), first_tag, lb_tag);
+                                step(t, std::true_type(), full_tag, std::integral_constant<int, 0>(), std::false_type(), first_tag, lb_tag, nt_tag);
                                 ++t;
                         }
 #ifdef KA_PROF
@@ -932,8 +1039,8 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
                         const int ev_in = t;
 #endif
                         if (t < tend && t == ev) {
-                                if (t & 1) step(t, std::true_type(), full_tag, std::integral_constant<int, 1>(), std::true_type(), first_tag, lb_tag);
-                                else step(t, std::true_type(), full_tag, std::integral_constant<int, 0>(), std::true_type(), first_tag, lb_tag);
+                                if (t & 1) step(t, std::true_type(), full_tag, std::integral_constant<int, 1>(), std::true_type(), first_tag, lb_tag, nt_tag);
+                                else step(t, std::true_type(), full_tag, std::integral_constant<int, 0>(), std::true_type(), first_tag, lb_tag, nt_tag);
                                 ++t;
                         }
 #ifdef KA_PROF
@@ -945,24 +1052,34 @@ __device__ __forceinline__ void ka_strip(const TaskShared& S, const int starta, 
         const int nsteps = ncols + nl;                                // t = 0 .. ncols + nl - 1
         const int t_steady0 = min(nl, nsteps);                        // first step with every active lane at v >= 1
         const int t_steady1 = ncols;                                  // one past the last step with every lane at v <= ncols-1
-        auto phases = [&](auto full_tag, auto first_tag, auto lb_tag) {
+        auto phases = [&](auto full_tag, auto first_tag, auto lb_tag, auto nt_tag) {
                 int t = 0;
-                run(t, t_steady0, std::false_type(), full_tag, first_tag, lb_tag);
-                run_steady(t, t_steady1, full_tag, first_tag, lb_tag);
-                run(t, nsteps, std::false_type(), full_tag, first_tag, lb_tag);
+                run(t, t_steady0, std::false_type(), full_tag, first_tag, lb_tag, nt_tag);
+                run_steady(t, t_steady1, full_tag, first_tag, lb_tag, nt_tag);
+                run(t, nsteps, std::false_type(), full_tag, first_tag, lb_tag, nt_tag);
         };
         // (which row of its lane a partial strip's last row is: two instances, so that the step does not select)
-        auto go = [&](auto full_tag, auto first_tag) {
+        auto go = [&](auto full_tag, auto first_tag, auto nt_tag) {
                 constexpr bool FULL = decltype(full_tag)::value;
-                if constexpr (FULL || Q == 1) phases(full_tag, first_tag, std::integral_constant<bool, Q == 2>());
-                else { if (last_is_b) phases(full_tag, first_tag, std::true_type()); else phases(full_tag, first_tag, std::false_type()); }
+                if constexpr (FULL || Q == 1) phases(full_tag, first_tag, std::integral_constant<bool, Q == 2>(), nt_tag);
+                else { if (last_is_b) phases(full_tag, first_tag, std::true_type(), nt_tag); else phases(full_tag, first_tag, std::false_type(), nt_tag); }
         };
-        if (nr == SROWS) {
-                if (first) go(std::true_type(), std::true_type());
-                else go(std::true_type(), std::false_type());
+        // (nt_tag: the form of the dot product the strip chose above -- one of two loops, never both)
+        // (always_inline: left to the inliner, the consistency kernels got this lambda as a real function, every captured state in memory)
+        auto go_form = [&](auto nt_tag) __attribute__((always_inline)) {
+                if (nr == SROWS) {
+                        if (first) go(std::true_type(), std::true_type(), nt_tag);
+                        else go(std::true_type(), std::false_type(), nt_tag);
+                } else {
+                        if (first) go(std::false_type(), std::true_type(), nt_tag);
+                        else go(std::false_type(), std::false_type(), nt_tag);
+                }
+        };
+        if constexpr (SPB) {
+                if (sp_nt != 0) go_form(std::integral_constant<int, KA_SPARSE_NT>());
+                else go_form(std::integral_constant<int, 0>());
         } else {
-                if (first) go(std::false_type(), std::true_type());
-                else go(std::false_type(), std::false_type());
+                go_form(std::integral_constant<int, 0>());
         }
 #undef REC
 #undef IDX

@@ -31,6 +31,7 @@ struct KaEnv {
         int per = 0;                   // KA_PER: strips per workgroup (KaTreeDev::per_target; experiments)
         int ho = -1;                   // KA_HO: hand-over between neighbouring strips through LDS (KaTreeDev::ho_mode); -1: on (1)
         int hw = 1;                    // KA_HW: profile-profile strips with helper waves (ka_wstrip.h; KaTreeDev::hw_mode)
+        int sparse = 1;                // KA_SPARSE: profile-profile strips whose rows have few non-zero counts run the gathered dot product (ka_pass.h; KaTreeDev::sparse_mode); 0: every strip dense
         int hw_prio = 3;               // KA_HW_PRIO: s_setprio of a strip wave that has a helper (experiments)
         int subtree = 1;               // KA_SUBTREE: small Hirschberg subtrees run wave-locally in LDS
         int overlap = 1;               // KA_OVERLAP: the chained launch goes out beside the queued launch (a stream of its own, ordered by the tasks' done flags)
@@ -64,6 +65,7 @@ static inline void read_env(KaEnv& v)
         v.ho = env_int("KA_HO", -1);
         v.per = env_int("KA_PER", 0);
         v.hw = env_int("KA_HW", 1);
+        v.sparse = env_int("KA_SPARSE", 1);
         v.hw_prio = std::max(0, std::min(3, env_int("KA_HW_PRIO", 3)));
         v.upgma_launches = getenv("KA_UPGMA_LAUNCHES") != nullptr;
         v.qorder = env_int("KA_QORDER", 1) != 0;

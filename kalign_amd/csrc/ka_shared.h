@@ -75,6 +75,13 @@ struct KaCtl {
                                         // of 3 in the head form of the helper-wave strip; ka_task_kernel_half: 16 bytes more scratch, 5 more spilled VGPRs)
 };
 
+// debug breadcrumbs into a host-pinned buffer (KA_TRACE=1): survives a hung kernel
+#define KA_CRUMB(D_trace, slot, val) do { if (D_trace) { ((volatile int*)(D_trace))[slot] = (val); __threadfence_system(); } } while (0)
+// The buffer's 64 slots: [3] recursion level, [4] task phase, [32 .. 55] per wave of workgroup 0 (KA_TRACE_STRIP builds), and two marks
+// the strips of a kernel built with the gathered dot product set (ka_pass.h; tests/test_gpu_sparse_strips.py reads them):
+#define KA_TRACE_GATHERED 60                                    // a strip chose the gathered form
+#define KA_TRACE_DENSE 61                                       // a strip that could have chosen it ran dense
+
 // Everything the waves of a workgroup share about the task being aligned.
 struct TaskShared {
         int kind, swapped;
@@ -163,10 +170,13 @@ struct TaskShared {
         long long t_pass, t_meet;      // KA_FLAG_TIMING: shader-clock cycles spent in passes / meetups
         int n_levels;
         int next_member, next_g;       // chained launch: this workgroup's place in the parent task's cluster
+        int sparse_ok;                 // strips of this task may run the gathered dot product (KaTreeDev::sparse_mode; written and read only by the kernels built with it:
+                                       // KA_SPARSE_BUILT, NB == 0).  In the four bytes of padding in front of `prof`: nothing else moves (see KaCtl::regalloc_pad)
         long long* prof;               // KA_PROF builds: per (level, wave) timestamps of the root task
         int lvl_n[16];                 // per recursion level: sub-problems, pass / meetup cycles
         int lvl_pass[16], lvl_meet[16];
 };
+static_assert(offsetof(TaskShared, sparse_ok) + 4 == offsetof(TaskShared, prof) && offsetof(TaskShared, sparse_ok) == offsetof(TaskShared, next_g) + 4, "sparse_ok left the padding it was put into");
 
 // ------------------------------------------------------------------------------------------
 // column-operand terms for column record `rec`
