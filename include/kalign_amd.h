@@ -1147,6 +1147,127 @@ long long ka_cod_fam_protein_rows_size(ka_cod_fam* h);
 int  ka_cod_fam_protein_rows(ka_cod_fam* h, uint8_t* out, long long cap, int* alnlens_out);
 int  ka_cod_fam_stats(ka_cod_fam* h, double* out);
 
+/*
+ * The output stage (ABI 30): the finished rows of a batch of families as alignment text -- FASTA, Clustal, MSF, Stockholm
+ * with PP lines -- each format written for the whole batch into one buffer by one launch.  What the reference does at its
+ * back door, one row and one line at a time:
+ *   msa_io.c:668-717          write_msa_fasta: "fprintf(f_ptr,">%s\n", msa->sequences[i]->name);" then the row, "f++; if(f ==
+ *                             60){ fprintf(f_ptr, "\n"); f = 0; }" and "if(f){ fprintf(f_ptr,"\n"); }"
+ *   python-kalign/io.py:168-173  write_fasta: "handle.write(f">{seq_id}\n")", "for i in range(0, len(seq), line_length):
+ *                             handle.write(seq[i : i + line_length] + "\n")" (line_length 80 by default)
+ *   msa_io.c:719-866          write_msa_clu: "snprintf(ol->line, line_length,"Kalign (%s) multiple sequence alignment",
+ *                             KALIGN_PACKAGE_VERSION);", an empty line, then per row and block "for(j = c;j <
+ *                             max_name_len+5;j++){ ol->line[j] = ' '; }" and up to 60 bytes of the row; with row 0 of each
+ *                             block a line "ol->line[0] = '\n'; ol->line[1] = 0;" of seq_id numseq; all lines sorted by
+ *                             block, then seq_id (sort_out_lines, :1293) and printed with "fprintf(f_ptr, "%s\n", ol->line);"
+ *   msa_io.c:869-1150         write_msa_msf: "aln_len = msa->sequences[0]->len;", the banner, "" and
+ *                             " %s  MSF: %d  Type: %c  %s  Check: %d  .." (basename or "stdout", aln_len, "msa->L ==
+ *                             ALPHA_defPROTEIN ? 'P' : 'N'", the date "%B %d, %Y %H:%M", GCGMultchecksum), "", per row
+ *                             " Name: %-*.*s  Len:  %5d  Check: %4d  Weight: %.2f" (max_name_len twice, the name, aln_len,
+ *                             "GCGchecksum(msa->sequences[i]->seq, msa->sequences[i]->len)", 1.0), "", "//", "", then
+ *                             "aln_len = msa->alnlen;" and write_msa_clu's blocks
+ *   msa_misc.c:12-33          GCGMultchecksum: "chk = (chk + GCGchecksum(...)) % 10000;"; GCGchecksum: "chk = (chk + (i % 57 +
+ *                             1) * (toupper((int) seq[i]))) % 10000;"
+ *   python-kalign/io.py:239-243  _conf_to_pp_char: "if conf >= 0.95: return "*"" else "return str(int(conf * 10))"
+ *   python-kalign/io.py:292-317  write_stockholm with confidences: "# STOCKHOLM 1.0\n", per row "f"{seq_id:<{max_id}}
+ *                             {seq}\n"" (three spaces) and, with residue confidences, "if ch == "-" or ch == ".":
+ *                             pp.append(".")" else the PP character, "f"#=GR {seq_id:<{max_id}} PP {pp_str}\n""; with column
+ *                             confidences "f"#=GC {'PP_cons':<{pp_label_len}}   {pp_cons}\n"" with pp_label_len = max(max_id,
+ *                             7); "//\n"
+ * This stage writes the same bytes:
+ *   Rows       packed as ka_sum_fam_create takes them (a row of W columns W + 1 bytes), in the caller's order, under
+ *              ka_sum_fam_check's rules.  A byte of a row equal to gap_char is a gap, every other byte a character, taken as an
+ *              unsigned byte.  Only MSF's character counts ask.
+ *   Names      packed as the input stage takes them (names, name_off[numseq + 1]), or both NULL: family f's rows are named
+ *              seq0, seq1, ..., python-kalign's default.  A name is 1 to 255 bytes of printable ASCII (32..126); the
+ *              reference keeps MSA_NAME_LEN = 256 with the terminator.
+ *   Texts      every format is written for the whole batch into `out` (cap bytes), family after family; fam_off_out[n_fam +
+ *              1] (may be NULL) says where each family's text lies, fam_off_out[n_fam] is the size.  The _size call gives the
+ *              size alone, or -1.
+ *   FASTA      line_length >= 1: per row ">name\n" and the row in pieces of line_length bytes, each followed by "\n".  60 is
+ *              write_msa_fasta, 80 kalign.io.write_fasta's default.
+ *   Clustal    `header` (at most 255 bytes; the reference's is "Kalign (<version>) multiple sequence alignment"), an empty line,
+ *              then max(1, ceil(W / 60)) blocks: per row the name padded with spaces to the family's longest name + 5 and up
+ *              to 60 bytes of the row, then two newline bytes (the reference's stored "\n" printed with "%s\n").  A width that
+ *              is a multiple of 60 opens no empty block.
+ *   MSF        the reference's arithmetic as it stands: finalise_alignment never sets seq->len to the alignment length, so
+ *              with chars_i the characters of row i, "MSF:" and every "Len:" carry chars_0, a row's "Check:" is GCGchecksum
+ *              over the first chars_i BYTES of the aligned row i, gaps included, and the file's "Check:" is their sum modulo
+ *              10000.  The blocks are Clustal's (no space every ten letters, whatever the reference's comment says).  Per family
+ *              a title (1 to 255 printable bytes; titles / title_off[n_fam + 1] packed like names: the file's basename, or
+ *              "stdout") and a biotype, 0 protein or 1 DNA; per call the date string (1 to 63 printable bytes).  The library
+ *              never reads the clock.  Banner and type letter are what the reference's CLI writes after a run, and it writes
+ *              "!!NA_MULTIPLE_ALIGNMENT 1.0" and "Type: N" for a protein and for a DNA family alike: after a run msa->L is
+ *              neither ALPHA_defPROTEIN nor ALPHA_redPROTEIN (recorded in tests/golden/out_prot.npz and out_dna.npz).
+ *   Stockholm  residue_conf: float32, N_f * W_f per family, packed like the rows without the pad byte; column_conf: float32,
+ *              W_f per family; either may be NULL, not both: without confidences the reference writes through Biopython, which
+ *              this stage does not restate.  Lines are not wrapped, and the "#=GR" lines do not line up with the rows, as in
+ *              the reference.  A PP byte is '.' where the row's byte is '-' or '.' -- the reference's test, NOT the handle's
+ *              gap_char -- and the confidence there is not looked at.  Elsewhere, with v the float's value as a double: '*'
+ *              when v >= 0.95, else the digit (int)(v * 10.0).  PP_cons uses the same rule without the gap test.  A NaN or a
+ *              value outside [0, 1] (-0.0 is inside) would make the reference print two characters or raise; here the call
+ *              fails naming the first offender in batch order -- families in order, in a family its residue confidences row
+ *              after row, then its column confidences -- and `out` is zeroed over the text's size: no text is handed out.
+ *
+ * Host only (no context, no GPU):
+ *   ka_out_pp_char   the PP byte of a confidence, or -1 for a NaN and a value outside [0, 1].
+ *   ka_out_fam_check ka_sum_fam_check's rules and messages under this stage's name ("ka_out_fam_check: empty family", ...),
+ *                    then the names: "ka_out_fam_check: name_off does not ascend", "ka_out_fam_check: family 1, sequence 2:
+ *                    empty name", "ka_out_fam_check: family 1, sequence 2: name of 256 bytes; a name holds 1 to 255",
+ *                    "ka_out_fam_check: family 1, sequence 2: name byte 0x1f at offset 3; a name is printable ASCII (32..126)".
+ *   ka_out_fam_text_sizes  the closed forms alone: fam_off_out[n_fam + 1] of FASTA (format 0, param line_length), Clustal (1,
+ *                    param the header's bytes) or Stockholm (2, param 1 residue, 2 column, 3 both confidences) for families of
+ *                    these sizes, widths and name lengths (name_off NULL: the default names).  An MSF text's size depends on
+ *                    its records and has no closed form.
+ * The stage:
+ *   ka_out_fam_create  runs the check and uploads rows and names once; every format is written from them.  Nothing is
+ *                    launched.  Runs on ctx's device and stream: destroy it before ctx.
+ *   ka_out_fam_fasta / ka_out_fam_clustal / ka_out_fam_stockholm  the size is a closed form on the host; a cap below it is
+ *                    refused before anything is launched ("ka_out_fam_fasta: 99 bytes do not hold the text (100)").  Then the
+ *                    call's tables go up (a record and an offset per family, FASTA: an offset per row, the header), one launch
+ *                    fills the text -- a lane per aligned dword, assembled from as many lines as it spans -- and the text comes
+ *                    down: 1 launch and 1 host synchronisation per call, whatever the number of families.  Refusals:
+ *                    "ka_out_fam_fasta: line_length 0; a line holds one column at least", "ka_out_fam_clustal: header of 300
+ *                    bytes; it holds 255 at most", "ka_out_fam_stockholm: without confidences the reference writes Stockholm
+ *                    through Biopython, which this stage does not restate: give residue_conf, column_conf or both",
+ *                    "ka_out_fam_stockholm: family 1, sequence 2, column 5: confidence 1.00010002 outside [0, 1]",
+ *                    "ka_out_fam_stockholm: family 1, column 5: column confidence nan outside [0, 1]".  A refused call leaves
+ *                    the handle usable.
+ *   ka_out_fam_msf_records  recs_out[numseq * 2]: characters and prefix checksum of every row; fam_check_out[n_fam]: the
+ *                    families' checks (each optional).  They come from a row pass on the device, a wave per row: 1 launch and
+ *                    1 synchronisation, once per handle; the records stay on the host.
+ *   ka_out_fam_msf_size / ka_out_fam_msf  run the row pass when the handle has not, format the headers on the host from its
+ *                    records with the reference's format strings, and upload them; then as above.  The first MSF call on a
+ *                    handle counts 2 launches and 2 synchronisations (the row pass, wherever it ran, counts with the first
+ *                    writer after it), later ones 1 and 1.  The size depends on the records, so the cap is checked after the
+ *                    row pass and before the fill.  Refusals: "ka_out_fam_msf: family 0: title of 0 bytes; it holds 1 to 255",
+ *                    "ka_out_fam_msf: family 0: title holds a byte that is not printable ASCII (32..126)", "ka_out_fam_msf:
+ *                    family 0: biotype 2 is not 0 (protein) or 1 (DNA)", "ka_out_fam_msf: the date of 0 bytes; it holds 1 to
+ *                    63", "ka_out_fam_msf: the date holds a byte that is not printable ASCII (32..126)".
+ *   ka_out_fam_stats out4: device ms of the row pass [0] and of the last fill [1]; kernel launches [2] and host
+ *                    synchronisations [3] of the last writer.
+ */
+typedef struct ka_out_fam ka_out_fam;
+int  ka_out_pp_char(float confidence);
+int  ka_out_fam_check(int n_fam, const int* fam_first, const uint8_t* rows, const int* alnlens, const uint8_t* names, const long long* name_off);
+int  ka_out_fam_text_sizes(int n_fam, const int* fam_first, const int* alnlens, const long long* name_off, int format, int param,
+                           long long* fam_off_out);
+int  ka_out_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, const uint8_t* rows, const int* alnlens, int gap_char,
+                       const uint8_t* names, const long long* name_off, ka_out_fam** out);
+void ka_out_fam_destroy(ka_out_fam* h);
+long long ka_out_fam_fasta_size(ka_out_fam* h, int line_length);
+int  ka_out_fam_fasta(ka_out_fam* h, int line_length, uint8_t* out, long long cap, long long* fam_off_out);
+long long ka_out_fam_clustal_size(ka_out_fam* h, const char* header);
+int  ka_out_fam_clustal(ka_out_fam* h, const char* header, uint8_t* out, long long cap, long long* fam_off_out);
+int  ka_out_fam_msf_records(ka_out_fam* h, int* recs_out, int* fam_check_out);
+long long ka_out_fam_msf_size(ka_out_fam* h, const uint8_t* titles, const long long* title_off, const int* biotypes, const char* date);
+int  ka_out_fam_msf(ka_out_fam* h, const uint8_t* titles, const long long* title_off, const int* biotypes, const char* date, uint8_t* out,
+                    long long cap, long long* fam_off_out);
+long long ka_out_fam_stockholm_size(ka_out_fam* h, int has_residue_conf, int has_column_conf);
+int  ka_out_fam_stockholm(ka_out_fam* h, const float* residue_conf, const float* column_conf, uint8_t* out, long long cap,
+                          long long* fam_off_out);
+int  ka_out_fam_stats(ka_out_fam* h, double* out4);
+
 #ifdef __cplusplus
 }
 #endif

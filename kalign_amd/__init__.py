@@ -9,3 +9,4 @@ from .api import (Context, KalignAmdError, TaskRec, lib_path, load_library, msa_
                   pairwise_batch)
 from . import prepare  # noqa: F401  (from raw sequences to rows: prepare.align_families, prepare.align)
 from . import codon  # noqa: F401  (coding DNA in frame: codon.align_codon_families, codon.align_codons)
+from . import output  # noqa: F401  (from rows to alignment text: output.format_families, output.write_families)

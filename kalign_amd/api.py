@@ -76,7 +76,10 @@ EXPORTS = ["ka_tree_profile_dev", "ka_tree_reserve_profile_dev", "ka_tree_build_
            "ka_in_fam_rows", "ka_in_fam_stats",
            "ka_cod_table", "ka_cod_fam_check", "ka_cod_fam_create", "ka_cod_fam_destroy", "ka_cod_fam_sequences", "ka_cod_fam_protein_size",
            "ka_cod_fam_protein", "ka_cod_fam_run", "ka_cod_fam_back", "ka_cod_fam_rows_size", "ka_cod_fam_rows",
-           "ka_cod_fam_protein_rows_size", "ka_cod_fam_protein_rows", "ka_cod_fam_stats"]
+           "ka_cod_fam_protein_rows_size", "ka_cod_fam_protein_rows", "ka_cod_fam_stats",
+           "ka_out_pp_char", "ka_out_fam_check", "ka_out_fam_text_sizes", "ka_out_fam_create", "ka_out_fam_destroy", "ka_out_fam_fasta_size", "ka_out_fam_fasta",
+           "ka_out_fam_clustal_size", "ka_out_fam_clustal", "ka_out_fam_msf_records", "ka_out_fam_msf_size", "ka_out_fam_msf",
+           "ka_out_fam_stockholm_size", "ka_out_fam_stockholm", "ka_out_fam_stats"]
 
 
 def lib_path():
@@ -322,6 +325,26 @@ def load_library():
         getattr(L, name + "_size").restype = C.c_longlong
         getattr(L, name).argtypes = [vp, vp, C.c_longlong, vp]
     L.ka_cod_fam_stats.argtypes = [vp, vp]
+    L.ka_out_pp_char.argtypes = [C.c_float]
+    L.ka_out_fam_check.argtypes = [C.c_int, vp, vp, vp, vp, vp]
+    L.ka_out_fam_text_sizes.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, vp]
+    L.ka_out_fam_create.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.POINTER(vp)]
+    L.ka_out_fam_destroy.argtypes = [vp]
+    L.ka_out_fam_destroy.restype = None
+    L.ka_out_fam_fasta_size.argtypes = [vp, C.c_int]
+    L.ka_out_fam_fasta_size.restype = C.c_longlong
+    L.ka_out_fam_fasta.argtypes = [vp, C.c_int, vp, C.c_longlong, vp]
+    L.ka_out_fam_clustal_size.argtypes = [vp, C.c_char_p]
+    L.ka_out_fam_clustal_size.restype = C.c_longlong
+    L.ka_out_fam_clustal.argtypes = [vp, C.c_char_p, vp, C.c_longlong, vp]
+    L.ka_out_fam_msf_records.argtypes = [vp, vp, vp]
+    L.ka_out_fam_msf_size.argtypes = [vp, vp, vp, vp, C.c_char_p]
+    L.ka_out_fam_msf_size.restype = C.c_longlong
+    L.ka_out_fam_msf.argtypes = [vp, vp, vp, vp, C.c_char_p, vp, C.c_longlong, vp]
+    L.ka_out_fam_stockholm_size.argtypes = [vp, C.c_int, C.c_int]
+    L.ka_out_fam_stockholm_size.restype = C.c_longlong
+    L.ka_out_fam_stockholm.argtypes = [vp, vp, vp, vp, C.c_longlong, vp]
+    L.ka_out_fam_stats.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -2081,6 +2104,182 @@ def _cod_fam_create(self, families, names=None):
 
 
 Context.family_codons = _cod_fam_create
+
+
+OUT_STATS = ("rows_ms", "fill_ms", "launches", "syncs")
+# write_msa_clu's header with the version the reference of this tree's oracle/_ref build writes (tests/golden/out_*.npz pin it)
+CLUSTAL_HEADER = b"Kalign (3.5.1) multiple sequence alignment"
+MSF_DATE = "%B %d, %Y %H:%M"       # write_msa_msf's strftime format
+
+
+def pp_char(confidence):
+    """ka_out_pp_char (no GPU): the Stockholm PP byte of a confidence (its float32 value) as bytes, or None for a NaN and a
+    value outside [0, 1]"""
+    c = int(load_library().ka_out_pp_char(float(np.float32(confidence))))
+    return None if c < 0 else bytes([c])
+
+
+def _pack_names(names, sizes):
+    if names is None:
+        return None, None
+    if [len(f) for f in names] != list(sizes):
+        raise KalignAmdError("one name per sequence")
+    return _pack_text([_raw(x) for f in names for x in f])
+
+
+def output_check(families_rows, names=None):
+    """ka_out_fam_check (no GPU): raises with the library's message when the batch or a name is refused"""
+    L = load_library()
+    fams = [[_raw(x) for x in f] for f in families_rows]
+    sizes = [len(f) for f in fams]
+    rows, widths = pack_families(fams)
+    nm, noff = _pack_names(names, sizes)
+    if L.ka_out_fam_check(len(fams), _ptr(_fam_first(sizes)), _ptr(rows if len(rows) else np.zeros(1, np.uint8)), _ptr(widths), _ptr(nm), _ptr(noff)) != 0:
+        raise KalignAmdError(L.ka_last_error().decode())
+
+
+def output_sizes(sizes, widths, name_lens, fmt, param):
+    """ka_out_fam_text_sizes (no GPU): the bytes of every family's text from the closed forms.  sizes, widths: per family;
+    name_lens: a list of lists of name lengths, or None (the default names); fmt "fasta" (param line_length), "clustal" (param
+    the header's bytes) or "stockholm" (param 1 residue, 2 column, 3 both confidences)"""
+    L = load_library()
+    noff = None
+    if name_lens is not None:
+        noff = np.zeros(int(sum(sizes)) + 1, np.int64)
+        noff[1:] = np.cumsum([n for f in name_lens for n in f], dtype=np.int64)
+    off = np.zeros(len(sizes) + 1, np.int64)
+    if L.ka_out_fam_text_sizes(len(sizes), _ptr(_fam_first(sizes)), _ptr(np.ascontiguousarray(widths, np.int32)), _ptr(noff),
+                               ("fasta", "clustal", "stockholm").index(fmt), int(param), _ptr(off)) != 0:
+        raise KalignAmdError(L.ka_last_error().decode())
+    return np.diff(off)
+
+
+class FamilyOutput(_CtxChild):
+    """The finished rows of a batch of families on the device (ka_out_fam) and the text the reference's writers make of each --
+    write_msa_fasta / kalign.io.write_fasta, write_msa_clu, write_msa_msf, kalign.io.write_stockholm with PP lines -- byte
+    for byte, each format in one launch whatever the number of families.  families_rows: one list of rows per family;
+    names: a list of lists like it (1 to 255 printable bytes each), or None: seq0, seq1, ... per family; gap: the gap byte.
+    Every writer returns a list of bytes, one text per family."""
+    _destroy = "ka_out_fam_destroy"
+
+    def __init__(self, ctx, families_rows, names=None, gap=b"-"):
+        self.ctx, self.L = ctx, ctx.L
+        if not ctx.h:
+            raise KalignAmdError("the context is closed")
+        fams = [[_raw(x) for x in f] for f in families_rows]
+        if not fams:
+            raise KalignAmdError("a family output needs a family")
+        gap = gap.encode() if isinstance(gap, str) else bytes(gap)
+        if len(gap) != 1:
+            raise KalignAmdError("the gap is one byte")
+        self.sizes = [len(f) for f in fams]
+        self.first = _fam_first(self.sizes)
+        rows, self.widths = pack_families(fams)
+        nm, noff = _pack_names(names, self.sizes)
+        h = C.c_void_p()
+        ctx._chk(self.L.ka_out_fam_create(ctx.h, len(fams), _ptr(self.first), _ptr(rows if len(rows) else np.zeros(1, np.uint8)),
+                                          _ptr(self.widths), gap[0], _ptr(nm), _ptr(noff), C.byref(h)))
+        self._adopt(ctx, h)
+        self.n = int(self.first[-1])
+
+    def _open(self):
+        if not self.h:
+            raise KalignAmdError("the family output is closed")
+        return len(self.sizes)
+
+    def _texts(self, size, write, cap=None):
+        """the batch's text through write(buf, cap, fam_off), cut per family; cap: a cap other than the size (tests)"""
+        if size < 0:
+            raise KalignAmdError(self.L.ka_last_error().decode())
+        cap = size if cap is None else cap
+        buf, off = np.zeros(max(cap, 1), np.uint8), np.zeros(len(self.sizes) + 1, np.int64)
+        self.ctx._chk(write(_ptr(buf), cap, _ptr(off)))
+        raw = buf.tobytes()
+        return [raw[off[f]:off[f + 1]] for f in range(len(self.sizes))]
+
+    def fasta(self, line_length=60, cap=None):
+        """per family ">name" and the row in lines of line_length bytes: 60 is write_msa_fasta, 80 kalign.io.write_fasta"""
+        self._open()
+        L = int(line_length)
+        return self._texts(int(self.L.ka_out_fam_fasta_size(self.h, L)), lambda b, c, o: self.L.ka_out_fam_fasta(self.h, L, b, c, o), cap)
+
+    def clustal(self, header=CLUSTAL_HEADER, cap=None):
+        """write_msa_clu's text per family under `header`"""
+        self._open()
+        hd = _raw(header)
+        return self._texts(int(self.L.ka_out_fam_clustal_size(self.h, hd)), lambda b, c, o: self.L.ka_out_fam_clustal(self.h, hd, b, c, o), cap)
+
+    def msf_records(self):
+        """per family (int32 [n_f, 2]: characters and prefix checksum of every row, the family's check)"""
+        F = self._open()
+        recs, check = np.zeros((max(self.n, 1), 2), np.int32), np.zeros(F, np.int32)
+        self.ctx._chk(self.L.ka_out_fam_msf_records(self.h, _ptr(recs), _ptr(check)))
+        return [(recs[self.first[f]:self.first[f + 1]], int(check[f])) for f in range(F)]
+
+    def msf(self, titles, biotypes, date=None, cap=None):
+        """write_msa_msf's text per family.  titles: one per family (the file's basename, or "stdout"); biotypes: 0 protein /
+        1 DNA, one value or one per family; date: write_msa_msf's date string (MSF_DATE), now when None"""
+        F = self._open()
+        if len(titles) != F:
+            raise KalignAmdError("%d titles for %d families" % (len(titles), F))
+        if date is None:
+            import time
+            date = time.strftime(MSF_DATE)
+        t, toff = _pack_text([_raw(x) for x in titles])
+        bt = np.ascontiguousarray(np.broadcast_to(np.asarray(biotypes, np.int32), (F,)))
+        d = _raw(date)
+        return self._texts(int(self.L.ka_out_fam_msf_size(self.h, _ptr(t), _ptr(toff), _ptr(bt), d)),
+                           lambda b, c, o: self.L.ka_out_fam_msf(self.h, _ptr(t), _ptr(toff), _ptr(bt), d, b, c, o), cap)
+
+    def _conf(self, conf, per_row, what):
+        """per family confidences -> one float32 array; float64 values that float32 does not hold are refused"""
+        if conf is None:
+            return None
+        F = len(self.sizes)
+        if len(conf) != F:
+            raise KalignAmdError("%d %s confidences for %d families" % (len(conf), what, F))
+        parts = []
+        for f, c in enumerate(conf):
+            a = np.asarray(c)
+            want = (self.sizes[f], int(self.widths[f])) if per_row else (int(self.widths[f]),)
+            if a.shape != want:
+                raise KalignAmdError("family %d: %s confidences of shape %s, not %s" % (f, what, a.shape, want))
+            b = a
+            if a.dtype != np.float32:
+                a64 = np.asarray(a, np.float64)
+                with np.errstate(over="ignore"):
+                    b = a64.astype(np.float32)
+                ok = (b.astype(np.float64) == a64) | np.isnan(a64)
+                if not ok.all():
+                    k = tuple(int(x) for x in np.argwhere(~ok)[0])
+                    raise KalignAmdError("family %d: %s confidence at %s is not a float32 value (%r): a rounding across 0.95 or a tenth would "
+                                         "change a PP byte; round it yourself" % (f, what, k, float(a64[k])))
+            parts.append(b.reshape(-1))
+        return np.ascontiguousarray(np.concatenate(parts))
+
+    def stockholm(self, residue_confidence=None, column_confidence=None, cap=None):
+        """kalign.io.write_stockholm's text per family with "#=GR <name> PP" lines (residue_confidence: per family [n_f, W_f])
+        and / or a "#=GC PP_cons" line (column_confidence: per family [W_f]); one of the two at least"""
+        self._open()
+        res, col = self._conf(residue_confidence, True, "residue"), self._conf(column_confidence, False, "column")
+        return self._texts(int(self.L.ka_out_fam_stockholm_size(self.h, res is not None, col is not None)),
+                           lambda b, c, o: self.L.ka_out_fam_stockholm(self.h, _ptr(res), _ptr(col), b, c, o), cap)
+
+    def stats(self):
+        """ka_out_fam_stats: device ms of the MSF row pass and of the last fill; kernel launches and host synchronisations of
+        the last writer (OUT_STATS)"""
+        self._open()
+        st = np.zeros(len(OUT_STATS), np.float64)
+        self.ctx._chk(self.L.ka_out_fam_stats(self.h, _ptr(st)))
+        return {k: (float(v) if k.endswith("_ms") else int(v)) for k, v in zip(OUT_STATS, st)}
+
+
+def _out_fam_create(self, families_rows, names=None, gap=b"-"):
+    """ka_out_fam_create: a FamilyOutput holding rows and names of every family on this context's device"""
+    return FamilyOutput(self, families_rows, names, gap)
+
+
+Context.family_output = _out_fam_create
 
 
 def ens_fam_consensus_host(fam_lens, cands, families_letters, n_threads=1):

@@ -18,7 +18,7 @@ __attribute__((visibility("hidden"))) int ka_fail_message(const char* m) { retur
 extern "C" const char* ka_last_error(void) { return g_err.c_str(); }
 struct ka_ctx;
 int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_guide.cpp)
-extern "C" int ka_abi_version(void) { return 29; }
+extern "C" int ka_abi_version(void) { return 30; }
 
 extern "C" int ka_ctx_create(int device, ka_ctx** out)
 {

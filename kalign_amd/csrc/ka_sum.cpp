@@ -288,6 +288,12 @@ extern "C" int ka_sum_fam_check(int n_fam, const int* fam_first, const uint8_t* 
         return sum_fam_check("ka_sum_fam_check", n_fam, fam_first, rows, alnlens);
 }
 
+// the check under another stage's name (library-internal: ka_out.cpp)
+int ka_sum_check_named(const std::string& me, int n_fam, const int* fam_first, const uint8_t* rows, const int* alnlens)
+{
+        return sum_fam_check(me.c_str(), n_fam, fam_first, rows, alnlens);
+}
+
 extern "C" int ka_sum_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, const uint8_t* rows, const int* alnlens, int gap_char, ka_sum_fam** out)
 {
         if (!ctx || !out || gap_char < 0 || gap_char > 255) return fail("ka_sum_fam_create: bad arguments");
