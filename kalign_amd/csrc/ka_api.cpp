@@ -16,8 +16,6 @@ int fail(const std::string& m) { g_err = m; return KA_FAIL; }
 __attribute__((visibility("hidden"))) int ka_fail_message(const char* m) { return fail(m); }
 
 extern "C" const char* ka_last_error(void) { return g_err.c_str(); }
-struct ka_ctx;
-int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_guide.cpp)
 extern "C" int ka_abi_version(void) { return 30; }
 
 extern "C" int ka_ctx_create(int device, ka_ctx** out)
@@ -87,19 +85,6 @@ extern "C" void ka_ctx_destroy(ka_ctx* c)
 {
         if (!c) return;
         (void)hipSetDevice(c->device);
-        c->d_codes.release(); c->d_seq_off.release(); c->d_node_len.release(); c->d_level_ids.release();
-        c->d_path_arena.release(); c->d_error.release(); c->d_node_prof.release(); c->d_dbg_off.release();
-        c->d_prof_arena.release(); c->d_subm.release(); c->d_dbg_arena.release(); c->d_counters.release();
-        c->d_scratch.release(); c->d_tasks.release(); c->d_recs.release(); c->d_timing.release();
-        c->d_ctl.release(); c->d_blocks.release(); c->d_blocks_tmp.release(); c->d_join.release();
-        c->p_codes.release(); c->p_off.release(); c->p_len.release(); c->p_ia.release(); c->p_ib.release(); c->p_paths.release();
-        c->p_err.release(); c->p_subm.release(); c->p_scores.release(); c->p_poff.release(); c->p_scr.release();
-        c->b_peq.release(); c->b_dist.release();
-        c->d_letters.release(); c->d_rows.release(); c->d_alnlen.release(); c->d_pair_of.release();
-        c->d_adm.release(); c->d_amean.release(); c->d_uactive.release(); c->d_ucand.release(); c->d_umerges.release();
-        c->d_cons_maps.release(); c->d_colof.release(); c->d_colof_init.release(); c->d_sip.release();
-        c->d_cons_map_off.release(); c->d_sip_off.release();
-        c->d_adtiles.release(); c->d_adfams.release(); c->d_fam_of.release(); c->d_utable.release(); c->d_row_off.release();
         for (int k = 0; k < 2; k++) { if (c->pin[k]) (void)hipHostFree(c->pin[k]); if (c->pin_ev[k]) (void)hipEventDestroy(c->pin_ev[k]); }
         if (c->h_trace) (void)hipHostFree(c->h_trace);
         for (hipEvent_t e : c->launch_ev) (void)hipEventDestroy(e);
@@ -915,18 +900,6 @@ extern "C" int ka_run_encoded_refine(ka_ctx* c, int numseq, const uint8_t* tree_
 
 
 // ---- a batch of families: the realignment trees of all of them in a handful of launches, and the one call --------------------
-static int check_fam_first(const char* who, int n_fam, const int* fam_first)
-{
-        const std::string me(who);
-        if (n_fam < 1 || !fam_first) return fail(me + ": bad arguments");
-        if (fam_first[0] != 0) return fail(me + ": fam_first does not ascend from 0 to numseq");
-        for (int f = 0; f < n_fam; f++) {
-                if (fam_first[f + 1] < fam_first[f]) return fail(me + ": fam_first does not ascend from 0 to numseq");
-                if (fam_first[f + 1] == fam_first[f]) return fail(me + ": empty family");
-        }
-        return KA_OK;
-}
-
 // compute_aln_pairwise_dist + build_tree_from_pairwise for every family of a batch: one launch of the
 // identity distances over a table of tiles, one of the row means, and the UPGMAs one workgroup per family, a launch per size
 // class.  The task list comes back in the forest numbering of ka_guide_forest.
@@ -942,7 +915,7 @@ static int aln_guide_forest(const char* who, ka_ctx* c, int n_fam, const int* fa
         const std::string me(who);
         if (!c) return fail("null ctx");
         if (!tasks_abc) return fail("null argument");
-        if (check_fam_first(who, n_fam, fam_first)) return KA_FAIL;
+        if (ka_fam_check_first(who, n_fam, fam_first)) return KA_FAIL;
         HIPCHK(hipSetDevice(c->device));
         const int numseq = fam_first[n_fam];
         std::vector<int> width(n_fam);
@@ -1055,7 +1028,7 @@ extern "C" int ka_run_encoded_batch(ka_ctx* c, int n_fam, const int* fam_first, 
                                     int refine_mode, uint8_t gap_char, int* alnlen_out)
 {
         if (!c) return fail("null ctx");
-        if (check_fam_first("ka_run_encoded_batch", n_fam, fam_first)) return KA_FAIL;
+        if (ka_fam_check_first("ka_run_encoded_batch", n_fam, fam_first)) return KA_FAIL;
         if (!tree_codes || !codes || !letters || !off || !lens || !subm || !scal) return fail("ka_run_encoded_batch: bad arguments");
         if (!refine_mode_ok(refine_mode)) return fail("ka_run_encoded_batch: refine_mode must be 0, 1, 2 (optionally | KA_REFINE_ADAPTIVE) or 3");
         if (n_anchors > KA_CONS_MAX_ANCHORS) return fail("this build takes at most 128 consistency anchors (KA_CONS_MAX_ANCHORS)");

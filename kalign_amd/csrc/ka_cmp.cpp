@@ -19,8 +19,6 @@
 
 #include <string.h>
 
-int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
-
 namespace {
 
 constexpr int kGroup = 32;         // test alignments per device pass of ka_cmp_score_batch: the bound on device memory
@@ -56,9 +54,6 @@ KaCmpCore::~KaCmpCore()
 {
         for (auto& e : ev)
                 if (e) (void)hipEventDestroy(e);
-        dRefs.release(); dJobs.release(); dRefFirst.release(); dJobFirst.release(); dOffs.release(); dLens.release(); dSeqOf.release();
-        dColR.release(); dColT.release(); dColCnt.release(); dMasks.release(); dResR.release(); dResT.release(); dRows.release();
-        dScored.release(); dFrac.release(); dMaskOff.release(); dSums.release(); dDet.release();
 }
 
 int KaCmpCore::attach(ka_ctx* ctx) { return ka_ctx_device_stream(ctx, &device, &stream); }

@@ -13,12 +13,8 @@ namespace {
 int cmp_fam_check(const char* who, int n_fam, const int* fam_first, const int* lens, const uint8_t* rows, const int* alnlens)
 {
         const std::string me(who);
-        if (n_fam < 1 || !fam_first || !lens || !rows || !alnlens) return fail(me + ": bad arguments");
-        if (fam_first[0] != 0) return fail(me + ": fam_first does not ascend from 0 to numseq");
-        for (int f = 0; f < n_fam; f++) {
-                if (fam_first[f + 1] < fam_first[f]) return fail(me + ": fam_first does not ascend from 0 to numseq");
-                if (fam_first[f + 1] == fam_first[f]) return fail(me + ": empty family");
-        }
+        if (!lens || !rows || !alnlens) return fail(me + ": bad arguments");
+        if (ka_fam_check_first(me, n_fam, fam_first)) return KA_FAIL;
         const std::string why = "the position maps hold at most " + std::to_string(KA_CMP_MAX_RES);
         long long residues = 0, cols = 0, off = 0;
         for (int f = 0; f < n_fam; f++) {
@@ -40,8 +36,7 @@ int cmp_fam_check(const char* who, int n_fam, const int* fam_first, const int* l
 // the packed rows of `alnlens` in one copy
 KaCmpUpload packed(const uint8_t* rows, const int* fam_first, int n_fam, const int* alnlens)
 {
-        long long bytes = 0;
-        for (int f = 0; f < n_fam; f++) bytes += (long long)(fam_first[f + 1] - fam_first[f]) * (alnlens[f] + 1);
+        const long long bytes = ka_fam_row_bytes(n_fam, fam_first, alnlens);
         return [=](uint8_t* dst, hipStream_t s) {
                 HIPCHK(hipMemcpyAsync(dst, rows, (size_t)bytes, hipMemcpyHostToDevice, s));
                 return (int)KA_OK;

@@ -17,20 +17,14 @@
 #include <string>
 #include <vector>
 #ifdef KA_COD_HOST_ONLY
-#include "kalign_amd.h"
-int fail(const std::string& m);
+#include "ka_fam.h"
 #define KA_COD_LETTERS "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF"
 #else
 #include <chrono>
 #include <memory>
 #include "ka_ctx.h"
 #include "ka_cod.h"
-
-int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
 #endif
-// ka_in_fam_check's rules with messages under the name `me`, and their first half, fam_first alone (library-internal: ka_in.cpp)
-int ka_in_check_first_named(const std::string& me, int n_fam, const int* fam_first);
-int ka_in_check_named(const std::string& me, int n_fam, const int* fam_first, const long long* seq_off, long long n_bytes);
 
 extern "C" int ka_cod_table(uint8_t* out64)
 {
@@ -47,10 +41,8 @@ extern "C" int ka_cod_fam_check(int n_fam, const int* fam_first, const long long
 
 #ifndef KA_COD_HOST_ONLY
 
-struct ka_cod_fam {
+struct ka_cod_fam : KaStage {
         ka_ctx* ctx = nullptr;
-        int device = 0;
-        hipStream_t stream = nullptr;
         int nFam = 0, nSeq = 0;
         long long nBytes = 0;
         std::vector<int> famFirst;
@@ -64,32 +56,23 @@ struct ka_cod_fam {
         DevBuf<uint8_t> dText, dPacked, dProtein, dKept, dTable, dRows, dOut;
         DevBuf<long long> dSeqOff, dRowOff, dOutOff;
         DevBuf<int> dRecs, dFamFirst, dAlnlen, dCount;
-        hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-        double st[KA_COD_STATS] = {};
+        double st[KA_COD_STATS] = {};          // [3], [4] create's launches and waits, [5], [6] the last backtranslation's
 
         ~ka_cod_fam()
         {
                 if (inp) ka_in_fam_destroy(inp);
-                for (auto& e : ev)
-                        if (e) (void)hipEventDestroy(e);
-                dText.release(); dPacked.release(); dProtein.release(); dKept.release(); dTable.release(); dRows.release(); dOut.release();
-                dSeqOff.release(); dRowOff.release(); dOutOff.release(); dRecs.release(); dFamFirst.release(); dAlnlen.release(); dCount.release();
         }
         int rec(int i, int k) const { return devRecs[(size_t)i * KA_COD_DEVREC + k]; }
         int nKept(int i) const { return rec(i, KA_COD_CODONS) - rec(i, KA_COD_STOPS); }
-        std::string where(const std::string& me, int f, int i) const
-        {
-                return me + ": family " + std::to_string(f) + ", sequence " + std::to_string(i - famFirst[f]);
-        }
+        std::string where(const std::string& me, int f, int i) const { return ka_fam_where(me, f, i - famFirst[f]); }
         int create(const std::string& me, const uint8_t* text, const long long* seq_off, const uint8_t* names, const long long* name_off);
         int back(const std::string& me, const uint8_t* rows, long long n_bytes, const int* alnlens, uint8_t gap_char);
 };
 
 int ka_cod_fam::create(const std::string& me, const uint8_t* text, const long long* seq_off, const uint8_t* names, const long long* name_off)
 {
-        HIPCHK(hipSetDevice(device));
-        for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-        int nLaunch = 0, nSync = 0;
+        if (open(5)) return KA_FAIL;
+        begin();
         devRecs.assign((size_t)nSeq * KA_COD_DEVREC, 0);
         std::vector<uint8_t> plane((size_t)nBytes);
         if (dText.alloc((size_t)nBytes) || dPacked.alloc((size_t)nBytes) || dProtein.alloc((size_t)nBytes) || dKept.alloc((size_t)nBytes) ||
@@ -114,11 +97,8 @@ int ka_cod_fam::create(const std::string& me, const uint8_t* text, const long lo
         // (the plane as it lies: a sequence's protein fills at most the first third of its range, and where it ends is in the
         // records that come down with it)
         if (nBytes) HIPCHK(hipMemcpyAsync(plane.data(), dProtein.p, (size_t)nBytes, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        nSync++;
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, ev[0], ev[1]); st[0] = ms;
-        (void)hipEventElapsedTime(&ms, ev[1], ev[2]); st[1] = ms;
+        if (wait()) return KA_FAIL;
+        st[0] = ms(0, 1); st[1] = ms(1, 2);
         st[3] = nLaunch; st[4] = nSync; st[7] = (double)nBytes;
 
         // ---- the host step: errors in batch order, then the proteins one after the other ----
@@ -161,7 +141,7 @@ int ka_cod_fam::back(const std::string& me, const uint8_t* rows, long long n_byt
         if (need != n_bytes)
                 return fail(me + ": " + std::to_string(n_bytes) + " bytes of rows, the alignment lengths say " + std::to_string(need));
         HIPCHK(hipSetDevice(device));
-        int nLaunch = 0, nSync = 0;
+        begin();
         std::vector<int> count(nSeq, 0);
         std::vector<uint8_t> out((size_t)outBytes);
         if (dRows.alloc((size_t)need) || dOut.alloc((size_t)outBytes) || dCount.alloc(nSeq) || dFamFirst.alloc((size_t)nFam + 1) ||
@@ -181,10 +161,8 @@ int ka_cod_fam::back(const std::string& me, const uint8_t* rows, long long n_byt
         HIPCHK(hipEventRecord(ev[4], stream));
         HIPCHK(hipMemcpyAsync(out.data(), dOut.p, (size_t)outBytes, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipMemcpyAsync(count.data(), dCount.p, sizeof(int) * (size_t)nSeq, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        nSync++;
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, ev[3], ev[4]); st[2] = ms;
+        if (wait()) return KA_FAIL;
+        st[2] = ms(3, 4);
         st[5] = nLaunch; st[6] = nSync;
         for (int f = 0; f < nFam; f++)
                 for (int i = famFirst[f]; i < famFirst[f + 1]; i++)
@@ -206,7 +184,7 @@ extern "C" int ka_cod_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, c
         const std::string me("ka_cod_fam_create");
         if (!ctx || !out || (names == nullptr) != (name_off == nullptr)) return fail(me + ": bad arguments");
         *out = nullptr;
-        if (ka_in_check_first_named(me, n_fam, fam_first)) return KA_FAIL;
+        if (ka_fam_check_first(me, n_fam, fam_first)) return KA_FAIL;
         if (!seq_off) return fail(me + ": bad arguments");
         const int n = fam_first[n_fam];
         if (ka_in_check_named(me, n_fam, fam_first, seq_off, seq_off[n])) return KA_FAIL;
@@ -215,24 +193,18 @@ extern "C" int ka_cod_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, c
                 for (int i = 0; i < n; i++)
                         if (name_off[i + 1] < name_off[i]) return fail(me + ": name_off does not ascend");
         std::unique_ptr<ka_cod_fam> h(new ka_cod_fam);
-        if (ka_ctx_device_stream(ctx, &h->device, &h->stream)) return fail(me + ": bad context");
+        if (h->attach(ctx)) return fail(me + ": bad context");
         h->ctx = ctx;
         h->nFam = n_fam; h->nSeq = n; h->nBytes = seq_off[n];
         h->famFirst.assign(fam_first, fam_first + n_fam + 1);
-        if (h->create(me, text, seq_off, names, name_off)) {
-                (void)hipStreamSynchronize(h->stream);           // (nothing of the caller's is read after a refusal)
-                return KA_FAIL;
-        }
+        if (h->create(me, text, seq_off, names, name_off)) return h->refused();
         *out = h.release();
         return KA_OK;
 }
 
 extern "C" void ka_cod_fam_destroy(ka_cod_fam* h)
 {
-        if (!h) return;
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        delete h;
+        ka_stage_destroy(h);
 }
 
 extern "C" int ka_cod_fam_sequences(ka_cod_fam* h, int* recs_out)

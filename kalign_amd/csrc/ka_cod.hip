@@ -1,7 +1,6 @@
 // ka_cod.hip -- the kernels of the codon stage (gfx950, wave64): raw coding DNA of a batch of families -> upper-cased
 // residues, proteins and stop-free codons, and protein rows -> codon rows.  A wave per sequence or row, four per workgroup;
-// the walks go KA_IN_STEP bytes a step as four ballots of 64, consecutive lanes on consecutive bytes, and a kept byte's
-// place is the count carried so far plus the population count of the lower lanes of its ballot (as ka_in.hip's walks).
+// the walks are ka_walk.h's.
 //   cod_pack       a sequence's raw bytes: residues, gap characters, dropped bytes and the offset of the first byte >= 128;
 //                  the residues, upper-cased, compacted from seqOff[i] on in a plane the size of the text.
 //   cod_translate  a codon per lane, 64 a step: three packed residues -> 2-bit codes -> the 64-letter table staged in LDS, X
@@ -16,18 +15,9 @@
 // Every store is held inside the sequence's or row's own range regardless of what the bytes say.
 #include "ka_cod.h"
 #include "ka_msa.h"          // ka_fam_find
+#include "ka_walk.h"
 
 namespace {
-
-// the bytes of one step of n bytes, -1 at and past the end
-__device__ __forceinline__ void cod_step(const uint8_t* raw, long long n, long long c0, int lane, int* b)
-{
-#pragma unroll
-        for (int q = 0; q < KA_IN_STEP / 64; q++) {
-                const long long c = c0 + 64 * q + lane;
-                b[q] = c < n ? (int)raw[c] : -1;
-        }
-}
 
 __global__ __launch_bounds__(KA_COD_THREADS) void cod_pack(KaCodTab a)
 {
@@ -37,11 +27,11 @@ __global__ __launch_bounds__(KA_COD_THREADS) void cod_pack(KaCodTab a)
         const long long o = a.seqOff[i], n = a.seqOff[i + 1] - o;
         const uint8_t* raw = a.text + o;
         uint8_t* out = a.packed + o;
-        const unsigned long long below = (1ull << lane) - 1ull;
+        const unsigned long long below = ka_lanes_below(lane);
         long long residues = 0, gaps = 0, dropped = 0, bad = -1;
         for (long long c0 = 0; c0 < n; c0 += KA_IN_STEP) {
                 int b[KA_IN_STEP / 64];
-                cod_step(raw, n, c0, lane, b);
+                ka_walk_step<KA_IN_STEP>(raw, n, c0, lane, b);
 #pragma unroll
                 for (int q = 0; q < KA_IN_STEP / 64; q++) {
                         const bool res = ka_in_is_letter(b[q]), pun = ka_in_is_punct(b[q]);
@@ -72,7 +62,7 @@ __global__ __launch_bounds__(KA_COD_THREADS) void cod_translate(KaCodTab a)
         const uint8_t* in = a.packed + o;
         uint8_t* prot = a.protein + o;
         uint8_t* kept = a.kept + o;
-        const unsigned long long below = (1ull << lane) - 1ull;
+        const unsigned long long below = ka_lanes_below(lane);
         long long run = 0, stops = 0, xs = 0;
         for (long long c0 = 0; c0 < nCod; c0 += 64) {
                 const long long c = c0 + lane;
@@ -112,11 +102,11 @@ __global__ __launch_bounds__(KA_COD_THREADS) void cod_back(KaCodBackTab a)
         const uint8_t* kept = a.kept + a.seqOff[r];
         const long long nKept = a.recs[r * KA_COD_DEVREC + KA_COD_CODONS] - a.recs[r * KA_COD_DEVREC + KA_COD_STOPS];
         const int gap = a.gap;
-        const unsigned long long below = (1ull << lane) - 1ull;
+        const unsigned long long below = ka_lanes_below(lane);
         long long run = 0;
         for (long long c0 = 0; c0 < W; c0 += KA_IN_STEP) {
                 int b[KA_IN_STEP / 64];
-                cod_step(in, W, c0, lane, b);
+                ka_walk_step<KA_IN_STEP>(in, W, c0, lane, b);
 #pragma unroll
                 for (int q = 0; q < KA_IN_STEP / 64; q++) {
                         const bool ch = b[q] >= 0 && b[q] != gap;
@@ -141,21 +131,18 @@ __global__ __launch_bounds__(KA_COD_THREADS) void cod_back(KaCodBackTab a)
 
 void ka_cod_run_pack(const KaCodTab& a, hipStream_t s, int* launches)
 {
-        constexpr int kSeqs = KA_COD_THREADS / 64;
-        cod_pack<<<(unsigned)(((long long)a.nSeq + kSeqs - 1) / kSeqs), KA_COD_THREADS, 0, s>>>(a);
+        cod_pack<<<ka_wave_grid(a.nSeq, KA_COD_THREADS), KA_COD_THREADS, 0, s>>>(a);
         ++*launches;
 }
 
 void ka_cod_run_translate(const KaCodTab& a, hipStream_t s, int* launches)
 {
-        constexpr int kSeqs = KA_COD_THREADS / 64;
-        cod_translate<<<(unsigned)(((long long)a.nSeq + kSeqs - 1) / kSeqs), KA_COD_THREADS, 0, s>>>(a);
+        cod_translate<<<ka_wave_grid(a.nSeq, KA_COD_THREADS), KA_COD_THREADS, 0, s>>>(a);
         ++*launches;
 }
 
 void ka_cod_run_back(const KaCodBackTab& a, hipStream_t s, int* launches)
 {
-        constexpr int kRows = KA_COD_THREADS / 64;
-        cod_back<<<(unsigned)(((long long)a.nSeq + kRows - 1) / kRows), KA_COD_THREADS, 0, s>>>(a);
+        cod_back<<<ka_wave_grid(a.nSeq, KA_COD_THREADS), KA_COD_THREADS, 0, s>>>(a);
         ++*launches;
 }

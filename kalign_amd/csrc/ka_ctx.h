@@ -1,5 +1,6 @@
 // ka_ctx.h -- what the host-side translation units of the library share (round 5: ka_api.cpp was one file of 2700 lines): the
-// context, the environment switches, the kernel launchers' prototypes and the functions one unit calls in another.  Library-internal:
+// context, the environment switches, the kernel launchers' prototypes, the functions one unit calls in another, the device
+// buffer (DevBuf) and the base of the stage handles (KaStage).  Library-internal:
 // nothing here is part of the C ABI (include/kalign_amd.h).
 //   ka_api.cpp   contexts, upload, the runs (ka_tree_run / _refine / _sync / _download), rows, realignment tree, ka_run_encoded, partial runs
 //   ka_plan.cpp  the launch planner: levels, leaf / queued / chained launches, clusters, spare workgroups by a simulated schedule -- over
@@ -21,6 +22,7 @@
 #include "ka_device.h"
 #include "ka_plan.h"         // KaEnv, KaPlan (the host-only base of the context), fail()
 #include "ka_forest.h"       // the records of the realignment-tree kernels
+#include "ka_fam.h"          // the family table's rule and what else the stages of a batch of families share on the host
 
 // the task kernels live in ten translation units (ka_kernels.hip, -DKA_UNIT=0..9); unit 5 is launched through unit 4
 extern "C" void ka_unit0_launch(const KaTreeDev* D, const int2* blocks_dev, int nblocks, int chain, hipStream_t stream);   // 8 waves
@@ -76,10 +78,23 @@ extern "C" long long ka_scratch_bytes_host_big(long long la, long long lb, long 
                 }                                                                         \
         } while (0)
 
+// A grow-only device buffer that frees itself with its owner.  An owner that sets its device and waits for its stream does so
+// in the body of its destroy function or destructor: the members go after it.  No object with static or thread storage owns
+// one (it would free after the runtime is gone), and no pointer of one is handed to something that outlives it.
 template <typename T>
 struct DevBuf {
         T* p = nullptr;
         size_t n = 0;
+        DevBuf() = default;
+        DevBuf(const DevBuf&) = delete;
+        DevBuf& operator=(const DevBuf&) = delete;
+        DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+        DevBuf& operator=(DevBuf&& o) noexcept
+        {
+                if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+                return *this;
+        }
+        ~DevBuf() { release(); }
         int alloc(size_t count)
         {
                 if (count <= n && p) return 0;
@@ -90,6 +105,59 @@ struct DevBuf {
         }
         void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
+
+struct ka_ctx;
+// the device and the stream of a context (ka_api.cpp); not 0: no context
+KA_INTERNAL int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);
+
+// What the handle of a stage of a batch of families (ka_sum_fam, ka_in_fam, ka_cod_fam, ka_out_fam) holds of its context and
+// of its calls: device and stream, a few events, and the counters of kernel launches (counted by the launchers) and host waits
+// that the stage's *_stats hand out.  Which call resets them, and where they go in st[], is the stage's own.
+struct KaStage {
+        int device = 0;
+        hipStream_t stream = nullptr;
+        hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+        int nLaunch = 0, nSync = 0;
+
+        KaStage() = default;
+        KaStage(const KaStage&) = delete;
+        KaStage& operator=(const KaStage&) = delete;
+        ~KaStage()
+        {
+                for (auto& e : ev)
+                        if (e) (void)hipEventDestroy(e);
+        }
+        int attach(ka_ctx* ctx) { return ka_ctx_device_stream(ctx, &device, &stream); }
+        // the handle's device made current and its first n events created
+        int open(int n)
+        {
+                HIPCHK(hipSetDevice(device));
+                for (int k = 0; k < n; k++) HIPCHK(hipEventCreate(&ev[k]));
+                return KA_OK;
+        }
+        // a call that launches: nothing launched, nothing waited for yet
+        void begin() { nLaunch = nSync = 0; }
+        // the host waits for the stream: counted where it happens
+        int wait()
+        {
+                HIPCHK(hipStreamSynchronize(stream));
+                nSync++;
+                return KA_OK;
+        }
+        // a create that was refused after its uploads went out: nothing of the caller's is read after the refusal
+        int refused() { (void)hipStreamSynchronize(stream); return KA_FAIL; }
+        float ms(int a = 0, int b = 1) { float m = 0.0f; (void)hipEventElapsedTime(&m, ev[a], ev[b]); return m; }
+};
+
+// a stage's destroy: the device, the stream's last work, then the handle and with it its buffers and events
+template <typename H>
+void ka_stage_destroy(H* h)
+{
+        if (!h) return;
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        delete h;
+}
 
 // The aligned rows that the last rows_build left in d_rows: n rows (0: nothing that a tree can be built from) `stride`
 // apart, row i the first alen[i] columns of its tree's alignment, the rest gap.  one_tree: all of one alignment -- what

@@ -313,9 +313,6 @@ extern "C" void ka_dist_destroy(ka_dist* d)
         if (!d) return;
         if (d->c) (void)hipSetDevice(d->c->device);
         if (d->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(d->comm);
-        for (auto& m : d->moves) { m.d_members.release(); m.d_moff.release(); }
-        for (auto& b : d->top_blocks) b.release();
-        d->d_mine.release(); d->d_counts.release(); d->d_gpaths.release(); d->d_colbuf.release(); d->d_goff.release();
         if (d->h_head) (void)hipHostFree(d->h_head);
         delete d;
 }
@@ -362,8 +359,6 @@ extern "C" int ka_dist_plan(ka_dist* d)
                 if (d->run_rank[t] == d->rank && !is_top[t]) d->mine_sub.push_back(t);
         }
         // the hand-overs: a child of a top task that sits on another rank than the one running the parent
-        for (auto& m : d->moves) { m.d_members.release(); m.d_moff.release(); }
-        for (auto& b : d->top_blocks) b.release();
         d->moves.clear(); d->top_moves.assign(n_top, std::vector<int>()); d->top_blocks.clear(); d->top_blocks.resize(n_top);
         std::vector<int> holder(2 * numseq - 1, -1);
         for (int t = 0; t < n_tasks; t++) if (!is_top[t]) holder[c->abc[3 * t + 2]] = d->run_rank[t];

@@ -25,8 +25,6 @@
 #include "ka_ens_core.h"
 #include "ka_ens_union.h"     // Uf, topo_order, ka_ens_fill: shared with ka_ens_fam.cpp
 
-int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
-
 // ---------------------------------------------------------------- the core ----------------------------------------------------------------
 
 KaEnsCore::~KaEnsCore()
@@ -36,15 +34,9 @@ KaEnsCore::~KaEnsCore()
                 if (ready[b]) (void)hipEventDestroy(ready[b]);
                 if (wBeg[b]) (void)hipEventDestroy(wBeg[b]);
                 if (wEnd[b]) (void)hipEventDestroy(wEnd[b]);
-                dOut[b].release();
         }
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
-        for (auto& r : dRows) r.release();
-        dFams.release(); dFirstSeq.release(); dBlkFirst.release(); dOffs.release(); dLens.release(); dCol.release(); dMemW.release();
-        dMemCell.release(); dColX.release(); dXTab.release(); dSup.release(); dNp.release(); dCnt.release();
-        dMemRowOff.release(); dXRowOff.release(); dPairOff.release(); dRowTot.release(); dRowBase.release(); dRes.release(); dResX.release();
-        dRowsX.release(); dScore.release(); dConf.release(); dColConf.release();
 }
 
 void KaEnsCore::close()
@@ -401,8 +393,6 @@ struct ka_ens {
         double st[KA_ENS_STATS] = {};
         long long levelCount[KA_ENS_MAX_RUNS + 1] = {};
         double levelMs[KA_ENS_MAX_RUNS + 1] = {};
-
-        ~ka_ens() { dPairStart.release(); dEnt.release(); }
 
         // the family's tables once n_runs is known
         int open(const char* who, int n_runs)
@@ -987,7 +977,6 @@ extern "C" int ka_ens_merge(ka_ens* a, ka_ens* b, ka_ens** out)
                 hipStream_t s = o->core.stream;
                 rc = o->derive_table(who, x, [s](int mode, const KaEnsArgs& y) { ka_poar_launch_merge(mode, y, s); });
         }
-        psA.release(); psB.release(); entA.release(); entB.release();
         if (rc) return rc;
         *out = o.release();
         return KA_OK;
@@ -1020,7 +1009,6 @@ extern "C" int ka_ens_select(ka_ens* e, const int* members, int n, ka_ens** out)
                 hipStream_t s = o->core.stream;
                 rc = o->derive_table(who, x, [s](int mode, const KaEnsArgs& y) { ka_poar_launch_select(mode, y, s); });
         }
-        ps.release(); ent.release();
         if (rc) return rc;
         *out = o.release();
         return KA_OK;

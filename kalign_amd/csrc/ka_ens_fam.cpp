@@ -26,12 +26,8 @@ const char* const kWhyRes = "residue indices must stay below 4096 (the reference
 // the families and their sequences: fam_first ascends from 0, no family is empty, every family's lengths as ka_ens_create takes them
 int ens_fam_check_seqs(const std::string& me, int n_fam, const int* fam_first, const int* lens)
 {
-        if (n_fam < 1 || !fam_first || !lens) return fail(me + ": bad arguments");
-        if (fam_first[0] != 0) return fail(me + ": fam_first does not ascend from 0 to numseq");
-        for (int f = 0; f < n_fam; f++) {
-                if (fam_first[f + 1] < fam_first[f]) return fail(me + ": fam_first does not ascend from 0 to numseq");
-                if (fam_first[f + 1] == fam_first[f]) return fail(me + ": empty family");
-        }
+        if (!lens) return fail(me + ": bad arguments");
+        if (ka_fam_check_first(me, n_fam, fam_first)) return KA_FAIL;
         long long residues = 0;
         for (int f = 0; f < n_fam; f++) {
                 const std::string fam = me + ": family " + std::to_string(f);
@@ -257,8 +253,7 @@ extern "C" int ka_ens_fam_add_member(ka_ens_fam* h, int k, const uint8_t* rows, 
         if (!h || k < 0 || k >= h->core.R) return fail("ka_ens_fam_add_member: bad arguments");
         KaEnsCore& c = h->core;
         if (ens_fam_check("ka_ens_fam_add_member", c.F, c.famFirst.data(), c.lens.data(), rows, alnlens, false)) return KA_FAIL;
-        long long ro = 0;
-        for (int f = 0; f < c.F; f++) ro += (long long)c.fams[f].N * (alnlens[f] + 1);
+        const long long ro = ka_fam_row_bytes(c.F, c.famFirst.data(), alnlens);
         HIPCHK(hipSetDevice(c.device));
         h->begin();
         if (c.dRows[k].alloc((size_t)ro)) return fail("ka_ens_fam_add_member: out of device memory");

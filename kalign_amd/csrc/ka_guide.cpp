@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "kalign_amd.h"
+#include "ka_ctx.h"          // ka_ctx_device_stream, the family table's rule (its fail() sets what ka_fail_message sets)
 #include "ka_kmeans.h"
 
 namespace {
@@ -318,7 +319,6 @@ thread_local KmDevice g_km;
 double g_last_bisect_ms = 0.0;
 int g_last_bisect_device = 0;
 }
-int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // ka_api.cpp
 extern "C" double ka_guide_last_bisect_ms(int* on_device)
 {
         if (on_device) *on_device = g_last_bisect_device;
@@ -397,11 +397,7 @@ static int guide_forest_from(const char* who, int n_fam, const int* fam_first, c
                              const float* dm_scale, int* tasks_abc, int* n_tasks_out, float* seq_distances)
 {
         const std::string me(who);
-        if (fam_first[0] != 0) return ka_fail_message((me + ": fam_first does not ascend from 0 to numseq").c_str());
-        for (int f = 0; f < n_fam; f++) {
-                if (fam_first[f + 1] < fam_first[f]) return ka_fail_message((me + ": fam_first does not ascend from 0 to numseq").c_str());
-                if (fam_first[f + 1] == fam_first[f]) return ka_fail_message((me + ": empty family").c_str());
-        }
+        if (ka_fam_check_first(me, n_fam, fam_first)) return KA_FAIL;
         const int numseq = fam_first[n_fam];
         for (int i = 0; i < numseq; i++)
                 if (lens[i] < 1) return ka_fail_message((me + ": zero-length sequence").c_str());

@@ -16,15 +16,12 @@
 #include <string>
 #include <vector>
 #ifdef KA_IN_HOST_ONLY
-#include "kalign_amd.h"
-int fail(const std::string& m);
+#include "ka_fam.h"
 #else
 #include <chrono>
 #include <memory>
 #include "ka_ctx.h"
 #include "ka_in.h"
-
-int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
 #endif
 
 namespace {
@@ -91,20 +88,9 @@ int detect(const std::string& me, const long long* freq, int* biotype)
         return KA_OK;
 }
 
-int check_fam_first(const std::string& me, int n_fam, const int* fam_first)
-{
-        if (n_fam < 1 || !fam_first) return fail(me + ": bad arguments");
-        if (fam_first[0] != 0) return fail(me + ": fam_first does not ascend from 0 to numseq");
-        for (int f = 0; f < n_fam; f++) {
-                if (fam_first[f + 1] < fam_first[f]) return fail(me + ": fam_first does not ascend from 0 to numseq");
-                if (fam_first[f + 1] == fam_first[f]) return fail(me + ": empty family");
-        }
-        return KA_OK;
-}
-
 int in_check(const std::string& me, int n_fam, const int* fam_first, const long long* seq_off, long long n_bytes)
 {
-        if (check_fam_first(me, n_fam, fam_first)) return KA_FAIL;
+        if (ka_fam_check_first(me, n_fam, fam_first)) return KA_FAIL;
         if (!seq_off || n_bytes < 0) return fail(me + ": bad arguments");
         const int n = fam_first[n_fam];
         if (seq_off[0] != 0 || seq_off[n] != n_bytes) return fail(me + ": seq_off does not ascend from 0 to n_bytes");
@@ -112,8 +98,8 @@ int in_check(const std::string& me, int n_fam, const int* fam_first, const long 
                 for (int i = fam_first[f]; i < fam_first[f + 1]; i++) {
                         if (seq_off[i + 1] < seq_off[i]) return fail(me + ": seq_off does not ascend from 0 to n_bytes");
                         if (seq_off[i + 1] - seq_off[i] > INT32_MAX)
-                                return fail(me + ": family " + std::to_string(f) + ", sequence " + std::to_string(i - fam_first[f]) + ": " +
-                                            std::to_string(seq_off[i + 1] - seq_off[i]) + " bytes; a sequence holds fewer than 2^31");
+                                return fail(ka_fam_where(me, f, i - fam_first[f]) + ": " + std::to_string(seq_off[i + 1] - seq_off[i]) +
+                                            " bytes; a sequence holds fewer than 2^31");
                 }
         return KA_OK;
 }
@@ -159,7 +145,7 @@ extern "C" int ka_in_detect(const long long* freq128, int* biotype_out)
 
 extern "C" int ka_in_order(int n_fam, const int* fam_first, const int* residues, const uint8_t* names, const long long* name_off, int* order_out)
 {
-        if (check_fam_first("ka_in_order", n_fam, fam_first)) return KA_FAIL;
+        if (ka_fam_check_first("ka_in_order", n_fam, fam_first)) return KA_FAIL;
         if (!residues || !order_out || (names == nullptr) != (name_off == nullptr)) return fail("ka_in_order: bad arguments");
         if (name_off)
                 for (int i = 0; i < fam_first[n_fam]; i++)
@@ -173,8 +159,7 @@ extern "C" int ka_in_fam_check(int n_fam, const int* fam_first, const long long*
         return in_check("ka_in_fam_check", n_fam, fam_first, seq_off, n_bytes);
 }
 
-// the check's two halves under another stage's name (library-internal: ka_cod.cpp)
-int ka_in_check_first_named(const std::string& me, int n_fam, const int* fam_first) { return check_fam_first(me, n_fam, fam_first); }
+// the check under another stage's name (ka_fam.h: the codon stage)
 int ka_in_check_named(const std::string& me, int n_fam, const int* fam_first, const long long* seq_off, long long n_bytes)
 {
         return in_check(me, n_fam, fam_first, seq_off, n_bytes);
@@ -182,10 +167,8 @@ int ka_in_check_named(const std::string& me, int n_fam, const int* fam_first, co
 
 #ifndef KA_IN_HOST_ONLY
 
-struct ka_in_fam {
+struct ka_in_fam : KaStage {
         ka_ctx* ctx = nullptr;
-        int device = 0;
-        hipStream_t stream = nullptr;
         int nFam = 0, nSeq = 0;
         long long nBytes = 0, size = 0;        // raw bytes; residues
         std::vector<int> famFirst, order, lens;          // lens[p]: residues of sorted position p
@@ -201,24 +184,8 @@ struct ka_in_fam {
         DevBuf<int> dFamFirst, dRecs, dOrder;
         DevBuf<unsigned long long> dFreq, dNoCode;
         DevBuf<int8_t> dTables;
-        hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
         double st[KA_IN_STATS] = {};
-        int nLaunch = 0, nSync = 0;
 
-        ~ka_in_fam()
-        {
-                for (auto& e : ev)
-                        if (e) (void)hipEventDestroy(e);
-                dText.release(); dBiotype.release(); dLetters.release(); dTree.release(); dCodes.release(); dSeqOff.release(); dOutOff.release();
-                dFamFirst.release(); dRecs.release(); dOrder.release(); dFreq.release(); dNoCode.release(); dTables.release();
-        }
-        // the host waits for the stream: counted where it happens
-        int wait()
-        {
-                HIPCHK(hipStreamSynchronize(stream));
-                nSync++;
-                return KA_OK;
-        }
         int create(const std::string& me, const uint8_t* text, const long long* seq_off, const uint8_t* names, const long long* name_off,
                    const int* biotype_in);
         int run(const std::string& me, int biotype, const float* subm, const float* scal, int n_anchors, float weight, int realign_iterations,
@@ -234,8 +201,7 @@ struct ka_in_fam {
 int ka_in_fam::create(const std::string& me, const uint8_t* text, const long long* seq_off, const uint8_t* names, const long long* name_off,
                       const int* biotype_in)
 {
-        HIPCHK(hipSetDevice(device));
-        for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+        if (open(4)) return KA_FAIL;
         std::vector<int> devRecs((size_t)nSeq * KA_IN_DEVREC, 0);
         std::vector<unsigned long long> noCode(nFam, 0);
         freq.assign((size_t)nFam * KA_IN_BINS, 0);
@@ -260,7 +226,7 @@ int ka_in_fam::create(const std::string& me, const uint8_t* text, const long lon
         if (wait()) return KA_FAIL;
 
         // ---- the host step: errors, biotype, status, order, offsets ----
-        auto where = [&](int f, int i) { return me + ": family " + std::to_string(f) + ", sequence " + std::to_string(i - famFirst[f]); };
+        auto where = [&](int f, int i) { return ka_fam_where(me, f, i - famFirst[f]); };
         for (int f = 0; f < nFam; f++)
                 for (int i = famFirst[f]; i < famFirst[f + 1]; i++) {
                         const int bad = devRecs[(size_t)i * KA_IN_DEVREC + KA_IN_BAD];
@@ -328,9 +294,7 @@ int ka_in_fam::create(const std::string& me, const uint8_t* text, const long lon
         HIPCHK(hipMemcpyAsync(noCode.data(), dNoCode.p, sizeof(unsigned long long) * nFam, hipMemcpyDeviceToHost, stream));
         if (wait()) return KA_FAIL;
         for (int f = 0; f < nFam; f++) famRecs[(size_t)f * KA_IN_FAMREC + 4] = (int)std::min<unsigned long long>(noCode[f], INT32_MAX);
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, ev[0], ev[1]); st[0] = ms;
-        (void)hipEventElapsedTime(&ms, ev[2], ev[3]); st[1] = ms;
+        st[0] = ms(0, 1); st[1] = ms(2, 3);
         st[4] = (double)nBytes;
         // the raw text has served: the planes are what every later call reads
         dText.release();
@@ -396,7 +360,7 @@ extern "C" int ka_in_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, co
         const std::string me("ka_in_fam_create");
         if (!ctx || !out || (names == nullptr) != (name_off == nullptr)) return fail(me + ": bad arguments");
         *out = nullptr;
-        if (check_fam_first(me, n_fam, fam_first)) return KA_FAIL;
+        if (ka_fam_check_first(me, n_fam, fam_first)) return KA_FAIL;
         if (!seq_off) return fail(me + ": bad arguments");
         const int n = fam_first[n_fam];
         if (in_check(me, n_fam, fam_first, seq_off, seq_off[n])) return KA_FAIL;
@@ -409,14 +373,11 @@ extern "C" int ka_in_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, co
                         if (biotype_in[f] < -1 || biotype_in[f] > 1)
                                 return fail(me + ": family " + std::to_string(f) + ": biotype " + std::to_string(biotype_in[f]) + " is not -1, 0 or 1");
         std::unique_ptr<ka_in_fam> h(new ka_in_fam);
-        if (ka_ctx_device_stream(ctx, &h->device, &h->stream)) return fail(me + ": bad context");
+        if (h->attach(ctx)) return fail(me + ": bad context");
         h->ctx = ctx;
         h->nFam = n_fam; h->nSeq = n; h->nBytes = seq_off[n];
         h->famFirst.assign(fam_first, fam_first + n_fam + 1);
-        if (h->create(me, text, seq_off, names, name_off, biotype_in)) {
-                (void)hipStreamSynchronize(h->stream);           // (nothing of the caller's is read after a refusal)
-                return KA_FAIL;
-        }
+        if (h->create(me, text, seq_off, names, name_off, biotype_in)) return h->refused();
         h->st[2] = h->nLaunch; h->st[3] = h->nSync;
         *out = h.release();
         return KA_OK;
@@ -424,10 +385,7 @@ extern "C" int ka_in_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, co
 
 extern "C" void ka_in_fam_destroy(ka_in_fam* h)
 {
-        if (!h) return;
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        delete h;
+        ka_stage_destroy(h);
 }
 
 extern "C" int ka_in_fam_sequences(ka_in_fam* h, int* recs_out)

@@ -1,40 +1,21 @@
 // ka_in.hip -- the kernels of the input stage (gfx950, wave64): raw text of a batch of families -> counts, checksums and
-// histograms, then the three encodings in sorted order.  Both walk a sequence's raw bytes a wave per sequence, KA_IN_STEP
-// bytes a step as four ballots of 64, consecutive lanes on consecutive bytes.
+// histograms, then the three encodings in sorted order.  Both walk a sequence's raw bytes a wave per sequence (ka_walk.h).
 //   in_scan     a wave per sequence in input order, sixteen consecutive sequences per workgroup.  Residues, gap characters,
 //               dropped bytes, the offset of the first byte >= 128 and the GCG checksum per sequence; the family's 128-bin
 //               histogram.  A residue's index is the residues before this step, plus the population counts of the step's
 //               earlier ballots, plus that of the lower lanes of its own; the lanes' terms (index % 57 + 1) * upper-case byte
 //               are summed in 64-bit integers and reduced % 10000 once (the remainder of the sum is what the reference's
 //               running remainder comes to; fewer than 2^31 terms below 2^13 each).  The histogram: every wave counts into its own 128 LDS counters by integer
-//               atomics; after the barrier one thread per bin adds up the waves of a family and sends the sum with one 64-bit
-//               global atomic per family the workgroup meets (it may hold the end of one family and the start of the next).
-//               Integer sums in any order: the result does not depend on scheduling.
+//               atomics; after the barrier one thread per bin folds them into the families' (ka_fold_families).
 //   in_encode   a wave per sorted position, four per workgroup.  The same walk; a residue's place is its index, and the wave
 //               writes the letter as given, its tree code and its alignment code -- through the two tables of its family's
 //               biotype, staged in LDS -- at the position's 64-bit offset in the three planes.  A letter without a code is
 //               written as code 0 and counted per family.  A write is held inside the position's own range regardless.
 #include "ka_in.h"
 #include "ka_msa.h"          // ka_fam_find
+#include "ka_walk.h"
 
 namespace {
-
-// the bytes of one step of a sequence of n raw bytes, -1 at and past its end
-__device__ __forceinline__ void in_step(const uint8_t* raw, long long n, long long c0, int lane, int* b)
-{
-#pragma unroll
-        for (int q = 0; q < KA_IN_STEP / 64; q++) {
-                const long long c = c0 + 64 * q + lane;
-                b[q] = c < n ? (int)raw[c] : -1;
-        }
-}
-
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-        return v;
-}
 
 __global__ __launch_bounds__(KA_IN_SCAN_THREADS) void in_scan(KaInTab a)
 {
@@ -49,11 +30,11 @@ __global__ __launch_bounds__(KA_IN_SCAN_THREADS) void in_scan(KaInTab a)
                 f = ka_fam_find(a.famFirst, a.nFam, (int)i);
                 const uint8_t* raw = a.text + a.seqOff[i];
                 const long long n = a.seqOff[i + 1] - a.seqOff[i];
-                const unsigned long long below = (1ull << lane) - 1ull;
+                const unsigned long long below = ka_lanes_below(lane);
                 long long residues = 0, gaps = 0, dropped = 0, bad = -1, chk = 0;
                 for (long long c0 = 0; c0 < n; c0 += KA_IN_STEP) {
                         int b[KA_IN_STEP / 64];
-                        in_step(raw, n, c0, lane, b);
+                        ka_walk_step<KA_IN_STEP>(raw, n, c0, lane, b);
 #pragma unroll
                         for (int q = 0; q < KA_IN_STEP / 64; q++) {
                                 const bool res = ka_in_is_letter(b[q]), pun = ka_in_is_punct(b[q]);
@@ -70,21 +51,14 @@ __global__ __launch_bounds__(KA_IN_SCAN_THREADS) void in_scan(KaInTab a)
                                 dropped += __popcll(ma & ~(mr | mp | mh));
                         }
                 }
-                chk = wave_sum(chk) % 10000;
+                chk = ka_wave_sum(chk) % 10000;
                 const long long rec = lane == KA_IN_RESIDUES ? residues : lane == KA_IN_GAPS ? gaps : lane == KA_IN_DROPPED ? dropped :
                                       lane == KA_IN_CHECKSUM ? chk : bad;
                 if (lane < KA_IN_DEVREC) a.recs[i * KA_IN_DEVREC + lane] = (int)rec;
         }
         if (lane == 0) famOf[wave] = f;
         __syncthreads();
-        if (threadIdx.x >= KA_IN_BINS) return;
-        unsigned long long acc = 0;
-        for (int w = 0; w < kWaves && famOf[w] >= 0; w++) {
-                acc += hist[w][threadIdx.x];
-                if (w + 1 < kWaves && famOf[w + 1] == famOf[w]) continue;
-                if (acc) atomicAdd(&a.freq[(long long)famOf[w] * KA_IN_BINS + threadIdx.x], acc);
-                acc = 0;
-        }
+        if (threadIdx.x < KA_IN_BINS) ka_fold_families(hist, famOf, threadIdx.x, a.freq, KA_IN_BINS);
 }
 
 __global__ __launch_bounds__(KA_IN_ENC_THREADS) void in_encode(KaInTab a)
@@ -104,12 +78,12 @@ __global__ __launch_bounds__(KA_IN_ENC_THREADS) void in_encode(KaInTab a)
         const int8_t* tAln = tab + (dna ? 0 : 256);
         const uint8_t* raw = a.text + a.seqOff[i];
         const long long len = a.seqOff[i + 1] - a.seqOff[i];
-        const unsigned long long below = (1ull << lane) - 1ull;
+        const unsigned long long below = ka_lanes_below(lane);
         const long long o = a.outOff[p];
         long long run = 0, missing = 0;
         for (long long c0 = 0; c0 < len && run < n; c0 += KA_IN_STEP) {
                 int b[KA_IN_STEP / 64];
-                in_step(raw, len, c0, lane, b);
+                ka_walk_step<KA_IN_STEP>(raw, len, c0, lane, b);
 #pragma unroll
                 for (int q = 0; q < KA_IN_STEP / 64; q++) {
                         const bool res = ka_in_is_letter(b[q]);
@@ -134,14 +108,12 @@ __global__ __launch_bounds__(KA_IN_ENC_THREADS) void in_encode(KaInTab a)
 
 void ka_in_run_scan(const KaInTab& a, hipStream_t s, int* launches)
 {
-        constexpr int kSeqs = KA_IN_SCAN_THREADS / 64;
-        in_scan<<<(unsigned)(((long long)a.nSeq + kSeqs - 1) / kSeqs), KA_IN_SCAN_THREADS, 0, s>>>(a);
+        in_scan<<<ka_wave_grid(a.nSeq, KA_IN_SCAN_THREADS), KA_IN_SCAN_THREADS, 0, s>>>(a);
         ++*launches;
 }
 
 void ka_in_run_encode(const KaInTab& a, hipStream_t s, int* launches)
 {
-        constexpr int kSeqs = KA_IN_ENC_THREADS / 64;
-        in_encode<<<(unsigned)(((long long)a.nSeq + kSeqs - 1) / kSeqs), KA_IN_ENC_THREADS, 0, s>>>(a);
+        in_encode<<<ka_wave_grid(a.nSeq, KA_IN_ENC_THREADS), KA_IN_ENC_THREADS, 0, s>>>(a);
         ++*launches;
 }

@@ -15,9 +15,6 @@
 #include "ka_ctx.h"
 #include "ka_out.h"
 
-int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
-int ka_sum_check_named(const std::string& me, int n_fam, const int* fam_first, const uint8_t* rows, const int* alnlens);   // (ka_sum.cpp)
-
 namespace {
 
 // What the reference's CLI writes after a run, for a protein (0) and for a DNA (1) family alike: write_msa_msf tests msa->L
@@ -36,7 +33,7 @@ int names_check(const std::string& me, int n_fam, const int* fam_first, const ui
                 if (name_off[i + 1] < name_off[i]) return fail(me + ": name_off does not ascend");
         for (int f = 0; f < n_fam; f++)
                 for (int i = fam_first[f]; i < fam_first[f + 1]; i++) {
-                        const std::string at = me + ": family " + std::to_string(f) + ", sequence " + std::to_string(i - fam_first[f]);
+                        const std::string at = ka_fam_where(me, f, i - fam_first[f]);
                         const long long n = name_off[i + 1] - name_off[i];
                         if (n == 0) return fail(at + ": empty name");
                         if (n > KA_OUT_NAME_MAX) return fail(at + ": name of " + std::to_string(n) + " bytes; a name holds 1 to 255");
@@ -130,9 +127,7 @@ long long out_layout(const std::vector<KaOutFam>& fams, const std::vector<long l
 
 } // namespace
 
-struct ka_out_fam {
-        int device = 0;
-        hipStream_t stream = nullptr;
+struct ka_out_fam : KaStage {
         uint8_t gap = '-';
         int nFam = 0, numseq = 0;
         long long bytes = 0, cells = 0, cols = 0;      // of the packed rows; sum of N W; sum of W
@@ -153,19 +148,9 @@ struct ka_out_fam {
         DevBuf<uint8_t> dRows, dNames, dHdr, dOut;
         DevBuf<float> dRes, dCol;
         DevBuf<unsigned long long> dOffender;
-        hipEvent_t ev[2] = { nullptr, nullptr };
-        double st[KA_OUT_STATS] = {};                  // device ms of the row pass [0] and of the last fill [1]; [2], [3] from the counters
-        int nLaunch = 0, nSync = 0;                    // of the last writer
+        double st[KA_OUT_STATS] = {};                  // device ms of the row pass [0] and of the last fill [1]; [2], [3] the last writer's counters
         int rowLaunch = 0, rowSync = 0;                // of a row pass no writer has counted yet
 
-        ~ka_out_fam()
-        {
-                for (auto& e : ev)
-                        if (e) (void)hipEventDestroy(e);
-                dFams.release(); dRowFirst.release(); dRecs.release(); dNameOff.release(); dFamOff.release(); dRowOut.release(); dRows.release();
-                dNames.release(); dHdr.release(); dOut.release(); dRes.release(); dCol.release(); dOffender.release();
-        }
-        float ms() { float m = 0.0f; (void)hipEventElapsedTime(&m, ev[0], ev[1]); return m; }
         KaOutTab tab() const
         {
                 KaOutTab a{};
@@ -192,8 +177,7 @@ int ka_out_fam::create(const std::string& me, int n_fam, const int* fam_first, c
         numseq = fam_first[n_fam];
         rowFirst.assign(fam_first, fam_first + nFam + 1);
         out_families(n_fam, fam_first, alnlens, names_in, name_off, fams, names, nameOff, &bytes, &cells, &cols);
-        HIPCHK(hipSetDevice(device));
-        for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+        if (open(2)) return KA_FAIL;
         if (dFams.alloc(nFam) || dRowFirst.alloc(rowFirst.size()) || dRows.alloc((size_t)bytes) || dNames.alloc(names.size()) ||
             dNameOff.alloc(nameOff.size()) || dFamOff.alloc((size_t)nFam + 1) || dRowOut.alloc((size_t)numseq + 1) || dOffender.alloc(1))
                 return fail(me + ": out of device memory");
@@ -307,8 +291,7 @@ int ka_out_fam::write(const std::string& me, int format, int lineLength, const f
         HIPCHK(hipEventRecord(ev[1], stream));
         HIPCHK(hipMemcpyAsync(out, dOut.p, (size_t)total, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipMemcpyAsync(&offender, dOffender.p, sizeof offender, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        nSync++;
+        if (wait()) return KA_FAIL;
         st[1] = ms();
         if (offender != KA_OUT_NONE) {
                 std::memset(out, 0, (size_t)total);              // no text is handed out
@@ -371,22 +354,16 @@ extern "C" int ka_out_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, c
         *out = nullptr;
         if (out_check(me, n_fam, fam_first, rows, alnlens, names, name_off)) return KA_FAIL;
         std::unique_ptr<ka_out_fam> h(new ka_out_fam);
-        if (ka_ctx_device_stream(ctx, &h->device, &h->stream)) return fail(me + ": bad context");
+        if (h->attach(ctx)) return fail(me + ": bad context");
         h->gap = (uint8_t)gap_char;
-        if (h->create(me, n_fam, fam_first, rows, alnlens, names, name_off)) {
-                (void)hipStreamSynchronize(h->stream);           // (nothing of the caller's is read after a refusal)
-                return KA_FAIL;
-        }
+        if (h->create(me, n_fam, fam_first, rows, alnlens, names, name_off)) return h->refused();
         *out = h.release();
         return KA_OK;
 }
 
 extern "C" void ka_out_fam_destroy(ka_out_fam* h)
 {
-        if (!h) return;
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        delete h;
+        ka_stage_destroy(h);
 }
 
 // ---- FASTA ----

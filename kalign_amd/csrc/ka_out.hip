@@ -15,15 +15,11 @@
 // All stores are plain C++ stores of the vector unit.
 #include "ka_out.h"
 #include "ka_msa.h"          // ka_fam_find
+#include "ka_walk.h"         // ka_wave_sum, ka_wave_grid (the row pass reads a prefix, not a row: its loads are its own)
 
 namespace {
 
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-        return v;
-}
+static_assert(KA_OUT_STEP == KA_WALK_STEP, "the row pass takes the walk's step");
 
 __global__ __launch_bounds__(KA_OUT_ROW_THREADS) void out_rows(KaOutTab a)
 {
@@ -52,7 +48,7 @@ __global__ __launch_bounds__(KA_OUT_ROW_THREADS) void out_rows(KaOutTab a)
                         chk += (c % 57 + 1) * (long long)(b >= 'a' && b <= 'z' ? b - 32 : b);
                 }
         }
-        chk = wave_sum(chk) % 10000;
+        chk = ka_wave_sum(chk) % 10000;
         if (lane == 0) {
                 a.recs[2 * r] = (int)chars;
                 a.recs[2 * r + 1] = (int)chk;
@@ -190,8 +186,7 @@ __global__ __launch_bounds__(KA_OUT_FILL_THREADS) void out_fill(KaOutTab a)
 
 void ka_out_run_rows(const KaOutTab& a, hipStream_t s, int* launches)
 {
-        constexpr int kRows = KA_OUT_ROW_THREADS / 64;
-        out_rows<<<(unsigned)(((long long)a.nRows + kRows - 1) / kRows), KA_OUT_ROW_THREADS, 0, s>>>(a);
+        out_rows<<<ka_wave_grid(a.nRows, KA_OUT_ROW_THREADS), KA_OUT_ROW_THREADS, 0, s>>>(a);
         ++*launches;
 }
 

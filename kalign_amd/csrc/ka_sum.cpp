@@ -17,19 +17,13 @@
 #include "ka_ctx.h"
 #include "ka_sum.h"
 
-int ka_ctx_device_stream(ka_ctx* c, int* device, hipStream_t* stream);    // (library-internal: ka_api.cpp)
-
 namespace {
 
 int sum_fam_check(const char* who, int n_fam, const int* fam_first, const uint8_t* rows, const int* alnlens)
 {
         const std::string me(who);
-        if (n_fam < 1 || !fam_first || !rows || !alnlens) return fail(me + ": bad arguments");
-        if (fam_first[0] != 0) return fail(me + ": fam_first does not ascend from 0 to numseq");
-        for (int f = 0; f < n_fam; f++) {
-                if (fam_first[f + 1] < fam_first[f]) return fail(me + ": fam_first does not ascend from 0 to numseq");
-                if (fam_first[f + 1] == fam_first[f]) return fail(me + ": empty family");
-        }
+        if (!rows || !alnlens) return fail(me + ": bad arguments");
+        if (ka_fam_check_first(me, n_fam, fam_first)) return KA_FAIL;
         long long cols = 0, items = 0;
         for (int f = 0; f < n_fam; f++) {
                 const std::string fam = me + ": family " + std::to_string(f);
@@ -50,12 +44,7 @@ int sum_fam_check(const char* who, int n_fam, const int* fam_first, const uint8_
 long long idm_entries(const char* who, int n_fam, const int* fam_first)
 {
         const std::string me(who);
-        if (n_fam < 1 || !fam_first) return fail(me + ": bad arguments"), -1;
-        if (fam_first[0] != 0) return fail(me + ": fam_first does not ascend from 0 to numseq"), -1;
-        for (int f = 0; f < n_fam; f++) {
-                if (fam_first[f + 1] < fam_first[f]) return fail(me + ": fam_first does not ascend from 0 to numseq"), -1;
-                if (fam_first[f + 1] == fam_first[f]) return fail(me + ": empty family"), -1;
-        }
+        if (ka_fam_check_first(me, n_fam, fam_first)) return -1;
         long long sum = 0;
         for (int f = 0; f < n_fam; f++) {
                 const long long N = fam_first[f + 1] - fam_first[f];
@@ -104,9 +93,7 @@ uint8_t ambiguous_of(const unsigned* present)
 
 } // namespace
 
-struct ka_sum_fam {
-        int device = 0;
-        hipStream_t stream = nullptr;
+struct ka_sum_fam : KaStage {
         uint8_t gap = '-';
         int nFam = 0, cols = 0, nTiles = 0, nItems = 0;
         long long bytes = 0;                   // of the packed rows
@@ -124,9 +111,9 @@ struct ka_sum_fam {
         DevBuf<unsigned long long> dFamSums;
         DevBuf<unsigned> dPresent;
         DevBuf<double> dThr;
-        hipEvent_t ev[2] = { nullptr, nullptr };
-        double st[KA_SUM_STATS] = {};          // device ms [0..3]; [4], [5] are filled from the counters below
-        int nLaunch = 0, nSync = 0;            // kernel launches (counted by the launchers, ka_sum.hip) and waits (wait()) of the last call that launches
+        // device ms [0..3]; [4], [5] are the counters of the last call that launches (create, consensus, keep, compact: begin()).
+        // The hand-outs (columns, summary, rows) are copies and leave the counters as they are.
+        double st[KA_SUM_STATS] = {};
         // the identity matrices: computed by the first ka_sum_fam_identity, then kept on the device
         bool haveIdm = false;
         long long idmEntries = 0;
@@ -147,27 +134,6 @@ struct ka_sum_fam {
         DevBuf<uint8_t> dUngap;
         double gapSt[KA_SUM_GAP_STATS] = {};   // ka_sum_fam_gap_stats
 
-        ~ka_sum_fam()
-        {
-                for (auto& e : ev)
-                        if (e) (void)hipEventDestroy(e);
-                dFams.release(); dFirst.release(); dNGap.release(); dNDistinct.release(); dTopCount.release(); dKeep.release(); dSrc.release();
-                dNewW.release(); dMasks.release(); dRows.release(); dTopChar.release(); dAmbiguous.release(); dCons.release(); dOut.release(); dSame.release();
-                dMaskOff.release(); dOutOff.release(); dFamSums.release(); dPresent.release(); dThr.release();
-                dIdmFirst.release(); dMatches.release(); dCompared.release(); dIdmTiles.release(); dIdentity.release();
-                dRowFirst.release(); dGapRecs.release(); dGapSums.release(); dUngapOff.release(); dUngap.release();
-        }
-        float ms() { float m = 0.0f; (void)hipEventElapsedTime(&m, ev[0], ev[1]); return m; }
-        // a call that launches (create, consensus, keep, compact): nothing launched, nothing waited for yet.  The hand-outs
-        // (columns, summary, rows) are copies and leave the counters as they are.
-        void begin() { nLaunch = nSync = 0; }
-        // the host waits for the stream: counted where it happens
-        int wait()
-        {
-                HIPCHK(hipStreamSynchronize(stream));
-                nSync++;
-                return KA_OK;
-        }
         KaSumTab tab() const
         {
                 KaSumTab a{};
@@ -219,8 +185,7 @@ int ka_sum_fam::create(const char* who, int n_fam, const int* fam_first, const u
         first[nFam] = nTiles; first[2 * nFam + 1] = cols; first[3 * nFam + 2] = nItems;
         famSums.assign((size_t)nFam * KA_SUM_FAMSUMS, 0);
         std::vector<unsigned> present((size_t)nFam * 8, 0);
-        HIPCHK(hipSetDevice(device));
-        for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+        if (open(2)) return KA_FAIL;
         if (dFams.alloc(nFam) || dFirst.alloc(first.size()) || dRows.alloc((size_t)bytes) || dNGap.alloc(cols) || dNDistinct.alloc(cols) ||
             dTopCount.alloc(cols) || dTopChar.alloc(cols) || dSame.alloc(cols) || dFamSums.alloc(famSums.size()) || dPresent.alloc(present.size()) ||
             dThr.alloc(nFam) || dAmbiguous.alloc(nFam) || dMaskOff.alloc(nFam) || dKeep.alloc(cols) || dSrc.alloc(cols) || dNewW.alloc(nFam) ||
@@ -300,7 +265,7 @@ extern "C" int ka_sum_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, c
         *out = nullptr;
         if (sum_fam_check("ka_sum_fam_create", n_fam, fam_first, rows, alnlens)) return KA_FAIL;
         std::unique_ptr<ka_sum_fam> h(new ka_sum_fam);
-        if (ka_ctx_device_stream(ctx, &h->device, &h->stream)) return fail("ka_sum_fam_create: bad context");
+        if (h->attach(ctx)) return fail("ka_sum_fam_create: bad context");
         h->gap = (uint8_t)gap_char;
         if (h->create("ka_sum_fam_create", n_fam, fam_first, rows, alnlens)) return KA_FAIL;
         *out = h.release();
@@ -309,10 +274,7 @@ extern "C" int ka_sum_fam_create(ka_ctx* ctx, int n_fam, const int* fam_first, c
 
 extern "C" void ka_sum_fam_destroy(ka_sum_fam* h)
 {
-        if (!h) return;
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        delete h;
+        ka_stage_destroy(h);
 }
 
 extern "C" int ka_sum_fam_columns(ka_sum_fam* h, int* n_gap, int* n_distinct, uint8_t* top_char, int* top_count, long long* same_pairs)

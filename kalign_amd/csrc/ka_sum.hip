@@ -30,6 +30,7 @@
 #include <algorithm>
 #include "ka_sum.h"
 #include "ka_msa.h"
+#include "ka_walk.h"
 
 namespace {
 
@@ -380,11 +381,9 @@ __global__ __launch_bounds__(KA_SUM_IDM_THREADS) void sum_identity(KaIdmTab a)
 }
 
 // ---- the walk along rows ------------------------------------------------------------------------------------------------
-// A wave per row, rows numbered flat over the batch (the family by ka_fam_find over the first-row table).  A step takes
-// KA_SUM_CHUNK columns as four ballots of 64, lane l of ballot q the column c0 + 64 q + l: a byte per lane, so that a row may
-// start at any byte, and the loads of all four go out before the first ballot.  A lane at or past column W loads nothing
-// and is neither a gap nor a character: the byte after a row, the next row and the end of the upload are never read.
-// Everything after the ballots is wave-uniform arithmetic on 64-bit masks.
+// A wave per row, rows numbered flat over the batch (the family by ka_fam_find over the first-row table), KA_SUM_CHUNK
+// columns a step (ka_walk.h, in int: a family holds fewer than 2^31 cells).  A lane at or past column W is neither a gap nor
+// a character.
 struct RowWalk {
         const uint8_t* row;
         int f, W;
@@ -400,23 +399,12 @@ __device__ __forceinline__ RowWalk row_walk(const KaGapTab& a, int r)
         return w;
 }
 
-// the bytes of one step, -1 at and past column W
-__device__ __forceinline__ void row_step(const RowWalk& w, int c0, int lane, int* b)
-{
-#pragma unroll
-        for (int q = 0; q < KA_SUM_CHUNK / 64; q++) {
-                const int c = c0 + 64 * q + lane;
-                b[q] = c < w.W ? (int)w.row[c] : -1;
-        }
-}
-
 // A row's record and its share of the family's sums.  Gap blocks: a block starts at a gap whose left neighbour is no gap --
 // inside a ballot the mask shifted by one, at its first column the carried bit, which says whether the last column of the
 // ballot before was a gap (so a block that crosses an edge is counted once, and one that ends at an edge is counted).  The
 // first and the last character of the row give leading and trailing; a row without a character has leading = trailing = W.
-// A workgroup's rows are consecutive, so those of one family are neighbours: their four sums are added up in LDS and go to
-// the family's by one 64-bit atomic each per family the workgroup meets (a family of thousands of rows would otherwise
-// queue one atomic per row on the same four addresses).
+// The four sums of a workgroup's rows are folded into the families' (ka_fold_families: a family of thousands of rows would
+// otherwise queue one atomic per row on the same four addresses).
 __global__ __launch_bounds__(KA_SUM_GAP_THREADS) void sum_gap_rows(KaGapTab a)
 {
         constexpr int kWaves = KA_SUM_GAP_THREADS / 64;
@@ -433,7 +421,7 @@ __global__ __launch_bounds__(KA_SUM_GAP_THREADS) void sum_gap_rows(KaGapTab a)
                 unsigned long long carry = 0;
                 for (int c0 = 0; c0 < w.W; c0 += KA_SUM_CHUNK) {
                         int b[KA_SUM_CHUNK / 64];
-                        row_step(w, c0, lane, b);
+                        ka_walk_step<KA_SUM_CHUNK>(w.row, w.W, c0, lane, b);
 #pragma unroll
                         for (int q = 0; q < KA_SUM_CHUNK / 64; q++) {
                                 const unsigned long long m = __ballot(b[q] == gap), k = __ballot(b[q] >= 0 && b[q] != gap);
@@ -457,14 +445,7 @@ __global__ __launch_bounds__(KA_SUM_GAP_THREADS) void sum_gap_rows(KaGapTab a)
         if (lane < KA_SUM_ROWREC) part[wave][lane] = sum;
         if (lane == 0) famOf[wave] = f;
         __syncthreads();
-        if (threadIdx.x >= KA_SUM_ROWREC) return;
-        long long acc = 0;
-        for (int w = 0; w < kWaves && famOf[w] >= 0; w++) {
-                acc += part[w][threadIdx.x];
-                if (w + 1 < kWaves && famOf[w + 1] == famOf[w]) continue;
-                if (acc) atomicAdd(&a.sums[(long long)famOf[w] * KA_SUM_GAPSUMS + threadIdx.x], (unsigned long long)acc);
-                acc = 0;
-        }
+        if (threadIdx.x < KA_SUM_ROWREC) ka_fold_families(part, famOf, threadIdx.x, a.sums, KA_SUM_GAPSUMS);
 }
 
 // flat over the columns of the batch: a column is gappy when more than half of its family's rows hold a gap, 2 nGap > N.
@@ -503,12 +484,12 @@ __global__ __launch_bounds__(KA_SUM_ROW_THREADS) void sum_ungap(KaGapTab a)
         if (n <= 0) return;                                      // (an all-gap row)
         const RowWalk w = row_walk(a, (int)r);
         const int gap = a.gap;
-        const unsigned long long below = (1ull << lane) - 1ull;
+        const unsigned long long below = ka_lanes_below(lane);
         uint8_t* o = a.out + a.off[r];
         long long run = 0;
         for (int c0 = 0; c0 < w.W && run < n; c0 += KA_SUM_CHUNK) {
                 int b[KA_SUM_CHUNK / 64];
-                row_step(w, c0, lane, b);
+                ka_walk_step<KA_SUM_CHUNK>(w.row, w.W, c0, lane, b);
 #pragma unroll
                 for (int q = 0; q < KA_SUM_CHUNK / 64; q++) {
                         const bool ch = b[q] >= 0 && b[q] != gap;
@@ -551,14 +532,13 @@ void ka_sum_run_gather(const KaSumTab& a, hipStream_t s, int* launches)
 {
         sum_offsets<<<1, 256, 0, s>>>(a);
         ++*launches;
-        sum_gather<<<(unsigned)(((long long)a.nItems + 3) / 4), 256, 0, s>>>(a);
+        sum_gather<<<ka_wave_grid(a.nItems, 256), 256, 0, s>>>(a);
         ++*launches;
 }
 
 void ka_sum_run_gaps(const KaGapTab& a, hipStream_t s, int* launches)
 {
-        constexpr int kRows = KA_SUM_GAP_THREADS / 64;
-        sum_gap_rows<<<(unsigned)(((long long)a.nRows + kRows - 1) / kRows), KA_SUM_GAP_THREADS, 0, s>>>(a);
+        sum_gap_rows<<<ka_wave_grid(a.nRows, KA_SUM_GAP_THREADS), KA_SUM_GAP_THREADS, 0, s>>>(a);
         ++*launches;
         sum_gappy<<<(unsigned)(((long long)a.cols + 255) / 256), 256, 0, s>>>(a);
         ++*launches;
@@ -566,8 +546,7 @@ void ka_sum_run_gaps(const KaGapTab& a, hipStream_t s, int* launches)
 
 void ka_sum_run_ungap(const KaGapTab& a, hipStream_t s, int* launches)
 {
-        constexpr int kRows = KA_SUM_ROW_THREADS / 64;
-        sum_ungap<<<(unsigned)(((long long)a.nRows + kRows - 1) / kRows), KA_SUM_ROW_THREADS, 0, s>>>(a);
+        sum_ungap<<<ka_wave_grid(a.nRows, KA_SUM_ROW_THREADS), KA_SUM_ROW_THREADS, 0, s>>>(a);
         ++*launches;
 }
 
